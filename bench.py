@@ -13,7 +13,12 @@ exits with the worst child's return code -- it never touches the GPU and never r
 A step = ONE cross-pseudo-supervision training iteration of the two VQ-UNets on B labelled +
 B unlabelled synthetic 512x512 images per GPU (6 forwards, 4 backwards, 2 Adam steps):
 "images" = the 2*B input images a step consumes per GPU.  Inputs are resident in HBM before the
-timed region.  Rank 0 prints ONE JSON line.  Extra objects:
+timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`); --dump-outputs DIR also writes
+what the last timed step computed as DIR/<name>.npy.  --full adds everything else the benchmark measures and checks, after the
+timed region (the multi-rank self-validation, the supervised / all-bf16 / event-bracketed steps, the per-kernel rooflines, the CPU
+baseline) -- the extra objects of the line:
   roofline     -- the hand-written distance+argmin kernel (vq_assign_f32_kernel): algorithmic flops
                   2*N*K*C of every launch inside the timed region / its HIP-event time, vs the fp32
                   MFMA peak (157.3 TF/s, MI355X_MICROARCH.md)
@@ -278,6 +283,15 @@ def measured_vq_clock(device, group):
             "workgroups": int(len(mhz))}
 
 
+def dump_outputs(out_dir: str, out: dict) -> None:
+    """What the timed path computed in its last step, as out_dir/<name>.npy: every value CPSTrainer.step returned to its caller
+    (losses, mIoU, learning rate), float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), torch.as_tensor(v).detach().double().cpu().numpy())
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: become the launcher.  Starts N fresh children of this same
     script, one per GPU, with the rendezvous variables torch.distributed.run would set; rank 0's stdout (the one JSON line) is this
@@ -335,13 +349,22 @@ def main():
                                                          "(32 at 512x512, 8 at 1024x1024)")
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS), help="BASELINE.json configs[1] / [2] / [3]; cfg3 = the metric's configuration")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the multi-rank self-validation, the VQ kernels' in-stream event timing "
+                         "(roofline, roofline_vq_bf16), the supervised / all-bf16 / roofline_conv steps, roofline_bn and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="timed region only: skip the all-bf16 step, the supervised step and the roofline_conv steps (profiler passes)")
+                    help="with --full: skip the all-bf16 step, the supervised step, the roofline_conv steps and the per-kernel runs "
+                         "after the timed region (profiler passes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--eval-amp", action="store_true",
                     help="run the two no-grad pseudo-label forwards under autocast too (all-bf16 step; NOT the reference's "
                          "precision: its trainers run them in fp32, outside autocast)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras = args.full and not args.no_extras
     wl = WORKLOADS[args.workload]
     if args.batch <= 0:
         args.batch = wl["batch"]
@@ -396,7 +419,7 @@ def main():
         note(f"warm-up step {i + 1}/{args.warmup} done")
     if multi:
         dist.barrier()
-    if rank == 0:
+    if rank == 0 and args.full:
         _hip.profile_begin(64 * args.steps)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -412,9 +435,12 @@ def main():
     elapsed = float(t.item())
     loss = float(out["loss"])
     note(f"{args.steps} timed steps done in {elapsed:.2f}s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
     dp_check = None
-    if multi:
-        # Self-validation of the N > 1 path in EVERY multi-rank run (RCCL on real GPUs as well as the gloo rehearsal):
+    if multi and args.full:
+        # Self-validation of the N > 1 path in every multi-rank --full run (RCCL on real GPUs as well as the gloo rehearsal):
         # after the same averaged updates every rank must hold bit-identical parameters -- checksums are all-gathered and compared --
         # and the gradient buckets must have been reduced from inside backward, in the same order on every rank.
         dev_c = device if not rehearsal else torch.device("cpu")
@@ -443,7 +469,7 @@ def main():
         note(f"rank {rank}: parameter checksums identical on all {dist.get_world_size()} ranks; buckets reduced inside backward: "
              f"{dp_check['buckets_reduced_in_backward']} of {dp_check['buckets']}")
 
-    recs_all = _hip.profile_collect(64 * args.steps, with_kind=True) if rank == 0 else []
+    recs_all = _hip.profile_collect(64 * args.steps, with_kind=True) if rank == 0 and args.full else []
     recs = [r[:4] for r in recs_all if r[4] != 2]              # the exact fp32-MFMA kernel (fp32 rows; bf16 rows without the filter)
     recs_f = [r[:4] for r in recs_all if r[4] == 2]            # the bf16 candidate filter + exact re-score (bf16 rows)
     # next to the CPS figure, plain forward + backward + Adam of ONE network on the B labelled images
@@ -453,7 +479,7 @@ def main():
     # (the gloo rehearsal moves every gradient through the host, ~9 s per CPS step, and its timings mean nothing: one repetition of
     # each extra leg and no warm-ups there -- what it checks is that every rank runs every leg)
     n_sup, n_conv = (1, 1) if rehearsal else (3, 2)
-    if not args.no_extras:
+    if extras:
         if not rehearsal:
             trainer.supervised_step(l_in, l_tg)
         torch.cuda.synchronize()
@@ -473,7 +499,7 @@ def main():
     # the all-bf16 variant of the step (pseudo-label forwards under autocast as well), reported NEXT to the headline: a build-side
     # speed mode, not the reference's precision -- `value` above is the step whose every forward has the reference's precision
     all_bf16_s = None
-    if args.dtype == "bf16" and not args.eval_amp and not args.no_extras:
+    if args.dtype == "bf16" and not args.eval_amp and extras:
         trainer.cfg.eval_amp = True
         if not rehearsal:
             one(0)
@@ -496,7 +522,7 @@ def main():
     # stream (with two streams a launch's in-stream time would include the other network's kernels sharing the chip).  Outside
     # the timed region: ~700 event pairs per step would perturb the headline.
     conv_recs = []
-    if not args.no_extras:
+    if extras:
         # EVERY rank runs these steps (they hold the gradient all-reduces: a rank that skipped them would leave the others
         # waiting in a collective); rank 0 alone brackets its launches with events
         was_two = trainer._two_streams
@@ -545,8 +571,8 @@ def main():
             traffic = None
             if (n_bf16 == 0 or "bf16" in tr) and (n_f32 == 0 or "f32" in tr):
                 traffic = round((n_bf16 * tr.get("bf16", 0) + n_f32 * tr.get("f32", 0)) / max(n_bf16 + n_f32, 1))
-            per_shape = vq_per_level(device, group, bf16_rows=False) if not args.no_extras else {}
-            clk = measured_vq_clock(device, group) if not args.no_extras else None
+            per_shape = vq_per_level(device, group, bf16_rows=False) if extras else {}
+            clk = measured_vq_clock(device, group) if extras else None
             roof = {"kernel": "vq_assign_f32_kernel", "bound": "mfma", "achieved": round(achieved, 2),
                     "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                     "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
@@ -623,8 +649,9 @@ def main():
                            "2 no-grad pseudo-label forwards": ("bf16 (--eval-amp: NOT the reference's precision)" if (args.eval_amp and args.dtype == "bf16")
                                                                else "fp32 (outside autocast, train_vqreptunet1x1v2.py:143-149)")},
                        "final_loss": round(loss, 5)},
-            "roofline": roof,
         }
+        if args.full:
+            line["roofline"] = roof
         if roof_f is not None:
             line["roofline_vq_bf16"] = roof_f
         if dp_check is not None:
@@ -678,13 +705,13 @@ def main():
                         "convolution's flops (they execute 3x that on the MFMA pipes); weight-gradient kernels are listed by_kind (kernel only, the slab "
                         "sums that follow are separate launches) and not part of achieved / whole_step_delivered; "
                         "whole_step_delivered = all convolution forward/data-gradient flops of a step / the headline's step time"}
-        if not args.no_extras:
+        if extras:
             line["roofline_bn"] = bn_roofline(device)
         if all_bf16_s is not None:
             line["all_bf16_step"] = {"images_per_sec": round(images / all_bf16_s, 3), "ms_per_step": round(all_bf16_s / args.steps * 1e3, 3),
                                      "what": "the same step with the two pseudo-label forwards under bf16 autocast too (CPSConfig.eval_amp=True); "
                                              "narrower than the reference's trainer there, so it is NOT the headline"}
-        if world == 1 and not args.no_cpu_baseline and wl["recipe"] == "v1":      # (the oracle's CPS iteration restates the v1 loop body)
+        if args.full and world == 1 and not args.no_cpu_baseline and wl["recipe"] == "v1":      # (the oracle's CPS iteration restates the v1 loop body)
             line["cpu_baseline"] = cpu_baseline(size, k_codes)
         print(json.dumps(line), flush=True)
     if multi:

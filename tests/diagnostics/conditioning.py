@@ -1,5 +1,5 @@
 """Conditioning of the whole-model fixture: how far a tiny input perturbation moves logits and gradients on the CPU oracle.\n   usage: python tests/diagnostics/conditioning.py <size> <eps>"""
-import sys; sys.path.insert(0,'/root/repo')
+import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from oracle import torch_ref as R
 from tests import cases, golden_io, synth

@@ -78,7 +78,7 @@ def test_bench_two_rank_rehearsal_with_extras_completes():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VQSEG_DIST_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "1"]
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "1", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-4000:]
     import json
@@ -96,7 +96,7 @@ def test_plain_bench_gpus_2_launches_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(VQSEG_DIST_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "1", "--no-extras"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "1", "--full", "--no-extras"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-4000:]
     lines = [ln for ln in res.stdout.strip().splitlines() if ln.startswith("{")]

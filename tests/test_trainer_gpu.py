@@ -151,3 +151,29 @@ def test_checkpoint_resume_is_bit_exact(tmp_path):
     # the file is the reference's layout: its loader returns model_2 (training) / model_1 (testing), utils/ckpoints.py:15-21
     m2, epoch, batch_idx, o1, o2 = load_ckpoints(path, True, map_location="cpu")
     assert (epoch, batch_idx) == (3, 7) and set(m2) == set(b.models[1].state_dict()) and "state" in o1 and "param_groups" in o2
+
+
+def test_two_runs_of_the_bench_step_are_bit_identical(monkeypatch):
+    """Same seed, same data: two trainers of the benchmark's configuration (512x512, B = 32 + 32, K = 512, bf16) return
+    bit-identical step results and hold bit-identical parameters after two steps (the convolution kernels' pipelined K loops
+    once let the next stage's LDS DMA overtake a wave's pending reads of the current one: a different sum every few runs)."""
+    import os
+    monkeypatch.setenv("MIOPEN_FIND_MODE", os.environ.get("MIOPEN_FIND_MODE", "FAST"))      # importing bench.py sets this default
+    import bench
+    from vq_seg_amd.trainer import CPSConfig, CPSTrainer, SyntheticCropWeed
+    dev = torch.device("cuda:0")
+    runs = []
+    for _ in range(2):
+        tr = CPSTrainer(CPSConfig(model=bench.model_cfg("cfg3"), recipe="v1", total_iters=3, amp_dtype=torch.bfloat16), dev)
+        data = SyntheticCropWeed(512, 32, dev, seed=42)
+        outs = []
+        for _ in range(2):
+            (l_in, l_tg), ul = data.labelled(), data.unlabelled()
+            outs.append({k: v.detach().cpu().clone() for k, v in tr.step(l_in, l_tg, ul).items()})
+        torch.cuda.synchronize()
+        runs.append((outs, [p.detach().cpu().clone() for m in tr.models for p in m.parameters()]))
+        del tr, data
+    (o1, p1), (o2, p2) = runs
+    for s, (a, b) in enumerate(zip(o1, o2)):
+        assert all(torch.equal(a[k], b[k]) for k in a), (s, {k: (float(a[k]), float(b[k])) for k in a if not torch.equal(a[k], b[k])})
+    assert all(torch.equal(x, y) for x, y in zip(p1, p2))

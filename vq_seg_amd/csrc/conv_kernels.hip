@@ -50,6 +50,17 @@ __device__ __forceinline__ void unpack8(const u32x4 a, float (&v)[8]) {      // 
 }
 __device__ __forceinline__ float bf16_round(float a) { return (float)((__bf16)a); }
 
+// Raw workgroup barrier of the software-pipelined K loops.  __builtin_amdgcn_s_barrier() alone is no memory barrier: the
+// compiler may move LDS reads of the stage just computed past it, and a wave's ds_reads may still be pending there -- while
+// another wave, released by the barrier, already DMAs the next stage into that same buffer (run-to-run differences).
+// The "memory" clobbers pin every load and store to its side of the barrier, lgkmcnt(0) retires this wave's LDS reads first;
+// vmcnt is left alone (the DMA of later stages stays in flight).
+__device__ __forceinline__ void stage_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
 // pixel row m -> (image n, offset inside the image): 32-bit division whenever the row count allows (a 64-bit
 // division is ~100 emulated instructions, which matters in layers whose whole K loop is one or two stages)
 __device__ __forceinline__ void split_row(long m, int hw, long M, int& n, int& rem) {
@@ -809,9 +820,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_igemm_glds_kernel(const Co
         for (int s = 0; s < n_stage; ++s) {
             stage(s, 0);
             __builtin_amdgcn_s_waitcnt(0x0F70);
-            __builtin_amdgcn_s_barrier();
+            stage_barrier();
             compute(0);
-            __builtin_amdgcn_s_barrier();
+            stage_barrier();
         }
     } else {
 #pragma unroll
@@ -821,7 +832,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_igemm_glds_kernel(const Co
     for (int s = 0; s < n_stage; ++s) {
         const int behind = n_stage - 1 - s;                // stages issued after stage s that may still be in flight
         wait_in_flight(behind < NBUF - 2 ? behind : NBUF - 2);
-        __builtin_amdgcn_s_barrier();
+        stage_barrier();
         if (s + NBUF - 1 < n_stage) stage(s + NBUF - 1, slot_i);
         compute(slot_c);
         slot_c = slot_c == NBUF - 1 ? 0 : slot_c + 1;
@@ -1215,7 +1226,7 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const ConvArgs p) {
         issue_chunk(0);
         for (int chunk = 0; chunk < n_chunks; ++chunk) {
             __builtin_amdgcn_s_waitcnt(0x0F70);                       // vmcnt(0): this chunk's patch and weights have landed
-            __builtin_amdgcn_s_barrier();                              // ... for every wave; the other buffers are free
+            stage_barrier();                              // ... for every wave; the other buffers are free
             if (chunk + 1 < n_chunks) issue_chunk(chunk + 1);
             const char* wb = wring + (chunk & 1) * (9 * WT_BYTES);
 #pragma unroll
@@ -1261,7 +1272,7 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const ConvArgs p) {
 #undef VM_CASE
                 default: __builtin_amdgcn_s_waitcnt(0x0F70); break;
             }
-            if (!(PATCH_ABL & 4)) __builtin_amdgcn_s_barrier();
+            if (!(PATCH_ABL & 4)) stage_barrier();
             auto issue_next = [&]() {
                 if (tap < PI && more && !(PATCH_ABL & 2)) issue_patch(chunk + 1, tap);
                 const int s2 = s + NBW - 1;
@@ -2571,7 +2582,7 @@ __global__ __launch_bounds__((Wg3<COT, CIT, S>::NW * 64)) void conv_wgrad3x3_ker
     for (int s = 0; s < ns; ++s) {
         const int behind = ns - 1 - s;
         wait_in_flight(behind < C::NBUF - 2 ? behind : C::NBUF - 2);
-        __builtin_amdgcn_s_barrier();
+        stage_barrier();
         if (s + C::NBUF - 1 < ns) stage(slot_i);
         compute(slot_c);
         slot_c = slot_c == C::NBUF - 1 ? 0 : slot_c + 1;
@@ -2782,7 +2793,7 @@ __global__ __launch_bounds__((Wg1<COT, CIT>::NW * 64)) void conv_wgrad1x1_kernel
     for (int s = 0; s < ns; ++s) {
         const int behind = ns - 1 - s;
         wait_in_flight(behind < C::NBUF - 2 ? behind : C::NBUF - 2);
-        __builtin_amdgcn_s_barrier();
+        stage_barrier();
         if (s + C::NBUF - 1 < ns) stage(slot_i);
         compute(slot_c);
         slot_c = slot_c == C::NBUF - 1 ? 0 : slot_c + 1;

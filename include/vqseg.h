@@ -538,6 +538,24 @@ int64_t vqseg_adam_work_items(int64_t numel, int k, int cout, int cin);
 int vqseg_adam_step_f32(const VqsegAdamParam* params_dev, const int32_t* items_dev, int n_items, double lr, double beta1,
                         double beta2, double eps, int64_t step, void* stream);
 
+/* ---------------------------------------------------------------------------------- *
+ * Batch assembly of the device-resident data loader (vq_seg_amd.data.DeviceLoader): the per-sample work of BaseDataset.__getitem__
+ * after its decode / resize (data/dataset.py:47-57: uint8 HWC -> float32 / 255, the raw uint8 mask) and of the loop's
+ * img_to_label (utils/seg_tools.py:3-8) for n samples cached in HBM.
+ *   img_cache           ragged uint8 cache: sample i's (h, w, 3) image at byte img_offsets_host[i] (HOST array of n offsets)
+ *   mask_cache          ragged uint8 cache: sample i's (mh, mw) mask at byte mask_offsets_host[i]; NULL for the unlabelled split
+ *   f32_lut    [256]    f32: the value of each byte (the host's uint8 -> float32 / 255, so the result does not depend on a division here)
+ *   label_lut  [256]    i64: img_to_label of each byte value; NULL: no label output
+ *   img_out    [n, h, w, 3]   f32 out (NHWC: torch channels_last of (n, 3, h, w))
+ *   target_out [n, mh, mw]    u8 out (NULL iff mask_cache is NULL);  label_out [n, mh, mw] i64 out (NULL iff label_lut is NULL)
+ * The offsets travel as kernel arguments (no host-to-device copy per batch); n above the argument block's capacity splits into
+ * several launches.  A wave moves a 1 KiB tile of one sample per iteration: whole tiles with 16-byte f32 stores that are contiguous
+ * across the wave (pointers 16-byte, offsets 4-byte aligned, the sample's output position a multiple of 4 elements), a sample's
+ * partial last tile (and any tile without that alignment) byte by byte.  Bit-exact by construction (a table lookup and copies). */
+int vqseg_batch_u8_f(int n, const uint8_t* img_cache, const uint8_t* mask_cache, const int64_t* img_offsets_host,
+                     const int64_t* mask_offsets_host, int h, int w, int mh, int mw, const float* f32_lut, const int64_t* label_lut,
+                     float* img_out, uint8_t* target_out, int64_t* label_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,7 @@ SYMBOLS = {
     "vqseg_s3_bilinear_f": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p]),
     "vqseg_adam_work_items": (c_int64, [c_int64, c_int, c_int, c_int]),
     "vqseg_adam_step_f32": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double, c_int64, c_void_p]),
+    "vqseg_batch_u8_f": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 6),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -494,6 +495,39 @@ def vq_ema_update(cluster_size: torch.Tensor, embed_avg: torch.Tensor, codebook:
                                        _dev(counts, torch.int64, "counts"), c, k, float(decay), float(eps), scratch.data_ptr(),
                                        _stream())
     _check(rc, "vqseg_vq_ema_update_f32")
+
+
+def batch_u8(img_cache: torch.Tensor, img_offsets, hw: Tuple[int, int], f32_lut: torch.Tensor, img_out: torch.Tensor,
+             mask_cache: Optional[torch.Tensor] = None, mask_offsets=None, mask_hw: Tuple[int, int] = (0, 0),
+             label_lut: Optional[torch.Tensor] = None, target_out: Optional[torch.Tensor] = None,
+             label_out: Optional[torch.Tensor] = None) -> None:
+    """Gather n cached uint8 samples into a batch (include/vqseg.h: vqseg_batch_u8_f): img_out (n, 3, h, w) f32 channels_last,
+    target_out (n, mh, mw) u8, label_out (n, mh, mw) i64.  Offsets are host sequences of byte offsets into the caches."""
+    import numpy as np
+    L = lib()
+    n = len(img_offsets)
+    (h, w), (mh, mw) = hw, mask_hw
+    io = np.ascontiguousarray(img_offsets, dtype=np.int64)
+    mo = np.ascontiguousarray(mask_offsets, dtype=np.int64) if mask_offsets is not None else None
+    if n and (int(io.min()) < 0 or int(io.max()) + h * w * 3 > img_cache.numel()):
+        raise HipLibraryError("batch_u8: an image offset lies outside the image cache")
+    if mask_cache is not None:
+        if mo is None or len(mo) != n:
+            raise HipLibraryError("batch_u8: one mask offset per sample required")
+        if n and (int(mo.min()) < 0 or int(mo.max()) + mh * mw > mask_cache.numel()):
+            raise HipLibraryError("batch_u8: a mask offset lies outside the mask cache")
+    if img_out.dim() != 4 or not img_out.is_contiguous(memory_format=torch.channels_last):
+        raise HipLibraryError("batch_u8: img_out must be a channels_last (n, 3, h, w) tensor")
+    dev = img_out.device
+    with on_device(dev):
+        rc = L.vqseg_batch_u8_f(n, tptr(img_cache, "img_cache", dtype=torch.uint8), tptr(mask_cache, "mask_cache", dtype=torch.uint8),
+                                io.ctypes.data, mo.ctypes.data if mo is not None else None, h, w, mh, mw,
+                                tptr(f32_lut, "f32_lut", dtype=torch.float32, numel=256),
+                                tptr(label_lut, "label_lut", dtype=torch.int64, numel=256),
+                                tptr(img_out, "img_out", dtype=torch.float32, numel=n * 3 * h * w),
+                                tptr(target_out, "target_out", dtype=torch.uint8, numel=n * mh * mw),
+                                tptr(label_out, "label_out", dtype=torch.int64, numel=n * mh * mw), _stream())
+    _check(rc, "vqseg_batch_u8_f")
 
 
 def profile_begin(capacity: int = 4096) -> None:

@@ -1694,6 +1694,7 @@ __global__ __launch_bounds__(256) void cast_kernel(const TI* __restrict__ x, lon
 // launchers
 // ---------------------------------------------------------------------------------------------
 static long g_grid_cap = 8192;                              // workgroups of the grid-stride elementwise kernels (option "nn_grid_cap")
+long nn_grid_cap() { return g_grid_cap; }                   // data_kernels.hip sizes its grid by the same cap
 static inline unsigned grid_for(long work, int per_block = 256, long cap = 0) {
     if (cap == 0) cap = g_grid_cap;
     long b = (work + per_block - 1) / per_block;

@@ -1,2 +1,3 @@
-"""Data path (reference: data/dataset.py:15-62 `BaseDataset`), SURVEY 8(f) row 4."""
+"""Data path (reference: data/dataset.py:15-62 `BaseDataset`); DeviceLoader feeds its batches from HBM."""
 from .dataset import BaseDataset, write_synthetic_dataset  # noqa: F401
+from .device_loader import DeviceLoader, f32_table, label_table  # noqa: F401

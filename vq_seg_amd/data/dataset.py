@@ -45,7 +45,9 @@ class BaseDataset(Dataset):
     def __len__(self):
         return len(self.filenames)
 
-    def __getitem__(self, index):
+    def _load_u8(self, index):
+        """The decoded, resized sample before TF.to_tensor's division: image uint8 (H, W, 3), mask uint8 (H, W) or None.
+        DeviceLoader caches these bytes; __getitem__ divides."""
         filename = self.filenames[index]
         img = Image.open(os.path.join(self.img_dir, filename)).convert("RGB")
         target = Image.open(os.path.join(self.target_dir, filename)).convert("L") if self.target_dir is not None else None
@@ -53,24 +55,34 @@ class BaseDataset(Dataset):
             img = img.resize(self.resize, resample=Image.BILINEAR)
             if self.target_resize and target is not None:
                 target = target.resize(self.resize, resample=Image.NEAREST)
-        img = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).permute(2, 0, 1).float().div_(255.0)   # TF.to_tensor
+        img = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy())
+        return img, (torch.from_numpy(np.array(target)) if target is not None else None)
+
+    def __getitem__(self, index):
+        img, target = self._load_u8(index)
+        img = img.permute(2, 0, 1).float().div_(255.0)   # TF.to_tensor
         if target is None:
-            return {"filename": filename, "img": img}
-        return {"filename": filename, "img": img, "target": torch.from_numpy(np.array(target))}
+            return {"filename": self.filenames[index], "img": img}
+        return {"filename": self.filenames[index], "img": img, "target": target}
 
 
 def write_synthetic_dataset(data_dir: str, n_labelled: int, n_unlabelled: int, size: int = 64, seed: int = 0, cell: int = 8,
                             pixel_values=(0, 128, 255)):
     """A CWFID-shaped folder of synthetic crop / weed blobs: class k's mask pixels carry pixel_values[k] (the reference configs'
-    `pixel_to_label` {"0": 0, "128": 1, "255": 2}), images are the class colours + noise (same recipe as trainer.SyntheticCropWeed)."""
+    `pixel_to_label` {"0": 0, "128": 1, "255": 2}), images are the class colours + noise (same recipe as trainer.SyntheticCropWeed).
+    `size`: an int for square files, or (w, h) -- PIL's order, as `resize` -- for non-square ones (e.g. CWFID's 1296 x 966)."""
     rng = np.random.default_rng(seed)
     palette = np.array([[0.25, 0.20, 0.15], [0.20, 0.55, 0.25], [0.55, 0.60, 0.20]])
     os.makedirs(os.path.join(data_dir, "input"), exist_ok=True)
     os.makedirs(os.path.join(data_dir, "target"), exist_ok=True)
+    w, h = (size, size) if isinstance(size, int) else size
     for i in range(n_labelled + n_unlabelled):
-        low = rng.integers(0, len(pixel_values), (max(size // cell, 1),) * 2)
-        lab = np.kron(low, np.ones((cell, cell), dtype=np.int64))[:size, :size]
-        img = np.clip(palette[lab] + 0.15 * rng.random((size, size, 3)), 0, 1)
+        if isinstance(size, int):
+            low = rng.integers(0, len(pixel_values), (max(size // cell, 1),) * 2)
+        else:
+            low = rng.integers(0, len(pixel_values), (-(-h // cell), -(-w // cell)))
+        lab = np.kron(low, np.ones((cell, cell), dtype=np.int64))[:h, :w]
+        img = np.clip(palette[lab] + 0.15 * rng.random((h, w, 3)), 0, 1)
         name = f"img_{i:04d}.png"
         Image.fromarray((img * 255).astype(np.uint8)).save(os.path.join(data_dir, "input", name))
         if i < n_labelled:

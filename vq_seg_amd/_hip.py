@@ -6,6 +6,7 @@ library, a CPU tensor, a wrong dtype or a non-zero return code raise.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -13,6 +14,7 @@ import time
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -129,6 +131,13 @@ class HipLibraryError(RuntimeError):
     pass
 
 
+def _bind_symbols(handle: ctypes.CDLL) -> ctypes.CDLL:
+    for name, (res, args) in SYMBOLS.items():
+        fn = getattr(handle, name)              # AttributeError if the symbol is missing
+        fn.restype, fn.argtypes = res, args
+    return handle
+
+
 def lib() -> ctypes.CDLL:
     """Load (once) and return the HIP library; raise if it is not built."""
     global _lib
@@ -137,10 +146,7 @@ def lib() -> ctypes.CDLL:
             raise HipLibraryError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"(or `make -C vq_seg_amd/csrc`). There is no CPU fallback.")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)          # AttributeError if the symbol is missing
-            fn.restype, fn.argtypes = res, args
+        handle = _bind_symbols(ctypes.CDLL(LIB_PATH))
         if handle.vqseg_abi_version() != 1:
             raise HipLibraryError("libvqseg_hip.so ABI version mismatch")
         for kv in filter(None, os.environ.get("VQSEG_OPTS", "").split(",")):     # dispatch tunables for A/B runs: "key=value,..."
@@ -253,7 +259,6 @@ def _dev(t: torch.Tensor, dtype: torch.dtype, name: str, numel: Optional[int] = 
 def on_device(dev):
     """`torch.cuda.device(dev)` for the launch; a no-op for a non-GPU device, so that the argument checks (tptr) are what raises
     when a CPU tensor reaches a wrapper."""
-    import contextlib
     dev = torch.device(dev) if not isinstance(dev, torch.device) else dev
     return torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()
 
@@ -309,18 +314,13 @@ def vq_forward(rows: torch.Tensor, codebook: torch.Tensor, training: bool, commi
 
 def bind(path: str) -> ctypes.CDLL:
     """another build of the same ABI (the per-workgroup timeline build) as a SECOND handle next to lib(): measurement code only"""
-    handle = ctypes.CDLL(path)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = res, args
-    return handle
+    return _bind_symbols(ctypes.CDLL(path))
 
 
 def vq_forward_group(rows_list, codebooks, prepared_list, training: bool, commitment_weights, handle=None):
     """vq_forward for several independent layers with ONE distance + argmin launch (vqseg_vq_forward_group).
     -> list of (quant, idx, loss (1,), dead_pct ()) per level; bit-identical to per-level vq_forward calls.
     `handle`: another build of the library (bind()), for measurement code."""
-    import numpy as np
     L = handle or lib()
     nl = len(rows_list)
     bf16 = rows_list[0].dtype == torch.bfloat16
@@ -503,7 +503,6 @@ def batch_u8(img_cache: torch.Tensor, img_offsets, hw: Tuple[int, int], f32_lut:
              label_out: Optional[torch.Tensor] = None) -> None:
     """Gather n cached uint8 samples into a batch (include/vqseg.h: vqseg_batch_u8_f): img_out (n, 3, h, w) f32 channels_last,
     target_out (n, mh, mw) u8, label_out (n, mh, mw) i64.  Offsets are host sequences of byte offsets into the caches."""
-    import numpy as np
     L = lib()
     n = len(img_offsets)
     (h, w), (mh, mw) = hw, mask_hw
@@ -540,7 +539,6 @@ def conv_profile_begin(capacity: int = 65536) -> None:
 
 def conv_profile_collect(capacity: int = 65536, with_shape: bool = False):
     """-> list of (algorithmic flops, kind = KH * 100 + {0 bf16, 1 precise, 2 split-3}, milliseconds) per convolution launch"""
-    import numpy as np
     fl = np.zeros(capacity, dtype=np.float64)
     kd = np.zeros(capacity, dtype=np.int32)
     ms = np.zeros(capacity, dtype=np.float32)
@@ -556,7 +554,6 @@ def conv_profile_collect(capacity: int = 65536, with_shape: bool = False):
 def profile_collect(capacity: int = 4096, with_kind: bool = False):
     """-> list of (n_rows, channels, n_codes, milliseconds[, kind]) for every assign launch since profile_begin
     (kind 0: exact kernel on f32 rows, 1: exact kernel on bf16 rows, 2: bf16 candidate filter + exact re-score)."""
-    import numpy as np
     n = np.zeros(capacity, dtype=np.int64)
     c = np.zeros(capacity, dtype=np.int32)
     k = np.zeros(capacity, dtype=np.int32)

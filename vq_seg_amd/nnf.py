@@ -9,6 +9,7 @@ Every function here has exactly one implementation; CPU tensors are refused (no 
 """
 from __future__ import annotations
 
+from collections import namedtuple
 import contextlib
 import ctypes
 from typing import Optional
@@ -97,7 +98,7 @@ def _pack_all(weight: torch.Tensor, kind):
         w = weight.detach()
         w = w if w.is_contiguous() else w.contiguous()
         cout, cin, k, _ = w.shape
-        cin_p, cout_p = (cin + 31) // 32 * 32, (cout + 31) // 32 * 32
+        cin_p, cout_p = _pad32(cin), _pad32(cout)
         s3k = next((kk for kk in kinds if isinstance(kk, tuple)), None)
         if s3k is not None and (cin % 32 or s3k[1] % 32):
             return None
@@ -141,22 +142,239 @@ def packed_weights(weight: torch.Tensor, precise: bool, transpose_flip: bool):
     return cache[k]
 
 
-def _conv_raw(x_rows, x2_rows, c1, w_hi, w_lo, out_shape, stat, n, h, w, cin, cout, kh, kw, stride, pad, reflect, up,
-              ho, wo, w_offset_elems=0):
+def _pad32(c: int) -> int:
+    return (c + 31) // 32 * 32
+
+
+def _packed_elems(rows: int, kh: int, kw: int, cols: int) -> int:
+    """elements of a packed weight image [rows][KH][KW][cols ^ 32] (vqseg_conv_packed_elems): THE size every kernel that reads one
+    is bounded by"""
+    return rows * kh * kw * _pad32(cols)
+
+
+class ConvGeom(namedtuple("ConvGeom", "n h w c1 cin cout kh kw stride pad reflect ho wo")):
+    """One convolution as the C entry points see it: input (n, h, w, cin) -- its first c1 channels from x, the rest from x2 -- to
+    output (n, ho, wo, cout).  A data gradient is one too (its input is the output gradient).  Immutable, compared by value."""
+    __slots__ = ()
+
+    @property
+    def m(self) -> int:
+        return self.n * self.ho * self.wo
+
+    @property
+    def packed(self) -> int:
+        return _packed_elems(self.cout, self.kh, self.kw, self.cin)
+
+
+class StemGeom(namedtuple("StemGeom", "kh kw cin stride pad reflect h w fused", defaults=(None,))):
+    """The 7x7 stem behind a 1x1 convolution over im2col patch columns: the kernel and the (h, w) image the patches come from.
+    `fused` = (ho, wo, kp): the forward reads the IMAGE (vqseg_stem7_conv_f) and only backward builds the patch matrix."""
+    __slots__ = ()
+
+    @property
+    def is_fused(self) -> bool:
+        return self.fused is not None
+
+
+# what two uses of a weight must share to go into one weight-gradient launch: everything but the batch size (geom.n = 0)
+_WgradKey = namedtuple("_WgradKey", "geom precise stem")
+
+
+_MODE_BF = (1, 0, 2)          # the convolutions' `precise` argument (0 bf16, 1 fp32 on split operands, 2 split-3 rows) -> tptr's `bf` flag
+
+
+def _stat_elems(m: int, cout: int) -> int:
+    return lib().vqseg_conv_stat_slots(m, cout) * 2 * cout
+
+
+def _conv_raw(x_rows, x2_rows, w_hi, w_lo, stat, g: ConvGeom, up=1, w_offset_elems=0):
+    """vqseg_conv2d_f -> y, BatchNorm partial sums into `stat`.  `up`: zero-dilation of the input (a strided layer's data gradient);
+    `w_offset_elems`: where the [Cout][KH][KW][Cin ^ 32] slice the kernel reads starts in the weight image."""
     precise = x_rows.dtype == torch.float32
-    y = torch.empty(out_shape, dtype=x_rows.dtype, device=x_rows.device)
+    y = torch.empty((g.n, g.ho, g.wo, g.cout), dtype=x_rows.dtype, device=x_rows.device)
     esz = 2
     bfa = 0 if precise else 1
-    wneed = w_offset_elems + cout * kh * kw * ((cin + 31) // 32 * 32)        # the [Cout][KH][KW][Cin ^ 32] slice the kernel reads
+    wneed = w_offset_elems + g.packed
+    nin = g.n * g.h * g.w
     with _hip.on_device(x_rows.device):
-        rc = lib().vqseg_conv2d_f(_T(x_rows, "conv input", bf=bfa, numel=n * h * w * c1), _T(x2_rows, "conv input 2", bf=bfa, numel=n * h * w * (cin - c1)),
-                                  c1, _w16(w_hi, "packed weights", wneed, at_least=True) + w_offset_elems * esz,
+        rc = lib().vqseg_conv2d_f(_T(x_rows, "conv input", bf=bfa, numel=nin * g.c1), _T(x2_rows, "conv input 2", bf=bfa, numel=nin * (g.cin - g.c1)),
+                                  g.c1, _w16(w_hi, "packed weights", wneed, at_least=True) + w_offset_elems * esz,
                                   (_w16(w_lo, "packed weights (lo)", wneed, at_least=True) + w_offset_elems * esz) if w_lo is not None else None,
-                                  _T(y, "conv output", bf=bfa, numel=n * ho * wo * cout),
-                                  _f32(stat, "BN partials", lib().vqseg_conv_stat_slots(n * ho * wo, cout) * 2 * cout if stat is not None else None),
-                                  n, h, w, cin, cout, kh, kw, stride, pad, int(reflect), up, ho, wo, int(precise), _stream())
+                                  _T(y, "conv output", bf=bfa, numel=g.m * g.cout),
+                                  _f32(stat, "BN partials", _stat_elems(g.m, g.cout) if stat is not None else None),
+                                  g.n, g.h, g.w, g.cin, g.cout, g.kh, g.kw, g.stride, g.pad, int(g.reflect), up, g.ho, g.wo, int(precise), _stream())
     _check(rc, "vqseg_conv2d_f")
     return y
+
+
+def _conv_affine(x_rows, x2_rows, w_hi, w_lo, scale, shift, res, relu, g: ConvGeom, mode: int):
+    """vqseg_conv2d_affine_f -> relu?(conv * scale + shift [+ res]) in one launch.  mode: the entry point's `precise` (_MODE_BF);
+    split-3 rows hold [hi | lo] (twice the channels in memory) and read the [w_hi | w_hi | w_lo] weight image."""
+    bf, f = _MODE_BF[mode], 2 if mode == 2 else 1
+    wneed = g.cout * g.kh * g.kw * 3 * g.cin if mode == 2 else g.packed
+    out = torch.empty((g.n, g.ho, g.wo, f * g.cout), dtype=_hip._BF_DTYPE[bf], device=x_rows.device)
+    nin = g.n * g.h * g.w * f
+    with _hip.on_device(x_rows.device):
+        _check(lib().vqseg_conv2d_affine_f(_T(x_rows, "conv input", bf=bf, numel=nin * g.c1), _T(x2_rows, "conv input 2", bf=bf, numel=nin * (g.cin - g.c1)),
+                                           g.c1, _w16(w_hi, "packed weights", wneed), _w16(w_lo, "packed weights (lo)", wneed),
+                                           _f32(scale, "scale", g.cout), _f32(shift, "shift", g.cout),
+                                           _T(res, "residual", bf=bf, numel=g.m * g.cout * f), int(relu), _T(out, "conv output", bf=bf, numel=g.m * g.cout * f),
+                                           g.n, g.h, g.w, g.cin, g.cout, g.kh, g.kw, g.stride, g.pad, int(g.reflect), g.ho, g.wo, mode, _stream()),
+               "vqseg_conv2d_affine_f")
+    return out
+
+
+def _conv_affine_bits(x_rows, w_hi, scale, shift, res, bits, g: ConvGeom):
+    """vqseg_conv2d_affine_bits_f (bf16, stride 1, zero padding) -> conv * scale + shift + res .* bits (a ReLU mask bit field)"""
+    out = torch.empty((g.n, g.ho, g.wo, g.cout), dtype=torch.bfloat16, device=x_rows.device)
+    with _hip.on_device(x_rows.device):
+        _check(lib().vqseg_conv2d_affine_bits_f(_T(x_rows, "conv input", bf=1, numel=g.n * g.h * g.w * g.cin), _w16(w_hi, "packed weights", g.packed),
+                                                _f32(scale, "scale", g.cout), _f32(shift, "shift", g.cout),
+                                                _T(res, "residual", bf=1, numel=g.m * g.cout),
+                                                _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=g.m * g.cout // 8),
+                                                _T(out, "conv output", bf=1, numel=g.m * g.cout), g.n, g.h, g.w, g.cin, g.cout, g.kh, g.kw, g.pad,
+                                                g.ho, g.wo, _stream()), "vqseg_conv2d_affine_bits_f")
+    return out
+
+
+def _stem7_conv(xr, w_img, stat, coef, relu, stem: StemGeom, cout: int, s3: bool = False):
+    """vqseg_stem7_conv_f -> the stem's output straight from the fp32 image rows: raw + BatchNorm partial sums (`stat`), or with the
+    affine + ReLU epilogue (`coef`); s3: [hi | lo] weights and output rows."""
+    n, f = xr.shape[0], 2 if s3 else 1
+    m = n * stem.fused[0] * stem.fused[1]
+    out = torch.empty((n, stem.fused[0], stem.fused[1], f * cout), dtype=torch.bfloat16, device=xr.device)
+    scale, shift = (coef[0], coef[1]) if coef is not None else (None, None)
+    with _hip.on_device(xr.device):
+        _check(lib().vqseg_stem7_conv_f(int(s3), _f32(xr, "image", n * stem.h * stem.w * stem.cin), _w16(w_img, "stem weight image", cout * f * 176),
+                                        _T(out, "conv output", bf=2 if s3 else 1, numel=m * cout * f),
+                                        _f32(stat, "BN partials", _stat_elems(m, cout) if stat is not None else None),
+                                        _f32(scale, "scale", cout), _f32(shift, "shift", cout), int(relu), n, stem.h, stem.w, int(stem.reflect),
+                                        _stream()), "vqseg_stem7_conv_f")
+    return out
+
+
+def _bn_finalize(stat, m, cout, gamma, beta, bn, training, dev):
+    """vqseg_bn_finalize_f -> coef (4, C) f32 = scale, shift, mean, invstd: from the convolution's partial sums (`stat`; training also
+    updates the running statistics and num_batches_tracked in the kernel) or, stat None, from the running statistics."""
+    coef = torch.empty(4, cout, dtype=torch.float32, device=dev)
+    with _hip.on_device(dev):
+        _check_fused_bn(lib().vqseg_bn_finalize_f(
+            _f32(stat, "BN partials", _stat_elems(m, cout) if stat is not None else None), m, cout, _f32(gamma, "bn.weight", cout),
+            _f32(beta, "bn.bias", cout), _f32(bn.running_mean, "bn.running_mean", cout), _f32(bn.running_var, "bn.running_var", cout),
+            float(bn.momentum), float(bn.eps), int(training), _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout),
+            _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout),
+            _T(bn.num_batches_tracked, "bn.num_batches_tracked", dtype=torch.int64, numel=1) if training else None,
+            _T(_bn_sync(bn, False), "bn sync", dtype=torch.int32) if training else None, _stream()), "vqseg_bn_finalize_f", bn)
+    return coef
+
+
+def _bn_apply(y, rr, coef, m, cout, relu):
+    """vqseg_bn_apply_f -> relu?(y * scale + shift [+ rr])"""
+    bf = _is_bf16(y)
+    out = torch.empty_like(y)
+    with _hip.on_device(y.device):
+        _check(lib().vqseg_bn_apply_f(bf, _T(y, "conv output", bf=bf, numel=m * cout), _T(rr, "residual", bf=bf, numel=m * cout),
+                                      _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout, int(relu),
+                                      _T(out, "BN output", bf=bf, numel=m * cout), _stream()), "vqseg_bn_apply_f")
+    return out
+
+
+def _bn_apply_bits(y, rr, coef, m, cout):
+    """vqseg_bn_apply_bits_f (bf16) -> relu(y * scale + shift + rr) and its ReLU mask as a bit field (1/16 of the output's bytes)"""
+    out = torch.empty_like(y)
+    bits = torch.empty(m * cout // 8, dtype=torch.uint8, device=y.device)
+    with _hip.on_device(y.device):
+        _check(lib().vqseg_bn_apply_bits_f(_T(y, "conv output", bf=1, numel=m * cout), _T(rr, "residual", bf=1, numel=m * cout),
+                                           _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout,
+                                           _T(out, "BN output", bf=1, numel=m * cout),
+                                           _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=m * cout // 8), _stream()), "vqseg_bn_apply_bits_f")
+    return out, bits
+
+
+def _bn_backward(g, out, bits, y, coef, gamma, m, cout, relu, training, sink, dgamma, dbeta, g_res, bn):
+    """vqseg_bn_backward_f / vqseg_bn_backward_bits_f (`bits`: the forward's ReLU mask bit field instead of its output) -> g_y; dgamma /
+    dbeta are written (sink: added to), g_res (if given) gets the residual branch's gradient.  Without a residual `out` is None: the
+    ReLU mask is recomputed from y with the forward's scale / shift."""
+    L = lib()
+    bf = _is_bf16(y)
+    g_y = torch.empty_like(y)
+    nws = L.vqseg_bn_backward_workspace_floats(m, cout)
+    ws = torch.empty(nws, dtype=torch.float32, device=y.device)
+    with _hip.on_device(y.device):
+        if bits is not None:
+            _check_fused_bn(L.vqseg_bn_backward_bits_f(
+                _T(g, "output gradient", bf=1, numel=m * cout), _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=m * cout // 8),
+                _T(y, "conv output", bf=1, numel=m * cout), _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout),
+                _f32(gamma.detach(), "bn.weight", cout), m, cout, int(training), int(sink), _f32(ws, "BN backward workspace", nws),
+                _f32(dgamma, "bn.weight.grad", cout), _f32(dbeta, "bn.bias.grad", cout),
+                _T(g_y, "conv output gradient", bf=1, numel=m * cout), _T(g_res, "residual gradient", bf=1, numel=m * cout),
+                _T(_bn_sync(bn, True), "bn sync", dtype=torch.int32), _stream()), "vqseg_bn_backward_bits_f", bn)
+        else:
+            _check_fused_bn(L.vqseg_bn_backward_f(
+                bf, _T(g, "output gradient", bf=bf, numel=m * cout), _T(out, "BN output", bf=bf, numel=m * cout),
+                _T(y, "conv output", bf=bf, numel=m * cout), _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout),
+                _f32(gamma.detach(), "bn.weight", cout), _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout, int(relu),
+                int(training), int(sink), _f32(ws, "BN backward workspace", nws), _f32(dgamma, "bn.weight.grad", cout),
+                _f32(dbeta, "bn.bias.grad", cout), _T(g_y, "conv output gradient", bf=bf, numel=m * cout),
+                _T(g_res, "residual gradient", bf=bf, numel=m * cout), _T(_bn_sync(bn, True), "bn sync", dtype=torch.int32), _stream()),
+                "vqseg_bn_backward_f", bn)
+    return g_y
+
+
+def _reflect_ring(g_y, t_hi, gp, dg: ConvGeom):
+    """vqseg_reflect_ring_f: the border ring of a 3x3 / stride-1 reflect-padded layer's data gradient `dg`, evaluated as a full
+    correlation and folded onto rows 1 / H-2 and columns 1 / W-2 of gp (the zero-padded data gradient) in place"""
+    n, h, w, c = dg.n, dg.ho, dg.wo, dg.cout
+    rbuf = torch.empty((n, 2 * (w + 2) + 2 * h, c), dtype=g_y.dtype, device=g_y.device)
+    with _hip.on_device(g_y.device):
+        _check(lib().vqseg_reflect_ring_f(_T(g_y, "conv output gradient", bf=1, numel=n * dg.h * dg.w * dg.cin), _w16(t_hi, "transposed image", dg.packed),
+                                          _T(rbuf, "gradient ring", bf=1, numel=rbuf.numel()), _T(gp, "input gradient", bf=1, numel=n * h * w * c),
+                                          n, h, w, dg.cin, c, _stream()), "vqseg_reflect_ring_f")
+
+
+def _reflect_fold(gp, g: ConvGeom, c: int):
+    """vqseg_reflect_fold_f: gradient of the reflect-padded (pad 1) input (n, h + 2, w + 2, c) -> gradient of the input (n, h, w, c);
+    zero padding: gp is that gradient already"""
+    if not g.reflect:
+        return gp
+    if g.pad != 1:
+        raise NotImplementedError("reflect-padding data gradient is implemented for pad == 1")
+    bf = _is_bf16(gp)
+    gx = torch.empty((g.n, g.h, g.w, c), dtype=gp.dtype, device=gp.device)
+    with _hip.on_device(gp.device):
+        _check(lib().vqseg_reflect_fold_f(bf, _T(gp, "padded input gradient", bf=bf, numel=g.n * (g.h + 2) * (g.w + 2) * c), g.n, g.h, g.w, c,
+                                          _T(gx, "input gradient", bf=bf, numel=g.n * g.h * g.w * c), _stream()), "vqseg_reflect_fold_f")
+    return gx
+
+
+def _dgrad_s2(g_y, s_hi, s_lo, acc, g: ConvGeom, c: int, gh: int, gw: int):
+    """vqseg_conv2d_dgrad_s2_f: data gradient (n, gh, gw, c) of the stride-2 layer `g` by parity classes of the output pixel, written
+    into a fresh tensor or accumulated into `acc` in place"""
+    L = lib()
+    bf = _is_bf16(g_y)
+    gp = acc if acc is not None else torch.empty((g.n, gh, gw, c), dtype=g_y.dtype, device=g_y.device)
+    with _hip.on_device(g_y.device):
+        sneed = L.vqseg_conv_packed_s2_elems(g.cout, c, g.kh)
+        _check(L.vqseg_conv2d_dgrad_s2_f(_T(g_y, "conv output gradient", bf=bf, numel=g.m * g.cout), _w16(s_hi, "parity-class image", sneed),
+                                         _w16(s_lo, "parity-class image (lo)", sneed), _T(gp, "input gradient", bf=bf, numel=g.n * gh * gw * c),
+                                         g.n, g.ho, g.wo, g.cout, c, g.kh, gh, gw, int(not bf), int(acc is not None), _stream()),
+               "vqseg_conv2d_dgrad_s2_f")
+    return gp
+
+
+def _dgrad_s2_fold(g_y, s_hi, g: ConvGeom, c: int):
+    """vqseg_conv2d_dgrad_s2_fold_f (bf16, 3x3 / stride 2 / pad 1): the four parity classes in ONE launch, written straight into the
+    unpadded gradient (reflect padding: the padded top row / left column go to a small ring behind the pixel rows and are added onto
+    row 1 / column 1) -- no (H+2) x (W+2) tensor, no fold / crop pass over it"""
+    L = lib()
+    rows = int(L.vqseg_conv2d_dgrad_s2_fold_rows(g.n, g.h, g.w, int(g.reflect)))
+    buf = torch.empty((rows, c), dtype=g_y.dtype, device=g_y.device)
+    with _hip.on_device(g_y.device):
+        _check(L.vqseg_conv2d_dgrad_s2_fold_f(_T(g_y, "conv output gradient", bf=1, numel=g.m * g.cout),
+                                              _w16(s_hi, "parity-class image", L.vqseg_conv_packed_s2_elems(g.cout, c, 3)),
+                                              _T(buf, "input gradient (+ ring)", bf=1, numel=rows * c),
+                                              g.n, g.ho, g.wo, g.cout, c, g.h, g.w, int(g.reflect), _stream()), "vqseg_conv2d_dgrad_s2_fold_f")
+    return buf[:g.n * g.h * g.w].view(g.n, g.h, g.w, c)
 
 
 def _bn_sync(bn, backward: bool):
@@ -221,36 +439,33 @@ def py_opt(key: str, default: int) -> int:
 _PENDING_WGRADS: set = set()
 
 
-def _wgrad_launch(geom, a, b, gw, accumulate, stream):
+def _wgrad_launch(key: _WgradKey, a, b, gw, accumulate, stream):
     """vqseg_conv2d_wgrad2_f over use `a` = (g_y, x, x2, n) [and use `b`] into gw; `stream`: the stream a queued use belongs to."""
-    h, w, c1, cin, ho, wo, cout, kh, kw, stride, pad, reflect, precise, patches_of = geom
+    g, precise, stem = key
     g_y, xr, x2r, n = a
     gb, xb, x2b, nb = b if b is not None else (None, None, None, 0)
     L = lib()
     dev = g_y.device
     bf = 0 if precise else 1
-    m = n * ho * wo
+    nout, nin = g.ho * g.wo * g.cout, g.h * g.w
     with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
-        if patches_of:
-            okh, okw, ocin = patches_of[0], patches_of[1], patches_of[2]
-            wkh = wkw = 1
-            im2col, cin_out, st_, pd_, rf_ = 1, ocin, 1, 0, 0
-            gnum = cout * ocin * okh * okw
+        if stem is not None:                                 # x is the stem's patch matrix: the gradient of the 7x7 weight itself
+            okh, okw, wkh, wkw = stem.kh, stem.kw, 1, 1
+            im2col, cin_out, st_, pd_, rf_ = 1, stem.cin, 1, 0, 0
         else:
-            okh, okw, wkh, wkw = kh, kw, kh, kw
-            im2col, cin_out, st_, pd_, rf_ = 0, cin, stride, pad, reflect
-            gnum = cout * cin * kh * kw
-        nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n + nb, h, w, cin, ho, wo, cout, wkh, wkw)
+            okh, okw, wkh, wkw = g.kh, g.kw, g.kh, g.kw
+            im2col, cin_out, st_, pd_, rf_ = 0, g.cin, g.stride, g.pad, int(g.reflect)
+        nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n + nb, g.h, g.w, g.cin, g.ho, g.wo, g.cout, wkh, wkw)
         wsw = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         with _hip.on_device(dev):
-            _check(L.vqseg_conv2d_wgrad2_f(_T(g_y, "conv output gradient", bf=bf, numel=m * cout), _T(xr, "conv input", bf=bf, numel=n * h * w * c1),
-                                           _T(x2r, "conv input 2", bf=bf, numel=n * h * w * (cin - c1)), n,
-                                           _T(gb, "conv output gradient (second use)", bf=bf, numel=nb * ho * wo * cout),
-                                           _T(xb, "conv input (second use)", bf=bf, numel=nb * h * w * c1),
-                                           _T(x2b, "conv input 2 (second use)", bf=bf, numel=nb * h * w * (cin - c1)), nb,
-                                           c1, h, w, cin, ho, wo, cout, okh, okw, st_, pd_, rf_, int(precise), cin_out, im2col, int(accumulate),
+            _check(L.vqseg_conv2d_wgrad2_f(_T(g_y, "conv output gradient", bf=bf, numel=n * nout), _T(xr, "conv input", bf=bf, numel=n * nin * g.c1),
+                                           _T(x2r, "conv input 2", bf=bf, numel=n * nin * (g.cin - g.c1)), n,
+                                           _T(gb, "conv output gradient (second use)", bf=bf, numel=nb * nout),
+                                           _T(xb, "conv input (second use)", bf=bf, numel=nb * nin * g.c1),
+                                           _T(x2b, "conv input 2 (second use)", bf=bf, numel=nb * nin * (g.cin - g.c1)), nb,
+                                           g.c1, g.h, g.w, g.cin, g.ho, g.wo, g.cout, okh, okw, st_, pd_, rf_, int(precise), cin_out, im2col, int(accumulate),
                                            _T(wsw, "wgrad workspace", dtype=torch.uint8, numel=nbytes), nbytes,
-                                           _f32(gw, "weight gradient", gnum), _stream()), "vqseg_conv2d_wgrad2_f")
+                                           _f32(gw, "weight gradient", g.cout * cin_out * okh * okw), _stream()), "vqseg_conv2d_wgrad2_f")
 
 
 def flush_pending_wgrads() -> int:
@@ -287,7 +502,7 @@ class GradLink:
         self.g = None
         self.closed = False
         self.leftover = None
-        self.bits = None            # r4: `g` is the block output's UNMASKED gradient, `bits` the ReLU mask of the block's last BatchNorm
+        self.bits = None            # `g` is the block output's UNMASKED gradient, `bits` the ReLU mask of the block's last BatchNorm
         self.takes_bits = False     # set by the first conv's forward: its data-gradient epilogue can apply `bits` itself
 
 
@@ -300,7 +515,7 @@ def _mask_with_bits(g, bits):
 
 
 # ------------------------------------------------------------------------------------------------
-# Fan-in fusion (r4).  A tensor with TWO consumers (an encoder feature feeds the next encoder stage AND the decoder / its VQ layer;
+# Fan-in fusion.  A tensor with TWO consumers (an encoder feature feeds the next encoder stage AND the decoder / its VQ layer;
 # the decoder output feeds the head AND the prototype loss) gets two gradients that autograd adds in a separate pass over the
 # tensor (5 such adds per backward pass, ~2 ms per training step).  With fusion on, the producer of the tensor tags it with a
 # GradLink (`t._vq_fanin`); the consumer whose backward runs FIRST deposits its gradient there (and returns nothing to autograd),
@@ -508,7 +723,7 @@ def _s3_weights(weight: torch.Tensor, c1: int, as_1x1_cols: int = 0) -> torch.Te
 
 def _conv_bn_act_s3(x: "S3", x2, residual, conv, bn, relu, kernel_1x1_cols: int = 0) -> "S3":
     """eval-mode Conv -> BN -> [+ residual] -> [ReLU] on split-3 tensors: the convolution's fused epilogue (precise = 2)."""
-    n, h, w, c3 = x.rows.shape
+    n, h, w, _ = x.rows.shape
     c1 = x.c
     x2s = to_s3(x2) if x2 is not None else None
     cin = c1 + (x2s.c if x2s is not None else 0)
@@ -520,366 +735,296 @@ def _conv_bn_act_s3(x: "S3", x2, residual, conv, bn, relu, kernel_1x1_cols: int 
         kh, kw = conv.weight.shape[2], conv.weight.shape[3]
         stride, pad = conv.stride[0], conv.padding[0]
         reflect = conv.padding_mode == "reflect" and pad > 0
-    ho, wo = _out_size(h, kh, stride, pad), _out_size(w, kw, stride, pad)
-    dev = x.rows.device
-    L = lib()
+    g = ConvGeom(n, h, w, c1, cin, cout, kh, kw, stride, pad, reflect, _out_size(h, kh, stride, pad), _out_size(w, kw, stride, pad))
     wimg = _s3_weights(conv.weight, c1, kernel_1x1_cols)
     res = to_s3(residual) if residual is not None else None
-    coef = torch.empty(4, cout, dtype=torch.float32, device=dev)
-    out = torch.empty((n, ho, wo, 2 * cout), dtype=torch.bfloat16, device=dev)
-    with _hip.on_device(dev):
-        _check(L.vqseg_bn_finalize_f(None, n * ho * wo, cout, _f32(bn.weight, "bn.weight", cout), _f32(bn.bias, "bn.bias", cout),
-                                     _f32(bn.running_mean, "bn.running_mean", cout), _f32(bn.running_var, "bn.running_var", cout),
-                                     float(bn.momentum), float(bn.eps), 0, _f32(coef[0], "scale", cout),
-                                     _f32(coef[1], "shift", cout), _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout), None, None, _stream()),
-               "vqseg_bn_finalize_f")
-        _check(L.vqseg_conv2d_affine_f(_T(x.rows, "split-3 input", bf=2, numel=n * h * w * 2 * c1),
-                                       _T(x2s.rows, "split-3 input 2", bf=2, numel=n * h * w * 2 * (cin - c1)) if x2s is not None else None, c1,
-                                       _w16(wimg, "split-3 image", cout * kh * kw * 3 * cin), None,
-                                       _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout),
-                                       _T(res.rows, "split-3 residual", bf=2, numel=n * ho * wo * 2 * cout) if res is not None else None, int(relu),
-                                       _T(out, "split-3 output", bf=2, numel=n * ho * wo * 2 * cout), n, h, w, cin, cout, kh, kw, stride, pad,
-                                       int(reflect), ho, wo, 2, _stream()),
-               "vqseg_conv2d_affine_f (split-3)")
+    coef = _bn_finalize(None, g.m, cout, bn.weight, bn.bias, bn, False, x.rows.device)
+    out = _conv_affine(x.rows, x2s.rows if x2s is not None else None, wimg, None, coef[0], coef[1], res.rows if res is not None else None,
+                       relu, g, 2)
     return S3(out, cout)
 
 
 # ------------------------------------------------------------------------------------------------
 # Conv (no bias) -> BatchNorm -> [+ residual] -> [ReLU], optional channel concat of two inputs
 # ------------------------------------------------------------------------------------------------
+def _residual_rows(residual, dtype):
+    rr = _rows(residual) if residual is not None else None
+    if rr is not None and rr.dtype != dtype:
+        raise _hip.HipLibraryError("residual dtype differs from the activation dtype")
+    return rr
+
+
+def _forward_eval(xr, x2r, residual, w_hi, w_lo, gamma, beta, bn, relu, g: ConvGeom, bf, stem):
+    """eval-mode BatchNorm is a fixed per-channel affine map: it rides in the convolution's epilogue together with the residual add
+    and the ReLU (the no-grad pseudo-label passes; nothing is kept for a backward)"""
+    rr = _residual_rows(residual, xr.dtype)
+    coef = _bn_finalize(None, g.m, g.cout, gamma, beta, bn, False, xr.device)
+    if stem is not None and stem.is_fused:
+        return _stem7_conv(xr, w_hi, None, coef, relu, stem, g.cout)
+    return _conv_affine(xr, x2r, w_hi, w_lo, coef[0], coef[1], rr, relu, g, int(not bf))
+
+
 class _ConvBNAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, x2, residual, weight, gamma, beta, bn, stride, pad, reflect, relu, patches_of, fuse_eval=False,
+    def forward(ctx, x, x2, residual, weight, gamma, beta, bn, stride, pad, reflect, relu, stem, fuse_eval=False,
                 link_in=None, link_out=None, link_x=None, fan_x=None, fan_x2=None):
-        """x (N,C1,H,W) [+ x2 (N,C2,H,W)] -> out (N,Cout,Ho,Wo).  `patches_of` = (kh, kw, cin, stride, pad, reflect,
-        H, W) when x is an im2col patch matrix of the stem (then the convolution itself is 1x1)."""
+        """x (N,C1,H,W) [+ x2 (N,C2,H,W)] -> out (N,Cout,Ho,Wo).  `stem` (a StemGeom): x is the stem's im2col patch matrix and the
+        convolution itself 1x1 -- or, `stem.is_fused`, x is the fp32 IMAGE: the convolution gathers its operands from it
+        (vqseg_stem7_conv_f, bit-identical to the 1x1 convolution over the patch matrix), the activations are bf16, and backward
+        builds the patch matrix for the weight gradient (shared between the two networks like the forward's)."""
         xr = _rows(x)
         x2r = _rows(x2) if x2 is not None else None
         bf = _is_bf16(xr)
-        precise = not bf
         n, h, w, c1 = xr.shape
-        # r4, the stem without its patch matrix (patches_of[8] = (ho, wo, kp)): x is the fp32 IMAGE; the convolution gathers its operands
-        # from it (vqseg_stem7_conv_f, bit-identical to the 1x1 convolution over the patch matrix), the activations are bf16; backward
-        # builds the patch matrix for the weight gradient then (shared between the two networks as before)
-        stem_img = bool(patches_of) and len(patches_of) > 8
+        fused = stem is not None and stem.is_fused
         stem_x = None
-        if stem_img:
+        if fused:
             stem_x, _STEM_X_ARG[0] = _STEM_X_ARG[0], None
-            h, w, c1 = patches_of[8]
-            bf, precise = True, False
-        adt = torch.bfloat16 if stem_img else xr.dtype      # activation dtype of y / out
+            (h, w, c1), bf = stem.fused, 1
         cin = c1 + (x2r.shape[3] if x2r is not None else 0)
         cout = weight.shape[0]
-        kh, kw = (1, 1) if patches_of else (weight.shape[2], weight.shape[3])
-        ho, wo = _out_size(h, kh, stride, pad), _out_size(w, kw, stride, pad)
-        m = n * ho * wo
+        kh, kw = (1, 1) if stem is not None else (weight.shape[2], weight.shape[3])
+        g = ConvGeom(n, h, w, c1, cin, cout, kh, kw, stride, pad, bool(reflect), _out_size(h, kh, stride, pad), _out_size(w, kw, stride, pad))
         training = bool(bn.training)
-        L = lib()
-        dev = xr.device
-        if stem_img:
+        if fused:
             w_hi, w_lo = _stem_weights_fused(weight, False), None
-        elif patches_of:
-            w_hi, w_lo = _stem_weights(weight, precise, cin)
+        elif stem is not None:
+            w_hi, w_lo = _stem_weights(weight, not bf, cin)
         else:
-            w_hi, w_lo = packed_weights(weight, precise, False)
-        coef = torch.empty(4, cout, dtype=torch.float32, device=dev)       # scale, shift, mean, invstd
+            w_hi, w_lo = packed_weights(weight, not bf, False)
         if bn.momentum is None:
             raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative average) is not used by the path")
         if fuse_eval and not training:
-            # eval-mode BatchNorm is a fixed per-channel affine map: it rides in the convolution's epilogue together with
-            # the residual add and the ReLU (the no-grad pseudo-label passes; nothing is kept for a backward)
-            rr = _rows(residual) if residual is not None else None
-            if rr is not None and rr.dtype != xr.dtype:
-                raise _hip.HipLibraryError("residual dtype differs from the activation dtype")
-            out = torch.empty((n, ho, wo, cout), dtype=adt, device=dev)
-            wneed = cout * kh * kw * ((cin + 31) // 32 * 32)
-            with _hip.on_device(dev):
-                _check(L.vqseg_bn_finalize_f(None, m, cout, _f32(gamma, "bn.weight", cout), _f32(beta, "bn.bias", cout),
-                                             _f32(bn.running_mean, "bn.running_mean", cout), _f32(bn.running_var, "bn.running_var", cout),
-                                             float(bn.momentum), float(bn.eps), 0, _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout),
-                                             _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout), None, None, _stream()), "vqseg_bn_finalize_f")
-                if stem_img:
-                    _check(L.vqseg_stem7_conv_f(0, _f32(xr, "image"), _w16(w_hi, "stem weight image", cout * 176), _T(out, "conv output", bf=1, numel=m * cout), None,
-                                                _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), int(relu), n, patches_of[6], patches_of[7],
-                                                int(patches_of[5]), _stream()), "vqseg_stem7_conv_f")
-                    return _nchw(out)
-                _check(L.vqseg_conv2d_affine_f(_T(xr, "conv input", bf=bf, numel=n * h * w * c1), _T(x2r, "conv input 2", bf=bf, numel=n * h * w * (cin - c1)),
-                                               c1, _w16(w_hi, "packed weights", wneed), _w16(w_lo, "packed weights (lo)", wneed),
-                                               _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout),
-                                               _T(rr, "residual", bf=bf, numel=m * cout), int(relu), _T(out, "conv output", bf=bf, numel=m * cout),
-                                               n, h, w, cin, cout, kh, kw, stride, pad, int(reflect), ho, wo, int(precise), _stream()),
-                       "vqseg_conv2d_affine_f")
-            return _nchw(out)
-        stat = torch.empty(L.vqseg_conv_stat_slots(m, cout) * 2 * cout, dtype=torch.float32, device=dev) if training else None
-        if stem_img:
-            y = torch.empty((n, ho, wo, cout), dtype=adt, device=dev)
-            with _hip.on_device(dev):
-                _check(L.vqseg_stem7_conv_f(0, _f32(xr, "image"), _w16(w_hi, "stem weight image", cout * 176),
-                                            _T(y, "conv output", bf=1, numel=m * cout), _f32(stat, "BN partials"), None, None, 0, n, patches_of[6],
-                                            patches_of[7], int(patches_of[5]), _stream()), "vqseg_stem7_conv_f")
+            return _nchw(_forward_eval(xr, x2r, residual, w_hi, w_lo, gamma, beta, bn, relu, g, bf, stem))
+        stat = torch.empty(_stat_elems(g.m, cout), dtype=torch.float32, device=xr.device) if training else None
+        y = _stem7_conv(xr, w_hi, stat, None, False, stem, cout) if fused else _conv_raw(xr, x2r, w_hi, w_lo, stat, g)
+        coef = _bn_finalize(stat, g.m, cout, gamma, beta, bn, training, xr.device)          # scale, shift, mean, invstd
+        rr = _residual_rows(residual, y.dtype)
+        # residual layers in bf16: the ReLU mask goes to the backward as a bit field (1/16 of `out`'s bytes), see vqseg.h
+        if rr is not None and relu and bf and cout % 8 == 0 and training and any(ctx.needs_input_grad) and py_opt("py_bn_bits", 1):
+            out, bits = _bn_apply_bits(y, rr, coef, g.m, cout)
         else:
-            y = _conv_raw(xr, x2r, c1, w_hi, w_lo, (n, ho, wo, cout), stat, n, h, w, cin, cout, kh, kw, stride, pad, reflect, 1,
-                          ho, wo)
-        with _hip.on_device(dev):
-            _check_fused_bn(L.vqseg_bn_finalize_f(_f32(stat, "BN partials"), m, cout, _f32(gamma, "bn.weight", cout), _f32(beta, "bn.bias", cout),
-                                         _f32(bn.running_mean, "bn.running_mean", cout), _f32(bn.running_var, "bn.running_var", cout),
-                                         float(bn.momentum), float(bn.eps), int(training), _f32(coef[0], "scale", cout),
-                                         _f32(coef[1], "shift", cout), _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout),
-                                         _T(bn.num_batches_tracked, "bn.num_batches_tracked", dtype=torch.int64, numel=1) if training else None,
-                                         _T(_bn_sync(bn, False), "bn sync", dtype=torch.int32) if training else None,
-                                         _stream()),   # += 1 in the kernel
-                   "vqseg_bn_finalize_f", bn)
-            rr = _rows(residual) if residual is not None else None
-            if rr is not None and rr.dtype != y.dtype:
-                raise _hip.HipLibraryError("residual dtype differs from the activation dtype")
-            out = torch.empty_like(y)
-            # residual layers in bf16: the ReLU mask goes to the backward as a bit field (1/16 of `out`'s bytes), see vqseg.h
-            bits = (torch.empty(m * cout // 8, dtype=torch.uint8, device=dev)
-                    if (rr is not None and relu and bf and cout % 8 == 0 and training and any(ctx.needs_input_grad)
-                        and py_opt("py_bn_bits", 1)) else None)
-            if bits is not None:
-                _check(L.vqseg_bn_apply_bits_f(_T(y, "conv output", bf=1, numel=m * cout), _T(rr, "residual", bf=1, numel=m * cout),
-                                               _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout,
-                                               _T(out, "BN output", bf=1, numel=m * cout),
-                                               _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=m * cout // 8), _stream()),
-                       "vqseg_bn_apply_bits_f")
-            else:
-                _check(L.vqseg_bn_apply_f(bf, _T(y, "conv output", bf=bf, numel=m * cout), _T(rr, "residual", bf=bf, numel=m * cout),
-                                          _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout, int(relu),
-                                          _T(out, "BN output", bf=bf, numel=m * cout), _stream()), "vqseg_bn_apply_f")
+            out, bits = _bn_apply(y, rr, coef, g.m, cout, relu), None
         ctx.mask_bits = bits is not None
-        if link_in is not None:                                             # see backward: the zero-padded stride-1 data gradient + shortcut
+        if link_in is not None:                                             # see _dgrad_shortcut: the zero-padded stride-1 data gradient + shortcut
             link_in.takes_bits = bool(bf and x2r is None and stride == 1 and not reflect and cin % 8 == 0 and py_opt("py_gres_bits", 1))
         ctx.save_for_backward(xr, x2r, y, bits if bits is not None else out, coef, weight, gamma)
-        ctx.stem_x = stem_x if stem_img else None                           # the image tensor OBJECT the patch matrix is shared under
+        ctx.stem_x = stem_x                                                 # the image tensor OBJECT the patch matrix is shared under
         ctx.params = (weight, gamma, beta)                                  # the Parameter objects (see grad sinks)
         ctx.bn = bn
         ctx.links = (link_in, link_out, link_x)
         ctx.fans = (fan_x, fan_x2)                                          # fan-in links: absorb into x's gradient / deposit x2's
-        ctx.cfg = (stride, pad, bool(reflect), bool(relu), training, residual is not None, patches_of, (n, h, w, c1, cin, cout,
-                                                                                                         kh, kw, ho, wo))
+        ctx.geom, ctx.stem = g, stem
+        ctx.relu, ctx.training, ctx.has_res = bool(relu), training, residual is not None
         return _nchw(out)
 
     @staticmethod
     def backward(ctx, g_out):
         xr, x2r, y, out, coef, weight, gamma = ctx.saved_tensors
-        stride, pad, reflect, relu, training, has_res, patches_of, (n, h, w, c1, cin, cout, kh, kw, ho, wo) = ctx.cfg
-        L = lib()
-        dev = y.device
-        if patches_of and len(patches_of) > 8:                              # forward ran from the image: the weight gradient's patch matrix now
+        g, stem = ctx.geom, ctx.stem
+        if stem is not None and stem.is_fused:                              # forward ran from the image: the weight gradient's patch matrix now
             img = xr
-            okh, okw, ocin, os_, op_, orf, ih_, iw_ = patches_of[:8]
-            xr = _shared_stem_patches(ctx.stem_x if ctx.stem_x is not None else img, (torch.bfloat16, okh, okw, os_, op_, orf),
-                                      lambda: _stem_patches(img, torch.bfloat16, okh, okw, os_, op_, orf, ho, wo, cin))
-        bf = _is_bf16(y)
-        precise = not bf
-        m = n * ho * wo
-        g = _rows(g_out)
-        if g.dtype != y.dtype:
-            g = g.to(y.dtype)
-        g_y = torch.empty_like(y)
-        link_in, link_out, link_x = ctx.links
-        # r4: the residual branch's gradient g_out .* mask is not stored when the block's first conv will apply the mask bits itself
-        bits_to_link = bool(has_res and ctx.mask_bits and link_out is not None and link_out.takes_bits and not link_out.closed)
-        g_res = torch.empty_like(y) if (has_res and not bits_to_link) else None
-        ws = torch.empty(L.vqseg_bn_backward_workspace_floats(m, cout), dtype=torch.float32, device=dev)
-        p_w, p_g, p_b = ctx.params
-        sink_bn = _sink_ready(p_g) and _sink_ready(p_b) and ctx.needs_input_grad[4] and ctx.needs_input_grad[5]
-        sink_w = _sink_ready(p_w) and ctx.needs_input_grad[3]
-        dgb = None if sink_bn else torch.empty(2, cout, dtype=torch.float32, device=dev)
-        dgamma, dbeta = (p_g.grad, p_b.grad) if sink_bn else (dgb[0], dgb[1])
-        with _hip.on_device(dev):
-            # without a residual the ReLU mask is recomputed from y with the forward's scale / shift: `out` is not re-read
-            if ctx.mask_bits:                                               # `out` holds the forward's mask bits here
-                _check_fused_bn(L.vqseg_bn_backward_bits_f(
-                    _T(g, "output gradient", bf=1, numel=m * cout), _T(out, "ReLU mask bits", dtype=torch.uint8, numel=m * cout // 8),
-                    _T(y, "conv output", bf=1, numel=m * cout), _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout),
-                    _f32(gamma.detach(), "bn.weight", cout), m, cout, int(training), int(sink_bn), _f32(ws, "BN backward workspace"),
-                    _f32(dgamma, "bn.weight.grad", cout), _f32(dbeta, "bn.bias.grad", cout),
-                    _T(g_y, "conv output gradient", bf=1, numel=m * cout), _T(g_res, "residual gradient", bf=1, numel=m * cout),
-                    _T(_bn_sync(ctx.bn, True), "bn sync", dtype=torch.int32), _stream()), "vqseg_bn_backward_bits_f", ctx.bn)
-            else:
-                _check_fused_bn(L.vqseg_bn_backward_f(bf, _T(g, "output gradient", bf=bf, numel=m * cout),
-                                           _T(out, "BN output", bf=bf, numel=m * cout) if has_res else None, _T(y, "conv output", bf=bf, numel=m * cout),
-                                           _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout), _f32(gamma.detach(), "bn.weight", cout),
-                                           _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout, int(relu), int(training), int(sink_bn),
-                                           _f32(ws, "BN backward workspace"), _f32(dgamma, "bn.weight.grad", cout), _f32(dbeta, "bn.bias.grad", cout),
-                                           _T(g_y, "conv output gradient", bf=bf, numel=m * cout), _T(g_res, "residual gradient", bf=bf, numel=m * cout),
-                                           _T(_bn_sync(ctx.bn, True), "bn sync", dtype=torch.int32), _stream()), "vqseg_bn_backward_f", ctx.bn)
-        if sink_bn:
-            _sink_done(p_g), _sink_done(p_b)
-        if link_out is not None and has_res:
-            link_out.g = g if bits_to_link else g_res                       # picked up by the block's first conv (GradLink)
-            link_out.bits = out if bits_to_link else None
-        # ---- weight gradient.  With a grad sink (the result is ADDED into the trainer's bucket, nothing returns to autograd) and a
-        # registered side stream, the weight-gradient kernel and its slab sum leave the network's stream: nothing downstream in
-        # backward depends on them, and as filler work they cover the latency-bound links of the main chain (BatchNorm statistics
-        # folds, finalizes, packs: skipping those ~950 launches -- wrong results, timing only -- was worth 11 ms of a 163 ms step)
-        gw = p_w.grad if sink_w else torch.empty(weight.shape, dtype=torch.float32, device=dev)
-        wside = _wgrad_side_stream(dev) if sink_w else None
-        if wside is not None:
-            main_s = torch.cuda.current_stream(dev)
-            wside.wait_event(main_s.record_event())                             # g_y (bn_backward above) is complete
-            for t_ in (g_y, xr, x2r):
-                if t_ is not None:
-                    t_.record_stream(wside)                                     # allocator: not reusable before the side stream is done
-        geom = (h, w, c1, cin, ho, wo, cout, kh, kw, stride, pad, int(reflect), int(precise), patches_of)
-        use = (g_y, xr, x2r, n)
-        # ---- two-use weights (r4): a weight used by two training forwards of the step (the labelled and the unlabelled batch of a
-        # CPS iteration) gets ONE launch over both uses -- the first use is queued on the Parameter, the second runs
-        # vqseg_conv2d_wgrad2_f over the virtual batch: twice the contraction length per workgroup, half the slab sums
-        pend = getattr(p_w, "_vq_wgrad_pending", None) if sink_w else None
-        if pend is not None:
-            p_w._vq_wgrad_pending = None
-            _PENDING_WGRADS.discard(p_w)
-        if pend is not None and (pend[0] != geom or pend[2] != torch.cuda.current_stream(dev) or wside is not None):
-            _wgrad_launch(pend[0], pend[1], None, p_w.grad, True, pend[2])      # not pairable after all: the queued use on its own
-            pend = None
-        if sink_w and pend is None and wside is None and getattr(p_w, "_vq_uses", 1) >= 2 and py_opt("py_wgrad_pair", 1):
-            p_w._vq_wgrad_pending = (geom, use, torch.cuda.current_stream(dev))
-            _PENDING_WGRADS.add(p_w)
-        else:
-            with (torch.cuda.stream(wside) if wside is not None else contextlib.nullcontext()):
-                _wgrad_launch(geom, pend[1] if pend is not None else use, use if pend is not None else None, gw, sink_w, None)
-        if sink_w:
-            _sink_done(p_w)
-        # ---- data gradient(s): the same implicit-GEMM kernel on g_y with tap-flipped, transposed weights
+            xr = _shared_stem_patches(ctx.stem_x if ctx.stem_x is not None else img,
+                                      (torch.bfloat16, stem.kh, stem.kw, stem.stride, stem.pad, stem.reflect),
+                                      lambda: _stem_patches(img, torch.bfloat16, stem.kh, stem.kw, stem.stride, stem.pad, stem.reflect, g.ho, g.wo, g.cin))
+        g_y, g_res, dgamma, dbeta = _bn_backward_step(ctx, g_out, y, out, coef, gamma)
+        gw = _wgrad_step(ctx, g_y, xr, x2r, weight)
         gx = gx2 = None
-        need1, need2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if (need1 or need2) and not patches_of:
-            t_hi, t_lo = packed_weights(weight, precise, True)                 # [Cin][kh][kw][Cout]
-            taps = kh * kw
-            hp, wp = (h + 2 * pad, w + 2 * pad) if reflect else (h, w)         # reflect: gradient of the padded input first
-            dpad = (kh - 1) if reflect else (kh - 1 - pad)
+        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and stem is None:
+            gx, gx2 = _dgrad_step(ctx, g_y, x2r, weight)
+        g_res_out = _nchw(g_res) if (ctx.has_res and ctx.links[1] is None) else None
+        # one entry per argument of forward (after ctx): the six tensors above, None for the rest
+        return (gx, gx2, g_res_out, gw, dgamma, dbeta) + (None,) * (_ConvBNAct.forward.__code__.co_argcount - 7)
 
-            extra = link_in.g if link_in is not None else None          # residual-branch gradient of the same block input
-            ebits = link_in.bits if link_in is not None else None
-            if link_in is not None:
-                link_in.g = link_in.bits = None
-                link_in.closed = True
-            if ebits is not None and not (not reflect and stride == 1 and x2r is None and bf and extra.shape == (n, hp, wp, c1)):
-                extra, ebits = _mask_with_bits(extra, ebits), None       # not the fusing path below after all
 
-            def dgrad(c_lo, c_cnt):
-                nonlocal extra
-                # reflect padding, 3x3 / stride 1 (every Bottleneck conv2): the padded gradient's INTERIOR is the zero-padded data
-                # gradient (fast patch kernel, unpadded grid); only its border ring is evaluated as a full correlation and folded
-                # onto rows 1 / H-2 and columns 1 / W-2 (vqseg_reflect_ring_f) -- no (H+2) x (W+2) tensor, no fold pass over it
-                ring = (reflect and stride == 1 and kh == 3 and kw == 3 and pad == 1 and bf and x2r is None and cout % 64 == 0
-                        and c_cnt % 8 == 0 and h >= 4 and w >= 4 and py_opt("py_reflect_ring", 1) == 1)
-                if ring:
-                    gp = None
-                    if extra is not None and extra.shape == (n, h, w, c_cnt):
-                        one, zero = _unit_affine(dev, c_cnt)
-                        gp = torch.empty((n, h, w, c_cnt), dtype=g_y.dtype, device=dev)
-                        with _hip.on_device(dev):
-                            tneed = c_cnt * 9 * ((cout + 31) // 32 * 32)
-                            _check(L.vqseg_conv2d_affine_f(_T(g_y, "conv output gradient", bf=bf, numel=m * cout), None, cout,
-                                                           _w16(t_hi, "transposed image", tneed), None, _f32(one, "unit scale", c_cnt),
-                                                           _f32(zero, "zero shift", c_cnt), _T(extra, "shortcut gradient", bf=bf, numel=n * h * w * c_cnt), 0,
-                                                           _T(gp, "input gradient", bf=bf, numel=n * h * w * c_cnt), n, ho, wo, cout, c_cnt,
-                                                           3, 3, 1, 1, 0, h, w, 0, _stream()), "vqseg_conv2d_affine_f")
-                        extra = None
-                    else:
-                        gp = _conv_raw(g_y, None, cout, t_hi, t_lo, (n, h, w, c_cnt), None, n, ho, wo, cout, c_cnt, 3, 3, 1, 1, False, 1, h, w)
-                    rbuf = torch.empty((n, 2 * (w + 2) + 2 * h, c_cnt), dtype=g_y.dtype, device=dev)
-                    with _hip.on_device(dev):
-                        _check(L.vqseg_reflect_ring_f(_T(g_y, "conv output gradient", bf=1, numel=m * cout),
-                                                      _w16(t_hi, "transposed image", c_cnt * 9 * ((cout + 31) // 32 * 32)),
-                                                      _T(rbuf, "gradient ring", bf=1, numel=rbuf.numel()), _T(gp, "input gradient", bf=1, numel=n * h * w * c_cnt),
-                                                      n, h, w, cout, c_cnt, _stream()), "vqseg_reflect_ring_f")
-                    return gp
-                if extra is not None and not reflect and stride == 1 and x2r is None and extra.shape == (n, hp, wp, c_cnt):
-                    # the data gradient and the residual-branch gradient meet in the convolution's epilogue (one add pass less)
-                    one, zero = _unit_affine(dev, c_cnt)
-                    gp = torch.empty((n, hp, wp, c_cnt), dtype=g_y.dtype, device=dev)
-                    with _hip.on_device(dev):
-                        tneed = c_cnt * kh * kw * ((cout + 31) // 32 * 32)
-                        if ebits is not None:
-                            _check(L.vqseg_conv2d_affine_bits_f(
-                                _T(g_y, "conv output gradient", bf=1, numel=m * cout), _w16(t_hi, "transposed image", tneed),
-                                _f32(one, "unit scale", c_cnt), _f32(zero, "zero shift", c_cnt),
-                                _T(extra, "block output gradient", bf=1, numel=n * hp * wp * c_cnt),
-                                _T(ebits, "ReLU mask bits", dtype=torch.uint8, numel=n * hp * wp * c_cnt // 8),
-                                _T(gp, "input gradient", bf=1, numel=n * hp * wp * c_cnt), n, ho, wo, cout, c_cnt, kh, kw, dpad, hp, wp,
-                                _stream()), "vqseg_conv2d_affine_bits_f")
-                        else:
-                            _check(L.vqseg_conv2d_affine_f(_T(g_y, "conv output gradient", bf=bf, numel=m * cout), None, cout,
-                                                         _w16(t_hi, "transposed image", tneed), _w16(t_lo, "transposed image (lo)", tneed),
-                                                         _f32(one, "unit scale", c_cnt), _f32(zero, "zero shift", c_cnt),
-                                                         _T(extra, "shortcut gradient", bf=bf, numel=n * hp * wp * c_cnt), 0,
-                                                         _T(gp, "input gradient", bf=bf, numel=n * hp * wp * c_cnt), n, ho, wo, cout, c_cnt,
-                                                         kh, kw, 1, dpad, 0, hp, wp, int(precise), _stream()), "vqseg_conv2d_affine_f")
-                    extra = None
-                    return gp
-                if (stride == 2 and x2r is None and kh == 3 and kw == 3 and pad == 1 and bf and h == 2 * ho and w == 2 * wo and h >= 4 and w >= 4
-                        and cout % 64 == 0 and c_cnt % 8 == 0 and c_cnt >= 64 and py_opt("py_dgrad_s2", 1) and py_opt("py_dgrad_s2_fold", 1)):
-                    # r4: the four parity classes in ONE launch, written straight into the unpadded gradient (reflect padding: the
-                    # padded top row / left column go to a small ring behind the pixel rows and are added onto row 1 / column 1) --
-                    # no (H+2) x (W+2) tensor, no fold / crop pass over it
-                    s_hi, _s_lo = _s2_weights(weight, precise)
-                    rows = int(L.vqseg_conv2d_dgrad_s2_fold_rows(n, h, w, int(reflect)))
-                    buf = torch.empty((rows, c_cnt), dtype=g_y.dtype, device=dev)
-                    with _hip.on_device(dev):
-                        _check(L.vqseg_conv2d_dgrad_s2_fold_f(_T(g_y, "conv output gradient", bf=1, numel=m * cout),
-                                                              _w16(s_hi, "parity-class image", L.vqseg_conv_packed_s2_elems(cout, c_cnt, 3)),
-                                                              _T(buf, "input gradient (+ ring)", bf=1, numel=rows * c_cnt),
-                                                              n, ho, wo, cout, c_cnt, h, w, int(reflect), _stream()), "vqseg_conv2d_dgrad_s2_fold_f")
-                    return buf[:n * h * w].view(n, h, w, c_cnt)
-                if stride == 2 and x2r is None and kh == kw and ((kh == 1 and pad == 0) or (kh == 3 and pad == 1)) and py_opt("py_dgrad_s2", 1):
-                    # stride-2 layer: parity classes of the output pixel instead of a dilated gradient grid (vqseg_conv2d_dgrad_s2_f)
-                    s_hi, s_lo = _s2_weights(weight, precise)
-                    gh, gw_ = (h + 2, w + 2) if kh == 3 else (h, w)          # k = 3: the padded input's grid
-                    # fan-in (1x1 projection of a stage's first block): the input's OTHER consumer (decoder skip / VQ layer) has
-                    # deposited its gradient; this data gradient accumulates into it in place -- no memset, no add pass
-                    acc_g = _fanin_take(fan_x, (n, gh, gw_, c_cnt), g_y.dtype) if (kh == 1 and c_cnt <= 4096) else None
-                    gp = acc_g if acc_g is not None else torch.empty((n, gh, gw_, c_cnt), dtype=g_y.dtype, device=dev)
-                    with _hip.on_device(dev):
-                        sneed = L.vqseg_conv_packed_s2_elems(cout, c_cnt, kh)
-                        _check(L.vqseg_conv2d_dgrad_s2_f(_T(g_y, "conv output gradient", bf=bf, numel=m * cout), _w16(s_hi, "parity-class image", sneed),
-                                                         _w16(s_lo, "parity-class image (lo)", sneed), _T(gp, "input gradient", bf=bf, numel=n * gh * gw_ * c_cnt),
-                                                         n, ho, wo, cout, c_cnt, kh, gh, gw_, int(precise), int(acc_g is not None), _stream()),
-                               "vqseg_conv2d_dgrad_s2_f")
-                    if kh == 3 and not reflect:                              # zero padding: the gradient of the padded border is dropped
-                        return gp[:, 1:h + 1, 1:w + 1, :].contiguous()
-                else:
-                    gp = _conv_raw(g_y, None, cout, t_hi, t_lo, (n, hp, wp, c_cnt), None, n, ho, wo, cout, c_cnt, kh, kw, 1, dpad, False,
-                                   stride, hp, wp, w_offset_elems=c_lo * taps * ((cout + 31) // 32 * 32))
-                if not reflect:
-                    return gp
-                if pad != 1:
-                    raise NotImplementedError("reflect-padding data gradient is implemented for pad == 1")
-                gxx = torch.empty((n, h, w, c_cnt), dtype=gp.dtype, device=dev)
-                with _hip.on_device(dev):
-                    _check(L.vqseg_reflect_fold_f(bf, _T(gp, "padded input gradient", bf=bf, numel=n * (h + 2) * (w + 2) * c_cnt), n, h, w, c_cnt,
-                                                  _T(gxx, "input gradient", bf=bf, numel=n * h * w * c_cnt), _stream()), "vqseg_reflect_fold_f")
-                return gxx
+def _bn_backward_step(ctx, g_out, y, out, coef, gamma):
+    """BatchNorm (+ ReLU, + residual split) backward -> (g_y, g_res, dgamma, dbeta); with grad sinks dgamma / dbeta are added into the
+    parameters' .grad and come back None.  A block's last conv hands the residual branch's gradient to `link_out` (GradLink)."""
+    g = ctx.geom
+    gr = _rows(g_out)
+    if gr.dtype != y.dtype:
+        gr = gr.to(y.dtype)
+    link_out = ctx.links[1]
+    # the residual branch's gradient g_out .* mask is not stored when the block's first conv will apply the mask bits itself
+    bits_to_link = bool(ctx.has_res and ctx.mask_bits and link_out is not None and link_out.takes_bits and not link_out.closed)
+    g_res = torch.empty_like(y) if (ctx.has_res and not bits_to_link) else None
+    _, p_g, p_b = ctx.params
+    sink = _sink_ready(p_g) and _sink_ready(p_b) and ctx.needs_input_grad[4] and ctx.needs_input_grad[5]
+    dgb = None if sink else torch.empty(2, g.cout, dtype=torch.float32, device=y.device)
+    dgamma, dbeta = (p_g.grad, p_b.grad) if sink else (dgb[0], dgb[1])
+    g_y = _bn_backward(gr, out if (ctx.has_res and not ctx.mask_bits) else None, out if ctx.mask_bits else None, y, coef, gamma,
+                       g.m, g.cout, ctx.relu, ctx.training, sink, dgamma, dbeta, g_res, ctx.bn)
+    if sink:
+        _sink_done(p_g), _sink_done(p_b)
+    if link_out is not None and ctx.has_res:
+        link_out.g = gr if bits_to_link else g_res                          # picked up by the block's first conv
+        link_out.bits = out if bits_to_link else None
+    return (g_y, g_res, None, None) if sink else (g_y, g_res, dgb[0], dgb[1])
 
-            fan_x, fan_x2 = ctx.fans
-            if need1:
-                g1 = dgrad(0, c1)
-                if extra is not None:                                       # link not fusable here: plain add
-                    g1 = g1 + extra
-                    extra = None
-                if fan_x is not None:                                       # a deposit the kernel path above could not absorb
-                    rest = _fanin_take(fan_x, g1.shape, g1.dtype)
-                    rest = rest if rest is not None else fan_x.leftover
-                    fan_x.leftover = None
-                    if rest is not None:
-                        g1 = g1 + rest.reshape(g1.shape).to(g1.dtype)
-                if link_x is not None and not link_x.closed and x2r is None:
-                    link_x.g = g1                                           # the block's first conv adds it (GradLink)
-                else:
-                    gx = _nchw(g1)
-            if need2 and x2r is not None:
-                g2 = dgrad(c1, cin - c1)
-                if g2.dtype == x2r.dtype and _fanin_deposit(fan_x2, g2):    # x2's other consumer adds it inside its own kernel
-                    gx2 = None
-                else:
-                    gx2 = _nchw(g2)
-        g_res_out = _nchw(g_res) if (has_res and link_out is None) else None
-        return (gx, gx2, g_res_out, None if sink_w else gw, None if sink_bn else dgb[0],
-                None if sink_bn else dgb[1], None, None, None, None, None, None, None, None, None, None, None, None)
+
+def _wgrad_step(ctx, g_y, xr, x2r, weight):
+    """Weight gradient -> gw (None with a grad sink: the result is ADDED into the trainer's bucket, nothing returns to autograd).
+    With a sink and a registered side stream the kernel and its slab sum leave the network's stream: nothing downstream in backward
+    depends on them, and as filler work they cover the latency-bound links of the main chain (BatchNorm statistics folds,
+    finalizes, packs: skipping those ~950 launches -- wrong results, timing only -- was worth 11 ms of a 163 ms step)."""
+    g, dev = ctx.geom, g_y.device
+    p_w = ctx.params[0]
+    sink_w = _sink_ready(p_w) and ctx.needs_input_grad[3]
+    gw = p_w.grad if sink_w else torch.empty(weight.shape, dtype=torch.float32, device=dev)
+    wside = _wgrad_side_stream(dev) if sink_w else None
+    if wside is not None:
+        main_s = torch.cuda.current_stream(dev)
+        wside.wait_event(main_s.record_event())                             # g_y (BatchNorm backward) is complete
+        for t_ in (g_y, xr, x2r):
+            if t_ is not None:
+                t_.record_stream(wside)                                     # allocator: not reusable before the side stream is done
+    key = _WgradKey(g._replace(n=0), not _is_bf16(g_y), ctx.stem)
+    use = (g_y, xr, x2r, g.n)
+    # two-use weights: a weight used by two training forwards of the step (the labelled and the unlabelled batch of a CPS iteration)
+    # gets ONE launch over both uses -- the first use is queued on the Parameter, the second runs vqseg_conv2d_wgrad2_f over the
+    # virtual batch: twice the contraction length per workgroup, half the slab sums
+    pend = getattr(p_w, "_vq_wgrad_pending", None) if sink_w else None
+    if pend is not None:
+        p_w._vq_wgrad_pending = None
+        _PENDING_WGRADS.discard(p_w)
+    if pend is not None and (pend[0] != key or pend[2] != torch.cuda.current_stream(dev) or wside is not None):
+        _wgrad_launch(pend[0], pend[1], None, p_w.grad, True, pend[2])      # not pairable after all: the queued use on its own
+        pend = None
+    if sink_w and pend is None and wside is None and getattr(p_w, "_vq_uses", 1) >= 2 and py_opt("py_wgrad_pair", 1):
+        p_w._vq_wgrad_pending = (key, use, torch.cuda.current_stream(dev))
+        _PENDING_WGRADS.add(p_w)
+    else:
+        with (torch.cuda.stream(wside) if wside is not None else contextlib.nullcontext()):
+            _wgrad_launch(key, pend[1] if pend is not None else use, use if pend is not None else None, gw, sink_w, None)
+    if sink_w:
+        _sink_done(p_w)
+    return None if sink_w else gw
+
+
+# What the data-gradient paths of one backward share: g the forward convolution, single: one input (no channel concat), t_hi / t_lo the
+# [Cin][kh][kw][Cout] tap-flipped weight image (the same implicit-GEMM kernels run on g_y with it), fan_x the input's fan-in link
+_Dgrad = namedtuple("_Dgrad", "g g_y bf single weight t_hi t_lo fan_x")
+
+
+def _dgrad_geom(g: ConvGeom, c_cnt, hp, wp, pad) -> ConvGeom:
+    """the stride-1 convolution g_y (n, ho, wo, cout) -> gradient (n, hp, wp, c_cnt) of (a channel range of) g's input"""
+    return ConvGeom(g.n, g.ho, g.wo, g.cout, g.cout, c_cnt, g.kh, g.kw, 1, pad, False, hp, wp)
+
+
+# Every path(d, c_lo, c_cnt, extra, ebits) -> (gradient rows of input channels [c_lo, c_lo + c_cnt), extra), or None where it does not
+# apply (its first statement).  `extra` is the shortcut gradient of the same block input (GradLink), `ebits` its ReLU mask bit field;
+# a path that adds `extra` in its kernel returns None for it.
+def _dgrad_ring(d, c_lo, c_cnt, extra, ebits):
+    """reflect padding, 3x3 / stride 1 (every Bottleneck conv2): the padded gradient's INTERIOR is the zero-padded data gradient (fast
+    patch kernel, unpadded grid); only its border ring is evaluated as a full correlation and folded onto it (_reflect_ring) -- no
+    (H+2) x (W+2) tensor, no fold pass over it"""
+    g = d.g
+    if not (g.reflect and g.stride == 1 and (g.kh, g.kw, g.pad) == (3, 3, 1) and d.bf and d.single and g.cout % 64 == 0
+            and c_cnt % 8 == 0 and g.h >= 4 and g.w >= 4 and py_opt("py_reflect_ring", 1) == 1):
+        return None
+    dg = _dgrad_geom(g, c_cnt, g.h, g.w, 1)
+    if extra is not None and extra.shape == (g.n, g.h, g.w, c_cnt):
+        one, zero = _unit_affine(d.g_y.device, c_cnt)
+        gp, extra = _conv_affine(d.g_y, None, d.t_hi, None, one, zero, extra, False, dg, 0), None
+    else:
+        gp = _conv_raw(d.g_y, None, d.t_hi, d.t_lo, None, dg)
+    _reflect_ring(d.g_y, d.t_hi, gp, dg)
+    return gp, extra
+
+
+def _shortcut_ok(d, c_cnt, extra):
+    g = d.g
+    return extra is not None and not g.reflect and g.stride == 1 and d.single and extra.shape == (g.n, g.h, g.w, c_cnt)
+
+
+def _dgrad_shortcut(d, c_lo, c_cnt, extra, ebits):
+    """the data gradient and the residual-branch gradient meet in the convolution's epilogue (one add pass less); with `ebits` the
+    epilogue also applies the block's last ReLU mask to the shortcut gradient"""
+    if not _shortcut_ok(d, c_cnt, extra):
+        return None
+    g = d.g
+    dg = _dgrad_geom(g, c_cnt, g.h, g.w, g.kh - 1 - g.pad)
+    one, zero = _unit_affine(d.g_y.device, c_cnt)
+    if ebits is not None:
+        return _conv_affine_bits(d.g_y, d.t_hi, one, zero, extra, ebits, dg), None
+    return _conv_affine(d.g_y, None, d.t_hi, d.t_lo, one, zero, extra, False, dg, int(not d.bf)), None
+
+
+def _dgrad_s2_folded(d, c_lo, c_cnt, extra, ebits):
+    g = d.g
+    if not (g.stride == 2 and d.single and (g.kh, g.kw, g.pad) == (3, 3, 1) and d.bf and g.h == 2 * g.ho and g.w == 2 * g.wo and g.h >= 4
+            and g.w >= 4 and g.cout % 64 == 0 and c_cnt % 8 == 0 and c_cnt >= 64 and py_opt("py_dgrad_s2", 1) and py_opt("py_dgrad_s2_fold", 1)):
+        return None
+    s_hi, _s_lo = _s2_weights(d.weight, not d.bf)
+    return _dgrad_s2_fold(d.g_y, s_hi, d.g, c_cnt), extra
+
+
+def _dgrad_s2_classes(d, c_lo, c_cnt, extra, ebits):
+    """stride-2 layer: parity classes of the output pixel instead of a dilated gradient grid"""
+    g = d.g
+    if not (g.stride == 2 and d.single and g.kh == g.kw and ((g.kh == 1 and g.pad == 0) or (g.kh == 3 and g.pad == 1)) and py_opt("py_dgrad_s2", 1)):
+        return None
+    s_hi, s_lo = _s2_weights(d.weight, not d.bf)
+    gh, gw = (g.h + 2, g.w + 2) if g.kh == 3 else (g.h, g.w)         # k = 3: the padded input's grid
+    # fan-in (1x1 projection of a stage's first block): the input's OTHER consumer (decoder skip / VQ layer) has deposited its
+    # gradient; this data gradient accumulates into it in place -- no memset, no add pass
+    acc = _fanin_take(d.fan_x, (g.n, gh, gw, c_cnt), d.g_y.dtype) if (g.kh == 1 and c_cnt <= 4096) else None
+    gp = _dgrad_s2(d.g_y, s_hi, s_lo, acc, g, c_cnt, gh, gw)
+    if g.kh == 3 and not g.reflect:                                  # zero padding: the gradient of the padded border is dropped
+        return gp[:, 1:g.h + 1, 1:g.w + 1, :].contiguous(), extra
+    return _reflect_fold(gp, g, c_cnt), extra
+
+
+def _dgrad_generic(d, c_lo, c_cnt, extra, ebits):
+    g = d.g
+    hp, wp = (g.h + 2 * g.pad, g.w + 2 * g.pad) if g.reflect else (g.h, g.w)      # reflect: gradient of the padded input first
+    dg = _dgrad_geom(g, c_cnt, hp, wp, (g.kh - 1) if g.reflect else (g.kh - 1 - g.pad))
+    gp = _conv_raw(d.g_y, None, d.t_hi, d.t_lo, None, dg, up=g.stride, w_offset_elems=_packed_elems(c_lo, g.kh, g.kw, g.cout))
+    return _reflect_fold(gp, g, c_cnt), extra
+
+
+def _dgrad(d, c_lo, c_cnt, extra, ebits):
+    """the first path that applies, in this order"""
+    for path in (_dgrad_ring, _dgrad_shortcut, _dgrad_s2_folded, _dgrad_s2_classes, _dgrad_generic):
+        res = path(d, c_lo, c_cnt, extra, ebits)
+        if res is not None:
+            return res
+
+
+def _dgrad_step(ctx, g_y, x2r, weight):
+    """Data gradients -> (gx, gx2), either None when not needed or handed over through a GradLink / fan-in link instead."""
+    g = ctx.geom
+    link_in, _, link_x = ctx.links
+    fan_x, fan_x2 = ctx.fans
+    bf = _is_bf16(g_y)
+    d = _Dgrad(g, g_y, bf, x2r is None, weight, *packed_weights(weight, not bf, True), fan_x)
+    extra = ebits = None                                            # residual-branch gradient of the same block input
+    if link_in is not None:
+        extra, ebits = link_in.g, link_in.bits
+        link_in.g = link_in.bits = None
+        link_in.closed = True
+    if ebits is not None and not (bf and _shortcut_ok(d, g.c1, extra)):
+        extra, ebits = _mask_with_bits(extra, ebits), None          # not the fusing path after all
+    gx = gx2 = None
+    if ctx.needs_input_grad[0]:
+        g1, extra = _dgrad(d, 0, g.c1, extra, ebits)
+        if extra is not None:                                       # link not fusable here: plain add
+            g1 = g1 + extra
+        if fan_x is not None:                                       # a deposit the kernel path above could not absorb
+            rest = _fanin_take(fan_x, g1.shape, g1.dtype)
+            rest = rest if rest is not None else fan_x.leftover
+            fan_x.leftover = None
+            if rest is not None:
+                g1 = g1 + rest.reshape(g1.shape).to(g1.dtype)
+        if link_x is not None and not link_x.closed and x2r is None:
+            link_x.g = g1                                           # the block's first conv adds it (GradLink)
+        else:
+            gx = _nchw(g1)
+    if ctx.needs_input_grad[1] and x2r is not None:
+        g2, _ = _dgrad(d, g.c1, g.cin - g.c1, None, None)
+        if not (g2.dtype == x2r.dtype and _fanin_deposit(fan_x2, g2)):     # else x2's other consumer adds it inside its own kernel
+            gx2 = _nchw(g2)
+    return gx, gx2
 
 
 def _s2_weights(weight, precise):
@@ -1016,12 +1161,13 @@ def stem_conv_bn_act(x, conv, bn):
     s, p = conv.stride[0], conv.padding[0]
     reflect = conv.padding_mode == "reflect"
     ho, wo = _out_size(h, kh, s, p), _out_size(w, kw, s, p)
-    kp = (kh * kw * cin + 31) // 32 * 32
+    kp = _pad32(kh * kw * cin)
+    stem = StemGeom(kh, kw, cin, s, p, reflect, h, w)
     dt = act_dtype()
-    # r4: the convolution straight from the image (vqseg_stem7_conv_f) where its tiling fits: 128 output pixels of one row per workgroup.
-    # It removes 7.5 GB of patch-matrix traffic per step and its kernel takes 197 us against 318 us.  Measured +-0 in the step when it was
-    # built (152.7 vs 152.5 ms) and -0.9 ms on the final r4 build (145.3 vs 146.1 ms, LEDGER r4): default from then on; the patch-matrix
-    # path (VQSEG_OPTS=py_stem_fused=0) stays for output widths that are not multiples of 128 and for the weight gradient
+    # The convolution straight from the image (vqseg_stem7_conv_f) where its tiling fits: 128 output pixels of one row per workgroup.
+    # It removes 7.5 GB of patch-matrix traffic per step and its kernel takes 197 us against 318 us; -0.9 ms of a 146 ms step (LEDGER
+    # r4).  The patch-matrix path (VQSEG_OPTS=py_stem_fused=0) stays for output widths that are not multiples of 128 and for the
+    # weight gradient
     fused_ok = ((kh, kw, cin) == (7, 7, 3) and s == 2 and p == 3 and wo % 128 == 0 and h >= 4 and w >= 4 and conv.weight.shape[0] == 64
                 and py_opt("py_stem_fused", 1) == 1)
     if _S3_SCOPE and dt == torch.float32 and not bn.training and not torch.is_grad_enabled() and (kh, kw, cin) == (7, 7, 3):
@@ -1035,32 +1181,23 @@ def stem_conv_bn_act(x, conv, bn):
                                             _T(out, "split-3 patches", bf=2, numel=n * ho * wo * 2 * kp3), _stream()), "vqseg_im2col_f (split-3)")
             return out
 
-        if fused_ok:                                             # r4: no split-3 patch matrix (1.6 GB written, read by both networks)
+        if fused_ok:                                             # no split-3 patch matrix (1.6 GB written, read by both networks)
             cout = conv.weight.shape[0]
-            wimg = _stem_weights_fused(conv.weight, True)
-            coef = torch.empty(4, cout, dtype=torch.float32, device=x.device)
-            out = torch.empty((n, ho, wo, 2 * cout), dtype=torch.bfloat16, device=x.device)
-            with _hip.on_device(x.device):
-                _check(lib().vqseg_bn_finalize_f(None, n * ho * wo, cout, _f32(bn.weight, "bn.weight", cout), _f32(bn.bias, "bn.bias", cout),
-                                                 _f32(bn.running_mean, "bn.running_mean", cout), _f32(bn.running_var, "bn.running_var", cout),
-                                                 float(bn.momentum), float(bn.eps), 0, _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout),
-                                                 _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout), None, None, _stream()), "vqseg_bn_finalize_f")
-                _check(lib().vqseg_stem7_conv_f(1, _f32(xr, "image", n * h * w * cin), _w16(wimg, "stem weight image (hi | lo)", cout * 2 * 176),
-                                                _T(out, "split-3 output", bf=2, numel=n * ho * wo * 2 * cout), None, _f32(coef[0], "scale", cout),
-                                                _f32(coef[1], "shift", cout), 1, n, h, w, int(reflect), _stream()), "vqseg_stem7_conv_f (split-3)")
+            coef = _bn_finalize(None, n * ho * wo, cout, bn.weight, bn.bias, bn, False, x.device)
+            out = _stem7_conv(xr, _stem_weights_fused(conv.weight, True), None, coef, True, stem._replace(fused=(ho, wo, kp)), cout, s3=True)
             return S3(out, cout)
         patches = _shared_stem_patches(x, ("s3", kh, kw, s, p, reflect), make3)
         return _conv_bn_act_s3(S3(patches, kp3), None, None, conv, bn, True, kernel_1x1_cols=kp3)
 
+    fuse_eval = not bn.training and not torch.is_grad_enabled()
     if fused_ok and dt == torch.bfloat16 and kp == 160:
         _sink_use(conv.weight, bn.weight, bn.bias)
         _STEM_X_ARG[0] = x
         return _ConvBNAct.apply(_nchw(xr), None, None, conv.weight, bn.weight, bn.bias, bn, 1, 0, False, True,
-                                (kh, kw, cin, s, p, reflect, h, w, (ho, wo, kp)), not bn.training and not torch.is_grad_enabled())
+                                stem._replace(fused=(ho, wo, kp)), fuse_eval)
     patches = _shared_stem_patches(x, (dt, kh, kw, s, p, reflect), lambda: _stem_patches(xr, dt, kh, kw, s, p, reflect, ho, wo, kp))
     _sink_use(conv.weight, bn.weight, bn.bias)
-    return _ConvBNAct.apply(_nchw(patches), None, None, conv.weight, bn.weight, bn.bias, bn, 1, 0, False, True,
-                            (kh, kw, cin, s, p, reflect, h, w), not bn.training and not torch.is_grad_enabled())
+    return _ConvBNAct.apply(_nchw(patches), None, None, conv.weight, bn.weight, bn.bias, bn, 1, 0, False, True, stem, fuse_eval)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1389,33 +1526,28 @@ class _ConvBias(torch.autograd.Function):
             with _hip.on_device(dev):
                 _check(L.vqseg_conv_pack_weights_f32(_f32(wp, "weight", cp * cin * kh * kw), cp, cin, kh, kw, int(tr), _w16(hi, "packed hi", ne),
                                                      _w16(lo, "packed lo", ne), _stream()), "vqseg_conv_pack_weights_f32")
-            return hi, lo, ne
+            return hi, lo
 
-        hi, lo, ne = pack(False)
-        ho, wo = _out_size(h, kh, 1, pad), _out_size(w, kw, 1, pad)
-        y = torch.empty((n, ho, wo, cp), dtype=torch.float32, device=dev)
-        with _hip.on_device(dev):
-            _check(L.vqseg_conv2d_affine_f(_T(xr, "conv input", bf=0, numel=n * h * w * cin), None, cin, _w16(hi, "packed weights", ne),
-                                           _w16(lo, "packed weights (lo)", ne), _f32(one, "unit scale", cp), _f32(shift, "bias", cp), None, 0,
-                                           _T(y, "conv output", bf=0, numel=n * ho * wo * cp), n, h, w, cin, cp, kh, kw, 1, pad, 0, ho, wo, 1,
-                                           _stream()), "vqseg_conv2d_affine_f")
+        g = ConvGeom(n, h, w, cin, cin, cp, kh, kw, 1, pad, False, _out_size(h, kh, 1, pad), _out_size(w, kw, 1, pad))
+        y = _conv_affine(xr, None, *pack(False), one, shift, None, False, g, 1)
         ctx.save_for_backward(xr)
-        ctx.cfg = (n, h, w, cin, cout, cp, kh, kw, pad, ho, wo, bias is not None)
+        ctx.geom, ctx.cout, ctx.has_bias = g, cout, bias is not None
         ctx.pack = pack
         return y[..., :cout].permute(0, 3, 1, 2)
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, grad):
         (xr,) = ctx.saved_tensors
-        n, h, w, cin, cout, cp, kh, kw, pad, ho, wo, has_bias = ctx.cfg
+        g, cout = ctx.geom, ctx.cout
+        n, h, w, cin, cp, kh, kw, pad, ho, wo = g.n, g.h, g.w, g.cin, g.cout, g.kh, g.kw, g.pad, g.ho, g.wo
         dev = xr.device
         L = lib()
         g4 = torch.zeros((n, ho, wo, cp), dtype=torch.float32, device=dev)
-        g4[..., :cout] = g.permute(0, 2, 3, 1)
+        g4[..., :cout] = grad.permute(0, 2, 3, 1)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            t_hi, t_lo, _ = ctx.pack(True)                      # [Cin][kh][kw][cp], taps flipped
-            gx = _nchw(_conv_raw(g4, None, cp, t_hi, t_lo, (n, h, w, cin), None, n, ho, wo, cp, cin, kh, kw, 1, kh - 1 - pad, False, 1, h, w))
+            t_hi, t_lo = ctx.pack(True)                         # [Cin][kh][kw][cp], taps flipped
+            gx = _nchw(_conv_raw(g4, None, t_hi, t_lo, None, _dgrad_geom(g, cin, h, w, kh - 1 - pad)))
         if ctx.needs_input_grad[1]:
             nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n, h, w, cin, ho, wo, cp, kh, kw)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -1426,8 +1558,8 @@ class _ConvBias(torch.autograd.Function):
                                               _T(ws, "wgrad workspace", dtype=torch.uint8, numel=nbytes), nbytes, _f32(gw4, "weight gradient", cp * cin * kh * kw),
                                               _stream()), "vqseg_conv2d_wgrad_f")
             gw = gw4[:cout]
-        if has_bias and ctx.needs_input_grad[2]:
-            gb = g.sum(dim=(0, 2, 3))
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = grad.sum(dim=(0, 2, 3))
         return gx, gw, gb, None
 
 

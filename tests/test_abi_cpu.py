@@ -202,3 +202,120 @@ def test_a_failed_fused_batchnorm_launch_zeroes_the_modules_counters():
         nnf._check_fused_bn(_hip.lib().vqseg_bn_apply_f(1, None, None, None, None, 0, 0, 0, None, None), "vqseg_bn_apply_f (null arguments)", bn)
     assert int(bn._vq_sync.abs().sum()) == 0
     nnf._check_fused_bn(0, "ok", bn)                            # a clean return code touches nothing
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# vqseg_set_option is pure host code.  The defaults ARE the dispatch the benchmark measures (profiles/LEDGER.md records each as a
+# decision), so they are pinned here, together with what every key does to a value: key -> (default, a second legal value, what
+# that value reads back as -- flags store value ? 1 : 0).
+# ---------------------------------------------------------------------------------------------------------------------------
+OPTIONS = {
+    "conv3x3_patch_min_workgroups": (128, 1, 1),
+    "conv_wgrad1x1_narrow": (1, 0, 0),
+    "stem_fused": (1, 0, 0),
+    "conv_wgrad_round_pct": (100, 400, 400),
+    "conv_wgrad_xcd": (1, 0, 0),
+    "conv_dgrad_s2_merge": (1, 0, 0),
+    "conv_wgrad3x3_fill": (1, 0, 0),
+    "conv_wgrad3x3_stride2": (1, 0, 0),
+    "conv_short_k_small_tile": (1, 3, 3),
+    "conv_short_k_single_buffer": (8, 0, 0),
+    "conv3x3_patch_unroll": (1, 2, 2),
+    "conv_linear_prologue": (1, 0, 0),
+    "conv_xcd_pair": (8, 4, 4),
+    "conv3x3_patch_xcd_pair": (0, 7, 1),
+    "conv3x3_patch_chunk_stage": (1, 0, 0),
+    "conv3x3_patch_tile512": (2, 0, 0),
+    "conv3x3_patch_tile512_launches": (0, 5, 5),
+    "conv3x3_patch_tile512_min_workgroups": (512, 1, 1),
+    "conv3x3_patch_wide_tile_s3": (1, 0, 0),
+    "conv3x3_patch_wide_tile": (1, 0, 0),
+    "vq_max_tiles_per_wave": (8, 2, 2),
+    "vq_fine_split": (1, 0, 0),
+    "vq_bf16_filter": (1, 0, 0),
+    "vq_filter_force_all": (0, 7, 1),
+    "vq_filter_launches": (0, 9, 9),
+    "debug_skip_small": (0, 7, 7),
+    "bn_bwd_premask": (1, 0, 0),
+    "nn_grid_cap": (8192, 256, 256),
+    "im2col_strip": (1, 0, 0),
+    "bilinear_up2": (1, 2, 2),
+}
+FLAGS = ["stem_fused", "conv_dgrad_s2_merge", "conv_linear_prologue", "conv3x3_patch_xcd_pair", "conv3x3_patch_chunk_stage",
+         "conv3x3_patch_wide_tile_s3", "conv3x3_patch_wide_tile", "vq_fine_split", "vq_bf16_filter", "vq_filter_force_all", "bn_bwd_premask",
+         "im2col_strip"]
+
+
+@pytest.fixture
+def option_lib():
+    """the library with every option at its default, before and after (it is process-wide and the other tests share it)"""
+    assert not os.environ.get("VQSEG_OPTS"), "the defaults are pinned without VQSEG_OPTS"
+    L = _hip.lib()
+    yield L
+    for key, (default, _v, _r) in OPTIONS.items():
+        assert L.vqseg_set_option(key.encode(), default) >= 0
+    for key, (default, _v, _r) in OPTIONS.items():
+        assert L.vqseg_set_option(key.encode(), default) == default, key
+
+
+@pytest.mark.parametrize("key", sorted(OPTIONS))
+def test_option_default_and_stored_value(option_lib, key):
+    L = option_lib
+    default, second, stored = OPTIONS[key]
+    k = key.encode()
+    assert L.vqseg_set_option(k, default) == default             # the default, and setting it again changes nothing
+    assert L.vqseg_set_option(k, default) == default
+    assert L.vqseg_set_option(k, second) == default              # returns the previous value ...
+    assert L.vqseg_set_option(k, default) == stored              # ... and stored the new one its own way
+
+
+def test_option_flags_store_zero_or_one(option_lib):
+    L = option_lib
+    for key in FLAGS:
+        k, default = key.encode(), OPTIONS[key][0]
+        L.vqseg_set_option(k, 7)
+        assert L.vqseg_set_option(k, 0) == 1, key
+        assert L.vqseg_set_option(k, 1 << 20) == 0, key
+        assert L.vqseg_set_option(k, default) == 1, key
+
+
+def test_option_odd_cases(option_lib):
+    L = option_lib
+    # out of range: ignored, the previous value is still the answer
+    for bad in (5, 9, 401, 1 << 30):
+        assert L.vqseg_set_option(b"conv_wgrad_round_pct", bad) == 100
+    assert L.vqseg_set_option(b"conv_wgrad_round_pct", 10) == 100
+    assert L.vqseg_set_option(b"conv_wgrad_round_pct", 401) == 10
+    assert L.vqseg_set_option(b"conv_wgrad_round_pct", 100) == 10
+    # bilinear_up2: 0 / 1 / 2 as given, anything above reads back as 1
+    assert L.vqseg_set_option(b"bilinear_up2", 0) == 1
+    assert L.vqseg_set_option(b"bilinear_up2", 3) == 0
+    assert L.vqseg_set_option(b"bilinear_up2", 2) == 1
+    assert L.vqseg_set_option(b"bilinear_up2", 1000) == 2
+    assert L.vqseg_set_option(b"bilinear_up2", 1) == 1
+    # out of range answered like an unknown key, nothing stored
+    for key, bad in ((b"nn_grid_cap", 255), (b"nn_grid_cap", 0), (b"vq_max_tiles_per_wave", 3), (b"vq_max_tiles_per_wave", 0),
+                     (b"vq_max_tiles_per_wave", 16), (b"no_such_option", 1), (b"", 1), (b"stem_fused ", 1), (b"STEM_FUSED", 1)):
+        assert L.vqseg_set_option(key, bad) == -1, (key, bad)
+        assert L.vqseg_last_error() == b"set_option: unknown key", (key, bad)
+    assert L.vqseg_set_option(b"nn_grid_cap", 8192) == 8192 and L.vqseg_set_option(b"vq_max_tiles_per_wave", 8) == 8
+    for tiles in (1, 2, 4, 8):
+        assert L.vqseg_set_option(b"vq_max_tiles_per_wave", tiles) == (8 if tiles == 1 else tiles // 2)
+    assert L.vqseg_set_option(b"nn_grid_cap", (1 << 31) - 1) == 8192
+    assert L.vqseg_set_option(b"nn_grid_cap", 8192) == (1 << 31) - 1
+    # a null key and a negative value fail before any table is looked at -- for known keys too, which keep their value
+    assert L.vqseg_set_option(None, 1) == -1 and L.vqseg_last_error() == b"set_option: null key or negative value"
+    for key in sorted(OPTIONS):
+        assert L.vqseg_set_option(key.encode(), -1) == -1, key
+        assert L.vqseg_last_error() == b"set_option: null key or negative value", key
+        assert L.vqseg_set_option(key.encode(), OPTIONS[key][0]) == OPTIONS[key][0], key
+    with pytest.raises(_hip.HipLibraryError, match="unknown option 'no_such_option' or bad value 1"):
+        _hip.set_option("no_such_option", 1)
+
+
+def test_option_table_of_the_integration_guide_lists_the_same_keys_and_defaults():
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    rows = re.findall(r"^\| `([a-z0-9_]+)` \| (\d+) \| (int|flag|range|set) \|", text, flags=re.M)
+    assert {k: int(d) for k, d, _ in rows} == {k: v[0] for k, v in OPTIONS.items()}
+    assert len(rows) == len(OPTIONS)
+    assert sorted(k for k, _, kind in rows if kind == "flag") == sorted(FLAGS)

@@ -1,5 +1,6 @@
 #!/bin/bash
 # A/B of two builds of the library on the full bench inside one gpurun call: bash tools/ab_lib.sh <other.so>
+# (other.so: e.g. make -C vq_seg_amd/csrc ab ABSRC=conv_igemm ABFLAGS=-DSTEM_ABL=1 -> vq_seg_amd/libvqseg_hip_ab.so)
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 LOG=$(mktemp)
 for rep in 1 2 3; do

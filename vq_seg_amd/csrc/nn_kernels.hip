@@ -9,10 +9,12 @@
 // All tensors are NHWC "rows" (pixel-major, channels contiguous).  T = float (precise mode) or __bf16.
 // Reductions are two-level with fixed order (no float atomics): results are run-to-run deterministic.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "nn_kernels.h"
+#include "options.h"
 
 namespace vqseg {
 
@@ -1693,7 +1695,7 @@ __global__ __launch_bounds__(256) void cast_kernel(const TI* __restrict__ x, lon
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-static long g_grid_cap = 8192;                              // workgroups of the grid-stride elementwise kernels (option "nn_grid_cap")
+static int g_grid_cap = 8192;                               // workgroups of the grid-stride elementwise kernels (option "nn_grid_cap")
 long nn_grid_cap() { return g_grid_cap; }                   // data_kernels.hip sizes its grid by the same cap
 static inline unsigned grid_for(long work, int per_block = 256, long cap = 0) {
     if (cap == 0) cap = g_grid_cap;
@@ -1706,30 +1708,21 @@ static inline unsigned grid_for(long work, int per_block = 256, long cap = 0) {
 // debug only (timing experiments, results garbage): bit 1 skip the forward statistics merge + finalize, 2 the backward finalize,
 // 4 the weight-gradient slab sums -- "what do the ~950 tiny launches of a step cost on the wall clock?" (VQSEG_OPTS=debug_skip_small=7)
 static int g_debug_skip_small = 0;
+static int g_bn_bwd_premask = 1;                            // residual layers: masked gradient written by the reduce pass (0: r3, both passes read g_out + out)
+static int g_bilinear_up2 = 1;                              // exact-2x fast kernels (bit-identical to the generic ones); 2: one input row per thread in the backward (r3)
+static int g_im2col_strip = 1;                              // the stem's patch matrix from LDS-staged strips (0: the gather kernel, r3)
+
+static const Option NN_OPTIONS[] = {
+    {"debug_skip_small", &g_debug_skip_small},
+    {"bn_bwd_premask", &g_bn_bwd_premask, OPT_FLAG},
+    {"nn_grid_cap", &g_grid_cap, OPT_RANGE_FAIL, 256, INT_MAX},
+    {"im2col_strip", &g_im2col_strip, OPT_FLAG},
+    {"bilinear_up2", &g_bilinear_up2},
+};
+
 int nn_set_option(const char* key, int value) {
-    if (key && !strcmp(key, "debug_skip_small")) {
-        const int prev = g_debug_skip_small;
-        g_debug_skip_small = value;
-        return prev;
-    }
-    if (key && !strcmp(key, "bn_bwd_premask")) {
-        extern int bn_bwd_premask_option(int);
-        return bn_bwd_premask_option(value);
-    }
-    if (key && !strcmp(key, "nn_grid_cap") && value >= 256) {
-        const int prev = (int)g_grid_cap;
-        g_grid_cap = value;
-        return prev;
-    }
-    if (key && !strcmp(key, "im2col_strip")) {
-        extern int im2col_strip_option(int);
-        return im2col_strip_option(value);
-    }
-    if (key && !strcmp(key, "bilinear_up2")) {
-        extern int bilinear_up2_option(int);
-        return bilinear_up2_option(value);
-    }
-    return -1;
+    if (key && !strcmp(key, "bilinear_up2") && value > 2) value = 1;      // 0 / 1 / 2 name kernels; anything above means "on"
+    return apply_option(NN_OPTIONS, key, value);
 }
 
 hipError_t launch_bn_finalize(float* partial, long n_slots, int rows_per_slot, long M, int C, const float* gamma,
@@ -1786,12 +1779,6 @@ static int bn_bwd_rows_per_block(long M) {
     return (int)r;
 }
 
-static int g_bn_bwd_premask = 1;                            // residual layers: masked gradient written by the reduce pass (0: r3, both passes read g_out + out)
-int bn_bwd_premask_option(int value) {
-    const int prev = g_bn_bwd_premask;
-    g_bn_bwd_premask = value ? 1 : 0;
-    return prev;
-}
 template <typename T, int MASK>
 static hipError_t bn_bwd_t(const void* g_out, const void* out, const void* y, const float* mean, const float* invstd,
                            const float* gamma, const float* fsc, const float* fsh, long M, int C, int relu, int training,
@@ -1871,15 +1858,8 @@ hipError_t launch_maxpool(int bf16, int backward, const void* x, const void* g, 
     return hipGetLastError();
 }
 
-static int g_bilinear_up2 = 1;                              // exact-2x fast kernels (bit-identical to the generic ones)
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
-int bilinear_up2_option(int value) {                        // 2: the fast kernels with one input row per thread in the backward (r3)
-    const int prev = g_bilinear_up2;
-    g_bilinear_up2 = value > 2 ? 1 : value;
-    return prev;
-}
 
 template <typename T, int VC>
 static void bilinear_t(int backward, const void* src, int N, int H, int W, int C, int Ho, int Wo, int align, void* dst,
@@ -1976,12 +1956,6 @@ hipError_t launch_s3_bilinear(const void* x, int N, int H, int W, int C, int Ho,
     return hipGetLastError();
 }
 
-static int g_im2col_strip = 1;                              // the stem's patch matrix from LDS-staged strips (0: the gather kernel, r3)
-int im2col_strip_option(int value) {
-    const int prev = g_im2col_strip;
-    g_im2col_strip = value ? 1 : 0;
-    return prev;
-}
 hipError_t launch_im2col_stem(int out_bf16, const float* x, int N, int H, int W, int Cin, int KH, int KW, int stride, int pad,
                               int reflect, int Ho, int Wo, int Kp, void* out, hipStream_t st_) {
     if (g_im2col_strip && KH == 7 && KW == 7 && Cin == 3 && stride == 2 && pad == 3 && (Kp == 160 || (Kp == 192 && out_bf16 == 2)) &&

@@ -29,6 +29,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "options.h"
 #include "vq_kernels.h"
 
 namespace vqseg {
@@ -1327,34 +1328,15 @@ static int g_vq_fine_split = 1;                             // option "vq_fine_s
 static int g_vq_bf16_filter = 1;                            // bf16 rows: candidate filter + exact re-score (0: the exact kernel on every row)
 static int g_vq_filter_force_all = 0;                       // tests: 1 = every row is re-scored by the exact kernel (the filter decides nothing)
 static int g_vq_filter_launches = 0;                        // launches that took the filter path (tests read and reset it)
-int vq_set_option(const char* key, int value) {
-    if (key && !strcmp(key, "vq_max_tiles_per_wave") && (value == 8 || value == 4 || value == 2 || value == 1)) {
-        const int prev = g_vq_max_tiles;
-        g_vq_max_tiles = value;
-        return prev;
-    }
-    if (key && !strcmp(key, "vq_fine_split")) {
-        const int prev = g_vq_fine_split;
-        g_vq_fine_split = value ? 1 : 0;
-        return prev;
-    }
-    if (key && !strcmp(key, "vq_bf16_filter")) {
-        const int prev = g_vq_bf16_filter;
-        g_vq_bf16_filter = value ? 1 : 0;
-        return prev;
-    }
-    if (key && !strcmp(key, "vq_filter_force_all")) {
-        const int prev = g_vq_filter_force_all;
-        g_vq_filter_force_all = value ? 1 : 0;
-        return prev;
-    }
-    if (key && !strcmp(key, "vq_filter_launches")) {
-        const int prev = g_vq_filter_launches;
-        g_vq_filter_launches = value;
-        return prev;
-    }
-    return -1;
-}
+static const Option VQ_OPTIONS[] = {
+    {"vq_max_tiles_per_wave", &g_vq_max_tiles, OPT_POW2_FAIL, 1, 8},
+    {"vq_fine_split", &g_vq_fine_split, OPT_FLAG},
+    {"vq_bf16_filter", &g_vq_bf16_filter, OPT_FLAG},
+    {"vq_filter_force_all", &g_vq_filter_force_all, OPT_FLAG},
+    {"vq_filter_launches", &g_vq_filter_launches},
+};
+
+int vq_set_option(const char* key, int value) { return apply_option(VQ_OPTIONS, key, value); }
 
 VqPlan vq_plan(int64_t N, int C, int K) {
     VqPlan p;

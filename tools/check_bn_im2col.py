@@ -1,5 +1,7 @@
-"""Debug aid: vqseg_im2col_f against F.unfold (must be bit-exact) and vqseg_bn_finalize_f against a numpy
-double-precision merge of the same partials."""
+"""Debug aid: vqseg_im2col_f against F.unfold (must be bit-exact).  Its second half prints the errors of vqseg_bn_finalize_f
+against a numpy double-precision merge of the same partials; that check is now ASSERTED by the suite
+(tests/test_nn_kernels_gpu.py::test_bn_finalize_training / test_bn_finalize_eval: both merge levels, with and without `sync`,
+up to 32768 slots) -- the printout stays only as a quick look while editing the merge kernels."""
 import os, sys
 import numpy as np
 import torch

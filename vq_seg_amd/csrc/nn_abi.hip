@@ -226,7 +226,7 @@ int vqseg_bn_backward_f(int bf16, const void* g_out, const void* out, const void
     if (!g_out || !y || !mean || !invstd || !gamma || !workspace || !dgamma || !dbeta || !g_y) return bad("bn_backward: null pointer");
     if (relu && !out && (!fwd_scale || !fwd_shift)) return bad("bn_backward: with ReLU pass either `out` or the forward scale/shift");
     if (relu && !out && g_res) return bad("bn_backward: a residual branch needs `out` (the mask depends on the residual)");
-    if (c <= 0) return bad("bn_backward: unsupported channel count");
+    if (c <= 0 || m_rows <= 0) return bad("bn_backward: bad size");
     float* partial = workspace;
     float* coef = workspace + (size_t)vqseg::bn_bwd_blocks(m_rows) * 2 * c;
     hipError_t e = vqseg::launch_bn_backward(bf16, g_out, out, y, mean, invstd, gamma, fwd_scale, fwd_shift, m_rows, c, relu, training, accumulate, partial, coef,
@@ -240,6 +240,7 @@ int vqseg_bn_backward_bits_f(const void* g_out, const unsigned char* bits, const
     if (!g_out || !bits || !y || !mean || !invstd || !gamma || !workspace || !dgamma || !dbeta || !g_y)
         return bad("bn_backward_bits: null pointer");
     if (c <= 0 || c % 8) return bad("bn_backward_bits: the channel count must be a multiple of 8");
+    if (m_rows <= 0) return bad("bn_backward_bits: bad size");
     float* partial = workspace;
     float* coef = workspace + (size_t)vqseg::bn_bwd_blocks(m_rows) * 2 * c;
     hipError_t e = vqseg::launch_bn_backward(1, g_out, nullptr, y, mean, invstd, gamma, nullptr, nullptr, m_rows, c, 1, training, accumulate, partial,
@@ -250,6 +251,7 @@ int vqseg_bn_backward_bits_f(const void* g_out, const unsigned char* bits, const
 int vqseg_maxpool3x3s2_f(int bf16, int backward, const void* x, const void* g, int n, int h, int w, int c, void* out,
                          unsigned char* idx, void* stream) {
     if (!out || (!x && !(backward && idx)) || (backward && !g)) return bad("maxpool: null pointer");
+    if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return bad("maxpool: bad size");
     hipError_t e = vqseg::launch_maxpool(bf16, backward, x, g, n, h, w, c, out, idx, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "maxpool");
 }

@@ -117,14 +117,14 @@ __device__ __forceinline__ PowerSums fold_slots(const float* partial, long s0, l
     if (c < C)
         for (long i = i_first; i < s1; i += 4 * step) {
             const double u = (double)rd((i * 2 + 0) * C + c), v = (double)rd((i * 2 + 1) * C + c);
-            if (merged) {
+            if (merged && i + 1 < s1) {                     // (hi, lo) pairs in the group's first two slots
                 a.s1 += u;
                 a.s2 += v;
-                if (i + 1 < s1) {                           // low parts in the next slot (groups hold >= 2 slots)
-                    a.s1 += (double)rd((i * 2 + 2) * C + c);
-                    a.s2 += (double)rd((i * 2 + 3) * C + c);
-                }
-            } else {
+                a.s1 += (double)rd((i * 2 + 2) * C + c);
+                a.s2 += (double)rd((i * 2 + 3) * C + c);
+            } else {                                        // a raw slot: level 1, or a last group of ONE slot, which level 1 leaves as it is
+                                                            // (it has no second slot for the low parts; S2 as one float costs the variance
+                                                            // 2^-24 mean^2 / var of that slot's weight: 2e-4 at |mean| = 1e3 std)
                 long n = M - i * rows_per_slot;
                 n = n < 0 ? 0 : (n > rows_per_slot ? rows_per_slot : n);
                 a.s1 += (double)n * u;
@@ -150,14 +150,12 @@ __global__ __launch_bounds__(256) void bn_stats_merge_kernel(float* __restrict__
     long s1 = s0 + slots_per_group;
     if (s1 > n_slots) s1 = n_slots;
     const PowerSums r = fold_slots(partial, s0, s1, 1, false, rows_per_slot, M, C, c, lds);
-    if ((threadIdx.x >> 6) == 0 && c < C) {                 // every read of this block's slots happened before the barrier
-        const float h1 = (float)r.s1, h2 = (float)r.s2;
+    if ((threadIdx.x >> 6) == 0 && c < C && s0 + 1 < s1) {  // every read of this block's slots happened before the barrier
+        const float h1 = (float)r.s1, h2 = (float)r.s2;     // (a group of one slot stays raw: see fold_slots)
         partial[(s0 * 2 + 0) * C + c] = h1;
         partial[(s0 * 2 + 1) * C + c] = h2;
-        if (s0 + 1 < s1) {
-            partial[(s0 * 2 + 2) * C + c] = (float)(r.s1 - (double)h1);
-            partial[(s0 * 2 + 3) * C + c] = (float)(r.s2 - (double)h2);
-        }
+        partial[(s0 * 2 + 2) * C + c] = (float)(r.s1 - (double)h1);
+        partial[(s0 * 2 + 3) * C + c] = (float)(r.s2 - (double)h2);
     }
 }
 
@@ -220,14 +218,12 @@ __global__ __launch_bounds__(256) void bn_stats_merge_finalize_kernel(float* par
     long s1 = s0 + slots_per_group;
     if (s1 > n_slots) s1 = n_slots;
     const PowerSums r = fold_slots(partial, s0, s1, 1, false, rows_per_slot, M, C, c, lds);
-    if ((threadIdx.x >> 6) == 0 && c < C) {
+    if ((threadIdx.x >> 6) == 0 && c < C && s0 + 1 < s1) {
         const float h1 = (float)r.s1, h2 = (float)r.s2;
         st_agent(partial + (s0 * 2 + 0) * C + c, h1);
         st_agent(partial + (s0 * 2 + 1) * C + c, h2);
-        if (s0 + 1 < s1) {
-            st_agent(partial + (s0 * 2 + 2) * C + c, (float)(r.s1 - (double)h1));
-            st_agent(partial + (s0 * 2 + 3) * C + c, (float)(r.s2 - (double)h2));
-        }
+        st_agent(partial + (s0 * 2 + 2) * C + c, (float)(r.s1 - (double)h1));
+        st_agent(partial + (s0 * 2 + 3) * C + c, (float)(r.s2 - (double)h2));
     }
     if (!last_workgroup_of(sync, blockIdx.x, gridDim.y)) return;
     if (num_batches_tracked && blockIdx.x == 0 && threadIdx.x == 0) *num_batches_tracked += 1;   // nn.BatchNorm2d bookkeeping
@@ -877,6 +873,30 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const T* __restrict__
     }
 }
 
+// Output positions [lo, hi] that can have input position i among their two taps (a superset; the caller tests each through bil_src).
+// Output d reads taps floor(s), floor(s) + 1 of its source coordinate s, so it touches i iff i - 1 < s < i + 1:
+//   align_corners: s = d (in-1)/(out-1)          ->  (i-1) (out-1)/(in-1) < d < (i+1) (out-1)/(in-1)
+//   else:          s = (d + 1/2) in/out - 1/2    ->  (i - 1/2) out/in - 1/2 < d < (i + 3/2) out/in - 1/2   (s clamps at 0: i = 0 reaches down to d = 0)
+// evaluated in integers and widened by one position each way, which covers the rounding of the fp32 s in bil_src.  A fixed radius of
+// out/in + 1 around i * out/in (the form this replaces) is short of the upper bound once out/in > 3 and under align_corners whenever
+// (out-1)/(in-1) is much larger than out/in (in = 2, out = 17: input row 0 lost outputs 11..15).  Extents < 2^15: 32-bit products.
+__device__ __forceinline__ void bil_bwd_range(int i, int in, int out, int align, int& lo, int& hi) {
+    if (in == 1 || out == 1) {
+        lo = 0;
+        hi = out - 1;
+        return;
+    }
+    if (align) {
+        lo = i > 0 ? ((i - 1) * (out - 1)) / (in - 1) - 1 : 0;
+        hi = ((i + 1) * (out - 1) + in - 2) / (in - 1) + 1;
+    } else {
+        lo = i > 0 ? ((2 * i - 1) * out) / (2 * in) - 1 : 0;
+        hi = ((2 * i + 3) * out + 2 * in - 1) / (2 * in);
+    }
+    if (lo < 0) lo = 0;
+    if (hi > out - 1) hi = out - 1;
+}
+
 // backward as a gather over the (few) output pixels whose footprint touches the input pixel
 template <typename T, int VC>
 __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const T* __restrict__ g, int N, int H, int W, int C, int Ho, int Wo,
@@ -884,17 +904,17 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const T* __restrict__
     constexpr int V = VecN<T>::N;
     const int cv = C / VC;
     const long total = (long)N * H * W * cv;
-    const int rh = (Ho + H - 1) / H + 1, rw = (Wo + W - 1) / W + 1;       // search radius in output pixels
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         int c, iw, ih, n;
         split_nhwc(i, cv, W, H, c, iw, ih, n);
         c *= VC;
-        const int ohc = (int)(((unsigned)ih * (unsigned)Ho) / (unsigned)H), owc = (int)(((unsigned)iw * (unsigned)Wo) / (unsigned)W);
+        int oh_lo, oh_hi, ow_lo, ow_hi;
+        bil_bwd_range(ih, H, Ho, align, oh_lo, oh_hi);
+        bil_bwd_range(iw, W, Wo, align, ow_lo, ow_hi);
         float acc[V];
 #pragma unroll
         for (int e = 0; e < VC; ++e) acc[e] = 0.0f;
-        for (int oh = ohc - rh; oh <= ohc + rh; ++oh) {
-            if (oh < 0 || oh >= Ho) continue;
+        for (int oh = oh_lo; oh <= oh_hi; ++oh) {
             int h0, h1;
             float lh;
             bil_src(oh, H, Ho, align, h0, h1, lh);
@@ -902,8 +922,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const T* __restrict__
             if (h0 == ih) wh += 1.0f - lh;
             if (h1 == ih) wh += lh;
             if (wh == 0.0f) continue;
-            for (int ow = owc - rw; ow <= owc + rw; ++ow) {
-                if (ow < 0 || ow >= Wo) continue;
+            for (int ow = ow_lo; ow <= ow_hi; ++ow) {
                 int w0, w1;
                 float lw;
                 bil_src(ow, W, Wo, align, w0, w1, lw);

@@ -556,6 +556,24 @@ int vqseg_batch_u8_f(int n, const uint8_t* img_cache, const uint8_t* mask_cache,
                      const int64_t* mask_offsets_host, int h, int w, int mh, int mw, const float* f32_lut, const int64_t* label_lut,
                      float* img_out, uint8_t* target_out, int64_t* label_out, void* stream);
 
+/* Box mix: CutMix / CutOut of a batch in one pass (vq_seg_amd.data.augmentations; the reference's CutMix.__call__ and augmentation(),
+ * data/augmentations.py:11-30, 62-73: batch[i] * mask + batch[(i + 1) % B] * (1 - mask) with a 0 / 1 box mask).  For a tensor of logical
+ * shape (n, planes, h, w):
+ *     out[s, p, y, x] = inside(box[s], y, x) ? (mode 0 MIX: src[(s + 1) % n, p, y, x] | mode 1 FILL: fill) : src[s, p, y, x]
+ * a selection by bits (no arithmetic): one kernel per element width (elem_bytes 1, 2, 4, 8: uint8, bf16, f32, int64).
+ *   src, out            out of place, the same layout; src is never written
+ *   stride_s/_p/_px     sample, plane and pixel strides in ELEMENTS (as vqseg_softmax_stats_f takes them), rows dense: planar (pixel stride 1,
+ *                       plane stride h * w: NCHW-contiguous, and 3-D label maps with planes = 1) or interleaved (plane stride 1, pixel
+ *                       stride planes: channels_last); anything else is VQSEG_EINVAL
+ *   boxes_host [n][4]   HOST array of (y1, x1, cut_h, cut_w) per sample; 0 <= y1, y1 + cut_h <= h, likewise x; cut_h or cut_w 0: empty box.
+ *                       The boxes travel as kernel arguments (64 samples per launch; the kernel sees the whole src and its block's first
+ *                       sample, since a sample's partner may belong to another block): no host-to-device copy, no synchronisation
+ *   fill_bits           mode 1: the fill value's bit pattern in the low elem_bytes bytes
+ * HBM-bound: one read and one write per element.  16-byte loads / stores where a sample starts on a 16-byte boundary (an edge of the
+ * box inside a 16-byte unit is exact), element-wise and coalesced elsewhere.  Grid capped by option "nn_grid_cap". */
+int vqseg_box_mix_f(int mode, int elem_bytes, const void* src, void* out, int n, int planes, int h, int w, int64_t stride_s,
+                    int64_t stride_p, int64_t stride_px, const int32_t* boxes_host, uint64_t fill_bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,7 @@ SYMBOLS = {
     "vqseg_adam_work_items": (c_int64, [c_int64, c_int, c_int, c_int]),
     "vqseg_adam_step_f32": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double, c_int64, c_void_p]),
     "vqseg_batch_u8_f": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 6),
+    "vqseg_box_mix_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 3 + [c_void_p, ctypes.c_uint64, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -527,6 +528,45 @@ def batch_u8(img_cache: torch.Tensor, img_offsets, hw: Tuple[int, int], f32_lut:
                                 tptr(target_out, "target_out", dtype=torch.uint8, numel=n * mh * mw),
                                 tptr(label_out, "label_out", dtype=torch.int64, numel=n * mh * mw), _stream())
     _check(rc, "vqseg_batch_u8_f")
+
+
+BOX_MIX_DTYPES = (torch.uint8, torch.bfloat16, torch.float32, torch.int64)       # element widths 1, 2, 4, 8: the kernel selects by bits
+BOX_MIX_CALLS = 0             # calls of box_mix that reached the library (tests assert the kernel path through it; never read by the product)
+
+
+def box_mix(src: torch.Tensor, boxes, mode: str = "mix", fill=0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """CutMix / CutOut of a batch (include/vqseg.h: vqseg_box_mix_f): for src (n, P, h, w) -- NCHW-contiguous or channels_last -- or
+    (n, h, w), out[s] = src[s] outside box[s] and, inside it, src[(s + 1) % n] (`mode` "mix") or `fill` ("fill").  `boxes`: n host rows
+    (y1, x1, cut_h, cut_w).  Out of place: returns `out` (default: a new tensor of src's layout); src is not written."""
+    global BOX_MIX_CALLS
+    L = lib()
+    if mode not in ("mix", "fill"):
+        raise HipLibraryError(f"box_mix: mode must be 'mix' or 'fill', got {mode!r}")
+    if not isinstance(src, torch.Tensor) or src.dim() not in (3, 4):
+        raise HipLibraryError("box_mix: src must be a (n, P, h, w) or (n, h, w) tensor")
+    n, (h, w) = src.shape[0], src.shape[-2:]
+    planes = src.shape[1] if src.dim() == 4 else 1
+    bx = np.ascontiguousarray(boxes, dtype=np.int32)
+    if bx.shape != (n, 4):
+        raise HipLibraryError(f"box_mix: one (y1, x1, cut_h, cut_w) box per sample required: {n} samples, boxes of shape {bx.shape}")
+    if n and (int(bx.min()) < 0 or int((bx[:, 0] + bx[:, 2]).max()) > h or int((bx[:, 1] + bx[:, 3]).max()) > w):
+        raise HipLibraryError(f"box_mix: a box lies outside the {h} x {w} image")
+    if out is None:
+        out = torch.empty_like(src)                          # dense src: the same strides
+    elif not isinstance(out, torch.Tensor) or out.shape != src.shape or out.stride() != src.stride():
+        raise HipLibraryError("box_mix: out must have src's shape and layout")
+    numel = n * planes * h * w
+    sp, op = tptr(src, "src", dtype=BOX_MIX_DTYPES, numel=numel), tptr(out, "out", dtype=src.dtype, numel=numel)
+    if numel == 0:
+        raise HipLibraryError("box_mix: empty tensor")
+    # tptr admits two dense layouts; the strides are stated from the layout (a size-1 dimension's own stride is arbitrary)
+    strides = (planes * h * w, h * w, 1) if src.is_contiguous() else (planes * h * w, 1, planes)
+    bits = int.from_bytes(torch.tensor([fill], dtype=src.dtype).view(torch.uint8).numpy().tobytes(), "little") if mode == "fill" else 0
+    with on_device(src.device):
+        rc = L.vqseg_box_mix_f(int(mode == "fill"), src.element_size(), sp, op, n, planes, h, w, *strides, bx.ctypes.data, bits, _stream())
+    _check(rc, "vqseg_box_mix_f")
+    BOX_MIX_CALLS += 1
+    return out
 
 
 def profile_begin(capacity: int = 4096) -> None:

@@ -1,4 +1,5 @@
-// data_kernels.hip -- batch assembly of the device-resident data loader (vq_seg_amd/data/device_loader.py).
+// data_kernels.hip -- batch assembly of the device-resident data loader (vq_seg_amd/data/device_loader.py), and the box mix of
+// CutMix / CutOut (vq_seg_amd/data/augmentations.py; second half of this file).
 //
 // Reference: BaseDataset.__getitem__ (data/dataset.py:47-57) turns a decoded, resized uint8 HWC image into float32 / 255
 // (TF.to_tensor) and returns the uint8 mask as it is; the training loop then maps the mask through img_to_label
@@ -111,6 +112,109 @@ __global__ __launch_bounds__(256) void batch_u8_kernel(BatchOffsets off, int nb,
     }
 }
 
+// ---- box mix (vq_seg_amd/data/augmentations.py: CutMix / CutOut / augmentation; the CPS step's strong augmentation) ---------------
+//
+// Reference: CutMix.__call__ / augmentation() (data/augmentations.py:11-30, 62-73) compute batch[i] * mask + batch[(i + 1) % B] * (1 - mask)
+// with a 0 / 1 box mask per sample of the batch, in Python.  With a 0 / 1 mask that arithmetic is a selection, and this kernel does it
+// as one: out[s, p, y, x] = inside(box[s], y, x) ? (MIX: src[(s + 1) % n, p, y, x] | FILL: fill) : src[s, p, y, x], by BITS (no
+// arithmetic), so float and integer tensors of the same element width share one instantiation and -0.0 / NaN payloads pass unchanged.
+// HBM-bound: per element one read (of the sample or of its partner, never both for a whole 16-byte unit outside / inside the box) and
+// one write, 2 x sizeof(element) bytes -- 8 B per f32, 16 B per int64 label, 4 B per bf16, 2 B per uint8.
+//
+// A sample is a dense run of `elems` = planes * h * w elements in either layout; it is walked as `lines` of `line` elements: planar
+// (NCHW, 3-D labels) planes * h lines of w elements, interleaved (channels_last) h lines of w * planes.  Element f lies in line f / line,
+// image row (f / line) % h, and in the box iff that row is in [y1, y1 + ch) and f % line in [x1 * g, (x1 + cw) * g), g = elements per pixel.
+// Work unit as in batch_u8_kernel: a 1 KiB tile of one sample per wave and iteration.  A whole tile of a 16-byte aligned sample takes
+// one 16-byte load and store per lane (contiguous across the wave); each element of the unit is selected on its own, so a box edge (or
+// a line end) inside a unit -- the rule with 12-byte channels_last f32 pixels -- is exact.  A sample's partial last tile, and every
+// tile of a sample that does not start on a 16-byte boundary, goes element by element, lane l taking elements l, l + 64, ... of the tile.
+constexpr int BOX_MODE_MIX = 0, BOX_MODE_FILL = 1;
+
+struct BoxArgs {                                            // 1 KiB of kernel arguments: BATCH_ARG_SAMPLES boxes
+    int y1[BATCH_ARG_SAMPLES], x1[BATCH_ARG_SAMPLES], ch[BATCH_ARG_SAMPLES], cw[BATCH_ARG_SAMPLES];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void box_mix_kernel(BoxArgs box, int s0, int nb, int n, int mode, int vec, const T* __restrict__ src,
+                                                      T* __restrict__ out, long stride_s, long elems, long line, int h, int g, T fill) {
+    constexpr int K = 16 / (int)sizeof(T);                  // elements per 16-byte unit
+    constexpr long TILE = 64L * K;                          // elements per 1 KiB tile
+    union Unit {
+        uint4 v;
+        T e[K];
+    };
+    const long stride = (long)gridDim.x * 256;
+    const long per = (elems + TILE - 1) / TILE * 64;        // units per sample, whole tiles
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < per * nb; c += stride) {
+        const int i = (int)(c / per);
+        const long u = c - i * per;
+        const long t = (u >> 6) * TILE;
+        const int l = (int)(u & 63);
+        const long s = s0 + i, p = s + 1 == n ? 0 : s + 1;  // the partner may lie in another launch's block: src is the whole tensor
+        const T* a = src + s * stride_s;
+        const T* b = src + p * stride_s;
+        T* o = out + s * stride_s;
+        const int y1 = box.y1[i], y2 = y1 + box.ch[i];
+        const long e1 = (long)box.x1[i] * g, e2 = e1 + (long)box.cw[i] * g;
+        if (vec && ((s * stride_s * (long)sizeof(T)) & 15) == 0 && t + TILE <= elems) {
+            const long f = t + (long)l * K;
+            Unit ua;
+            ua.v = *reinterpret_cast<const uint4*>(a + f);
+            const long ln = f / line;
+            long pos = f - ln * line;
+            int y = (int)(ln % h);
+            unsigned m = 0;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                m |= (unsigned)(y >= y1 && y < y2 && pos >= e1 && pos < e2) << k;
+                if (++pos == line) {
+                    pos = 0;
+                    if (++y == h) y = 0;
+                }
+            }
+            if (m) {
+                if (mode == BOX_MODE_FILL) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k)
+                        if ((m >> k) & 1u) ua.e[k] = fill;
+                } else if (((p * stride_s * (long)sizeof(T)) & 15) == 0) {
+                    Unit ub;
+                    ub.v = *reinterpret_cast<const uint4*>(b + f);
+#pragma unroll
+                    for (int k = 0; k < K; ++k) ua.e[k] = ((m >> k) & 1u) ? ub.e[k] : ua.e[k];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < K; ++k)
+                        if ((m >> k) & 1u) ua.e[k] = b[f + k];
+                }
+            }
+            *reinterpret_cast<uint4*>(o + f) = ua.v;
+        } else {
+            for (int j = 0; j < K; ++j) {
+                const long f = t + l + 64L * j;
+                if (f >= elems) break;
+                const long ln = f / line;
+                const long pos = f - ln * line;
+                const int y = (int)(ln % h);
+                const bool in = y >= y1 && y < y2 && pos >= e1 && pos < e2;
+                o[f] = in ? (mode == BOX_MODE_FILL ? fill : b[f]) : a[f];
+            }
+        }
+    }
+}
+
+template <typename T>
+static hipError_t launch_box_mix(const BoxArgs& box, int s0, int nb, int n, int mode, int vec, const void* src, void* out, long stride_s,
+                                 long elems, long line, int h, int g, unsigned long long fill_bits, hipStream_t st) {
+    constexpr long TILE = 64L * (16 / (long)sizeof(T));
+    long blocks = ((elems + TILE - 1) / TILE * nb + 3) / 4;  // 4 waves per workgroup, one tile per wave and iteration
+    const long cap = nn_grid_cap();
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(box_mix_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, box, s0, nb, n, mode, vec, static_cast<const T*>(src),
+                       static_cast<T*>(out), stride_s, elems, line, h, g, (T)fill_bits);
+    return hipGetLastError();
+}
+
 }  // namespace vqseg
 
 extern "C" {
@@ -162,6 +266,55 @@ int vqseg_batch_u8_f(int n, const uint8_t* img_cache, const uint8_t* mask_cache,
         if (e != hipSuccess) {
             char buf[160];
             snprintf(buf, sizeof(buf), "batch_u8_kernel: %s", hipGetErrorString(e));
+            return vqseg_set_error((int)e, buf);
+        }
+    }
+    return 0;
+}
+
+int vqseg_box_mix_f(int mode, int elem_bytes, const void* src, void* out, int n, int planes, int h, int w, int64_t stride_s,
+                    int64_t stride_p, int64_t stride_px, const int32_t* boxes_host, uint64_t fill_bits, void* stream) {
+    using namespace vqseg;
+    if (mode != BOX_MODE_MIX && mode != BOX_MODE_FILL) return vqseg_set_error(VQSEG_EINVAL, "box_mix: mode must be 0 (mix) or 1 (fill)");
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8)
+        return vqseg_set_error(VQSEG_EINVAL, "box_mix: element width must be 1, 2, 4 or 8 bytes");
+    if (n <= 0 || planes <= 0 || h <= 0 || w <= 0) return vqseg_set_error(VQSEG_EINVAL, "box_mix: n, planes, h and w must be positive");
+    if ((long)planes * h * w > (1L << 40)) return vqseg_set_error(VQSEG_EINVAL, "box_mix: sample larger than 2^40 elements");
+    if (!src || !out || !boxes_host) return vqseg_set_error(VQSEG_EINVAL, "box_mix: null src, out or boxes_host");
+    if (src == out) return vqseg_set_error(VQSEG_EINVAL, "box_mix: out of place only (a sample's partner is read after the sample is written)");
+    const long elems = (long)planes * h * w;
+    // rows dense, and the sample one dense run: planar (pixel stride 1, planes h * w apart) or interleaved (plane stride 1, pixels `planes` apart)
+    const bool planar = stride_px == 1 && (planes == 1 || stride_p == (int64_t)h * w);
+    const bool interleaved = planes > 1 && stride_p == 1 && stride_px == planes;
+    if (!planar && !interleaved)
+        return vqseg_set_error(VQSEG_EINVAL, "box_mix: layout must be planar (NCHW, 3-D labels) or interleaved (channels_last) with dense rows");
+    if (n > 1 && stride_s < elems) return vqseg_set_error(VQSEG_EINVAL, "box_mix: sample stride smaller than a sample");
+    for (int i = 0; i < n; ++i) {
+        const int32_t* b = boxes_host + 4 * (long)i;
+        if (b[0] < 0 || b[1] < 0 || b[2] < 0 || b[3] < 0 || (long)b[0] + b[2] > h || (long)b[1] + b[3] > w)
+            return vqseg_set_error(VQSEG_EINVAL, "box_mix: a box (y1, x1, cut_h, cut_w) lies outside the image");
+    }
+    const long line = planar ? w : (long)w * planes;
+    const int g = planar ? 1 : planes;
+    const int vec = (((uintptr_t)src | (uintptr_t)out) & 15u) == 0;      // per-sample alignment (s * stride_s): in the kernel
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (int s0 = 0; s0 < n; s0 += BATCH_ARG_SAMPLES) {
+        const int nb = n - s0 < BATCH_ARG_SAMPLES ? n - s0 : BATCH_ARG_SAMPLES;
+        BoxArgs box = {};
+        for (int i = 0; i < nb; ++i) {
+            const int32_t* b = boxes_host + 4 * (long)(s0 + i);
+            box.y1[i] = b[0], box.x1[i] = b[1], box.ch[i] = b[2], box.cw[i] = b[3];
+        }
+        hipError_t e;
+        switch (elem_bytes) {
+            case 1: e = launch_box_mix<uint8_t>(box, s0, nb, n, mode, vec, src, out, stride_s, elems, line, h, g, fill_bits, st); break;
+            case 2: e = launch_box_mix<uint16_t>(box, s0, nb, n, mode, vec, src, out, stride_s, elems, line, h, g, fill_bits, st); break;
+            case 4: e = launch_box_mix<uint32_t>(box, s0, nb, n, mode, vec, src, out, stride_s, elems, line, h, g, fill_bits, st); break;
+            default: e = launch_box_mix<uint64_t>(box, s0, nb, n, mode, vec, src, out, stride_s, elems, line, h, g, fill_bits, st); break;
+        }
+        if (e != hipSuccess) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "box_mix_kernel: %s", hipGetErrorString(e));
             return vqseg_set_error((int)e, buf);
         }
     }

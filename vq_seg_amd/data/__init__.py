@@ -1,3 +1,5 @@
-"""Data path (reference: data/dataset.py:15-62 `BaseDataset`); DeviceLoader feeds its batches from HBM."""
+"""Data path (reference: data/dataset.py:15-62 `BaseDataset`); DeviceLoader feeds its batches from HBM;
+CutMix / CutOut (reference: data/augmentations.py, data/__init__.py) on the box-mix kernel."""
 from .dataset import BaseDataset, write_synthetic_dataset  # noqa: F401
 from .device_loader import DeviceLoader, f32_table, label_table  # noqa: F401
+from .augmentations import CutMix, CutOut, aug_dict, augmentation, draw_box, make_aug, make_cutout_mask  # noqa: F401

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import dist as vdist
+from .data import augmentations
 from .loss import make_loss
 from .loss.dice_loss import DiceLoss, ce_dice_loss
 from .measurement import confusion_matrix_device, miou_device
@@ -208,6 +209,10 @@ class CPSConfig:
     two_streams: bool = True                  # each network of the pair on its own HIP stream (see CPSTrainer.__init__)
     wgrad_side_stream: bool = False           # opt-in: weight-gradient kernels on a side stream per network (nnf.WGRAD_SIDE_STREAMS); measured +-0 (r3)
     seed: int = 42
+    cutmix_ratio: Optional[float] = None      # CutMix (data/augmentations.py of the reference; deprecated/train_vqpt_easyhard_aug.py:90,119-123): the
+                                              # unlabelled TRAINING forwards see box-mixed images, the pseudo targets are mixed with the same boxes
+                                              # (area ratio of the box); None = the plain step, the mixing code is not entered
+    cutmix_boxes: str = "batch"               # "batch": one box per step for all samples (CutMix.__call__); "sample": one per sample (augmentation())
     extra: dict = field(default_factory=dict)
 
 
@@ -459,6 +464,23 @@ class CPSTrainer:
             with on(1):
                 score_2 = score_2.float()
             m1.train(); m2.train()
+            ul_train = ul_input
+            if cfg.cutmix_ratio is not None:
+                # CutMix: boxes on the host, a pure function of (seed, rank, iteration[, sample]) -- no generator state to checkpoint, nothing
+                # taken from the global generators.  The images are mixed ONCE (both networks get the same tensor object: one stem patch
+                # matrix), each score map on the stream that made it, before anything derives a pseudo label from it; from here on the
+                # step is the plain one on mixed scores and, for the two training forwards, mixed images.
+                boxes = augmentations.step_boxes(ul_input.shape[0], ul_input.shape[-2], ul_input.shape[-1], cfg.cutmix_ratio, cfg.seed,
+                                                 vdist.rank(), self.iter, cfg.cutmix_boxes)
+                clean_1, clean_2 = score_1, score_2
+                ul_train = augmentations.mix_boxes(ul_input, boxes)
+                if split:
+                    for s_ in streams:
+                        ul_train.record_stream(s_)                      # made on the caller's stream, read by both networks' streams
+                with on(0):
+                    score_1 = augmentations.mix_boxes(clean_1, boxes)
+                with on(1):
+                    score_2 = augmentations.mix_boxes(clean_2, boxes)
         if cfg.recipe == "v1":
             percent = 100 - cfg.unsup_loss_drop_percent * (1 - epoch_frac)
             kw = dict(percent=percent)
@@ -477,7 +499,7 @@ class CPSTrainer:
             streams[1].wait_event(e_gt[1])
             gt_ul_1.record_stream(streams[0])
             gt_ul_2.record_stream(streams[1])
-        (pu1, c_u1, _u, p_u1), (pu2, c_u2, usage, p_u2) = self._fwd_pair((ul_input, gt_ul_1), (ul_input, gt_ul_2), **kw)
+        (pu1, c_u1, _u, p_u1), (pu2, c_u2, usage, p_u2) = self._fwd_pair((ul_train, gt_ul_1), (ul_train, gt_ul_2), **kw)
         if not split:
             self._join()
         crit = self.criterion if cfg.recipe == "v1" else self._ce_dice
@@ -516,6 +538,10 @@ class CPSTrainer:
                     x.record_stream(main)
         if cfg.keep_aux:
             self.aux = dict(mask_1=mask_1, mask_2=mask_2, score_1=score_1, score_2=score_2, pred_sup_1=ps1.detach(), pred_ul_2=pu2.detach())
+            if cfg.cutmix_ratio is not None:                            # score_1 / score_2 stay the clean maps; what the step used comes beside them
+                if split:
+                    clean_1.record_stream(main), clean_2.record_stream(main)
+                self.aux.update(score_1=clean_1, score_2=clean_2, ul_mixed=ul_train, score_1_mixed=score_1, score_2_mixed=score_2, boxes=list(boxes))
         lr = self.sched.get_lr(self.iter)
         for o in self.opts:
             o.param_groups[0]["lr"] = lr

@@ -28,6 +28,38 @@ def test_library_exports_every_declared_symbol():
     assert L.vqseg_abi_version() == 1
 
 
+def header_signatures():
+    """name -> (restype, argtypes) as ctypes, parsed from the prototypes of include/vqseg.h (the header is the truth)"""
+    import ctypes as C
+    text = open(os.path.join(ROOT, "include", "vqseg.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    scalars = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+
+    def ctype(decl):
+        toks = [t for t in decl.replace("*", " * ").split() if t != "const"]
+        if len(toks) > 1 and toks[-1] not in scalars and toks[-1] not in ("void", "char", "hipStream_t", "*"):
+            toks.pop()                                          # the parameter's name
+        if toks == ["char", "*"]:
+            return C.c_char_p
+        if "*" in toks or toks == ["hipStream_t"]:
+            return C.c_void_p
+        return scalars[" ".join(toks)]
+
+    sigs = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(vqseg_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        sigs[name] = (ctype(ret), [ctype(p) for p in params.split(",") if p.strip() != "void"])
+    return sigs
+
+
+def test_ctypes_signatures_are_the_headers():
+    """Symbol names alone would let a c_int stand where the header says int64_t: every parameter and return type of every
+    prototype, mapped to ctypes, equals what _hip.SYMBOLS binds."""
+    sigs = header_signatures()
+    assert sorted(sigs) == header_symbols()
+    for name, sig in sigs.items():
+        assert _hip.SYMBOLS[name] == sig, f"{name}: include/vqseg.h says {sig}, _hip.SYMBOLS binds {_hip.SYMBOLS[name]}"
+
+
 def test_workspace_and_argument_validation_without_gpu():
     L = _hip.lib()
     assert L.vqseg_vq_workspace_bytes(8192, 512, 512) >= 512 * 512 * 4
@@ -38,6 +70,11 @@ def test_workspace_and_argument_validation_without_gpu():
     assert rc == -1 and b"multiple of 4" in L.vqseg_last_error()
     rc = L.vqseg_vq_assign_f32(None, None, None, 16, 8, 8, None, None, None, 0, None)
     assert rc == -1 and b"null" in L.vqseg_last_error()
+    # the bf16 entry points make the shared shape check first, then their own (8 bf16 = one 16-byte segment)
+    rc = L.vqseg_vq_assign_bf16(None, None, None, 16, 6, 8, None, None, None, 0, None)
+    assert rc == -1 and b"multiple of 4" in L.vqseg_last_error()
+    rc = L.vqseg_vq_assign_bf16(None, None, None, 16, 12, 8, None, None, None, 0, None)
+    assert rc == -1 and b"channels % 8 == 0" in L.vqseg_last_error()
     assert L.vqseg_kernel_name(b"vqseg_vq_forward_f32") == b"vq_assign_f32_kernel"
 
 
@@ -100,15 +137,30 @@ def test_tptr_checks_type_flag_size_density_then_device():
         _hip.tptr(f32[:, ::2], "rows", bf=0)
     with pytest.raises(E, match="expected a tensor"):
         _hip.tptr([1.0], "rows")
-    # everything else right: only now the device matters -- remembered, and raised by _stream(), the last argument of every launch,
-    # so that the other tensors of the same call get their type / size checks first
-    assert _hip.tptr(f32, "rows", bf=0, numel=32) == 0
+    # everything else right: only now the device matters.  tptr does not raise -- the other tensors of the same call get their type /
+    # size checks first -- and what it returns is nothing ctypes converts to a pointer: the fact travels with the argument
+    import ctypes
+    p = _hip.tptr(f32, "rows", bf=0, numel=32)
+    assert p is not None and not isinstance(p, int) and not hasattr(p, "_as_parameter_") and p + 64 is p
+    with pytest.raises(TypeError):
+        ctypes.c_void_p.from_param(p)
+    called = []
+    proto = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)
+    fn = proto(lambda ptr: called.append(ptr) or 0)
+    assert fn(None) == 0 and called == [None]
+    with pytest.raises(ctypes.ArgumentError):                        # refused before the foreign function is entered
+        fn(p)
+    assert called == [None]
     with pytest.raises(E, match="rows: the HIP path needs .* no CPU fallback"):
-        _hip._stream()
-    assert _hip.tptr(f32, "rows", bf=0) == 0
-    with pytest.raises(E, match="expected torch.int64"):            # a later type error wins and clears the pending device error
+        _hip.launch("vqseg_vq_assign_f32", f32.device, p, None, None, 4, 8, 8, None, None, None, 0)
+    with pytest.raises(E, match="rows: the HIP path needs .* no CPU fallback"):
+        _hip.on_gpu(p)
+    p = _hip.tptr(f32, "rows", bf=0)
+    with pytest.raises(E, match="expected torch.int64"):            # a later type error of the same call wins: it raises at once
         _hip.tptr(f32, "idx", dtype=torch.int64)
-    assert not _hip._NOT_ON_GPU
+    with pytest.raises(E, match="logits: expected a float32"):       # dense=False: a strided view, everything else still checked
+        _hip.tptr(bf, "logits", dtype=torch.float32, numel=32, dense=False)
+    assert type(_hip.tptr(f32[:, ::2], "logits", dtype=torch.float32, numel=16, dense=False)) is type(p)
 
 
 WRONG = [
@@ -171,6 +223,20 @@ def test_nnf_kernels_refuse_wrong_types_before_touching_a_device():
         nnf.softmax_stats(torch.zeros(1, 3, 4, 4), True, True)       # all types right on a CPU tensor: the device error surfaces
 
 
+def test_an_orphaned_tptr_result_does_not_reach_a_later_call():
+    """Nothing about a call is kept between tptr() and its launch: a result that is dropped (an unrelated exception between the two)
+    neither fails the next valid call under the wrong tensor's name nor hides that call's own errors."""
+    from vq_seg_amd import nnf
+    _hip.tptr(torch.zeros(4), "orphan", dtype=torch.float32)
+    with pytest.raises(_hip.HipLibraryError, match="logits") as e:
+        nnf.softmax_stats(torch.zeros(1, 3, 4, 4), True, True)
+    assert "orphan" not in str(e.value) and "no CPU fallback" in str(e.value)
+    _hip.tptr(torch.zeros(4), "orphan", dtype=torch.float32)
+    with pytest.raises(_hip.HipLibraryError, match="expected torch.float32") as e:
+        _hip.vq_forward(torch.zeros(8, 16, dtype=torch.float64), torch.zeros(4, 16), False, 1.0)
+    assert "orphan" not in str(e.value)
+
+
 def test_hip_adam_has_no_cpu_path_and_keeps_torch_adams_layout():
     """optim.HipAdam (r4): a torch.optim.Adam whose step is the HIP kernel -- CPU parameters are refused (no fallback), the
     argument checks of the entry point and the work-item count are host-side."""
@@ -182,6 +248,9 @@ def test_hip_adam_has_no_cpu_path_and_keeps_torch_adams_layout():
     with pytest.raises(_hip.HipLibraryError, match="no CPU fallback"):
         opt.step()
     assert torch.equal(p.detach(), torch.ones(4, 4))              # nothing was updated behind the error
+    opt.state[p]["exp_avg_sq"] = torch.zeros(4, 4, dtype=torch.float64)
+    with pytest.raises(_hip.HipLibraryError, match="exp_avg_sq: expected torch.float32"):
+        opt.step()                                                # a type error of a later tensor wins over the parameter's device error
     L = _hip.lib()
     assert L.vqseg_adam_work_items(4096 * 3 + 1, 0, 0, 0) == 4
     assert L.vqseg_adam_work_items(64 * 32 * 9, 3, 64, 32) == 2 and L.vqseg_adam_work_items(256 * 64, 1, 256, 64) == 8
@@ -190,7 +259,23 @@ def test_hip_adam_has_no_cpu_path_and_keeps_torch_adams_layout():
     assert L.vqseg_conv2d_wgrad2_f(None, None, None, 1, None, None, None, 1, 8, 4, 4, 8, 4, 4, 8, 3, 3, 1, 1, 0, 0, 8, 0, 0, None, 0, None, None) == -1
 
 
-def test_a_failed_fused_batchnorm_launch_zeroes_the_modules_counters():
+def test_profile_begin_raises_on_any_non_zero_code_and_collect_only_on_a_negative_one(monkeypatch):
+    """the begin calls answer 0 or an error code -- a HIP error code is positive -- and the collect calls a count"""
+    class Stub:
+        vqseg_profile_begin = vqseg_conv_profile_begin = staticmethod(lambda capacity: 2)          # hipErrorOutOfMemory
+        vqseg_profile_collect = vqseg_conv_profile_collect = staticmethod(lambda *a: 2)            # two records
+        vqseg_last_error = staticmethod(lambda: b"profile_begin: out of memory")
+    with pytest.raises(_hip.HipLibraryError, match=r"vqseg_profile_begin failed \(code -1\)"):
+        _hip.profile_begin(0)                                     # the library itself: capacity out of range
+    monkeypatch.setattr(_hip, "lib", lambda: Stub)
+    with pytest.raises(_hip.HipLibraryError, match=r"vqseg_profile_begin failed \(code 2\): profile_begin: out of memory"):
+        _hip.profile_begin()
+    with pytest.raises(_hip.HipLibraryError, match=r"vqseg_conv_profile_begin failed \(code 2\)"):
+        _hip.conv_profile_begin()
+    assert len(_hip.profile_collect(4)) == 2 and len(_hip.conv_profile_collect(4)) == 2
+
+
+def test_a_failed_fused_batchnorm_launch_zeroes_the_modules_counters(monkeypatch):
     """the opt-in fused BatchNorm launches hand over through per-module counters that must read zero between launches; an
     entry point that returns an error may leave them dirty -- the host wrapper zeroes them before raising."""
     import torch
@@ -198,10 +283,13 @@ def test_a_failed_fused_batchnorm_launch_zeroes_the_modules_counters():
     from vq_seg_amd import _hip, nnf
     bn = nn.BatchNorm2d(8)
     bn._vq_sync = torch.tensor([3, 0, 1, 0], dtype=torch.int32)
-    with pytest.raises(_hip.HipLibraryError):
-        nnf._check_fused_bn(_hip.lib().vqseg_bn_apply_f(1, None, None, None, None, 0, 0, 0, None, None), "vqseg_bn_apply_f (null arguments)", bn)
+    with pytest.raises(_hip.HipLibraryError):                   # the launch is refused (no GPU here): the error passes through the wrapper
+        nnf._check_fused_bn("vqseg_bn_apply_f", torch.device("cpu"), bn, 1, None, None, None, None, 0, 0, 0, None)
     assert int(bn._vq_sync.abs().sum()) == 0
-    nnf._check_fused_bn(0, "ok", bn)                            # a clean return code touches nothing
+    bn._vq_sync = torch.tensor([3, 0, 1, 0], dtype=torch.int32)
+    monkeypatch.setattr(nnf, "_launch", lambda name, dev, *args: None)
+    nnf._check_fused_bn("vqseg_bn_apply_f", torch.device("cpu"), bn, 1, None, None, None, None, 0, 0, 0, None)
+    assert bn._vq_sync.tolist() == [3, 0, 1, 0]                 # a clean launch touches nothing
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

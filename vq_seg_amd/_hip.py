@@ -3,14 +3,15 @@
 Torch is used only to own device memory and to name the current HIP stream; every
 argument crossing the boundary is a raw pointer or a size.  Fails loudly: a missing
 library, a CPU tensor, a wrong dtype or a non-zero return code raise.
+
+Two functions carry the protocol: `tptr` is the way a tensor becomes an argument, `launch` the way
+an entry point that takes a stream is called.  What is known about a call travels in its arguments;
+nothing is kept between the two.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes
 import os
-import threading
-import time
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 from typing import Optional, Tuple
 
@@ -165,23 +166,19 @@ PY_OPTS: dict = {}
 FILTER_DIAG = None            # set to a list to collect (n, c, k, open-row counter) of every bf16 grouped VQ forward (diagnostics only)
 
 
-def _check(rc: int, what: str) -> None:
-    _raise_if_not_on_gpu()
-    if rc != 0:
-        msg = lib().vqseg_last_error().decode(errors="replace")
-        raise HipLibraryError(f"{what} failed (code {rc}): {msg}")
-
-
 _BF_DTYPE = {0: torch.float32, 1: torch.bfloat16, 2: torch.bfloat16}      # the `bf16` flag of the entry points (2: split-3 [hi | lo] rows)
 
 
-def tptr(t, name: str, dtype=None, numel: Optional[int] = None, bf: Optional[int] = None, at_least: bool = False) -> Optional[int]:
+def tptr(t, name: str, dtype=None, numel: Optional[int] = None, bf: Optional[int] = None, at_least: bool = False, dense: bool = True):
     """THE way a tensor crosses the C ABI: returns its address after checking what the untyped `void*` on the other side cannot --
     the element type (`dtype`: one torch dtype or a tuple; or `bf`: the 0 / 1 / 2 activation-type flag that is passed to the SAME
-    entry point, so flag and buffer cannot disagree), dense memory, the element count the sizes passed along imply (`numel`, exact
-    unless `at_least`), and a 'cuda' (ROCm) device.  A bf16 buffer behind an f32 flag is a 2x out-of-bounds read on the GPU (it
-    happened: DESIGN 2, r2); here it is a Python exception.  The dtype / size checks come BEFORE the device check, so the CPU test
-    suite can feed every wrapper the wrong type (tests/test_abi_cpu.py).  None passes through as a null pointer."""
+    entry point, so flag and buffer cannot disagree), dense memory (not with `dense=False`: a view addressed through explicit
+    strides that are passed along, which a valid torch view bounds by construction), the element count the sizes passed along
+    imply (`numel`, exact unless `at_least`), and a 'cuda' (ROCm) device.  A bf16 buffer behind an f32 flag is a 2x out-of-bounds
+    read on the GPU (it happened: DESIGN 2, r2); here it is a Python exception.  Type, density and size errors are raised HERE;
+    a tensor that is right in all of these but not on the GPU comes back as a _NotOnGpu marker that `launch` refuses, so the
+    call's other tensors still get their type / size checks first and the CPU test suite can feed every wrapper the wrong type
+    (tests/test_abi_cpu.py).  None passes through as a null pointer."""
     if t is None:
         return None
     if bf is not None:
@@ -189,84 +186,92 @@ def tptr(t, name: str, dtype=None, numel: Optional[int] = None, bf: Optional[int
     try:                                                     # fast path: everything in order (one short-circuit expression per launch argument)
         if (dtype is None or t.dtype is dtype or (type(dtype) is tuple and t.dtype in dtype)) and t.is_cuda and \
                 (numel is None or (t.numel() >= numel if at_least else t.numel() == numel)) and \
-                (t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))):
+                (not dense or t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))):
             return t.data_ptr()
     except AttributeError:
         pass
-    return _tptr_report(t, name, dtype, numel, at_least)
+    return _tptr_report(t, name, dtype, numel, at_least, dense)
 
 
-def _tptr_report(t, name, dtype, numel, at_least):
+def _tptr_report(t, name, dtype, numel, at_least, dense):
     """slow path of tptr: say exactly what is wrong (type, density, size before the device)"""
     def bad(msg):
-        _NOT_ON_GPU.clear()
         return HipLibraryError(f"{name}: {msg}")
     if not isinstance(t, torch.Tensor):
         raise bad(f"expected a tensor, got {type(t).__name__}")
     if dtype is not None and (t.dtype not in dtype if isinstance(dtype, tuple) else t.dtype != dtype):
-        raise bad(f"expected {dtype}, got {t.dtype}")
-    if not t.is_contiguous() and not (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)):
+        if dense:
+            raise bad(f"expected {dtype}, got {t.dtype}")
+        names = " or ".join(str(d).removeprefix("torch.") for d in (dtype if isinstance(dtype, tuple) else (dtype,)))
+        raise bad(f"expected a {names} tensor, got {t.dtype}")           # the strided logits' wording, kept
+    if dense and not t.is_contiguous() and not (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)):
         raise bad(f"expected a dense (contiguous) tensor, got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
     if numel is not None and (t.numel() < numel if at_least else t.numel() != numel):
         raise bad(f"the sizes passed along need {'at least ' if at_least else ''}{numel} elements, the tensor has {t.numel()} (shape {tuple(t.shape)})")
     if not t.is_cuda:
-        # remembered, raised by _stream() -- the last argument every launch evaluates -- so that the OTHER tensors of the call still get
-        # their type / size checks first (a box without a GPU can then exercise them: tests/test_abi_cpu.py); nothing is launched
-        _NOT_ON_GPU.append(f"{name}: the HIP path needs a tensor on a 'cuda' (ROCm) device; got {t.device}. There is no CPU fallback.")
-        return 0
+        return _NotOnGpu(f"{name}: the HIP path needs a tensor on a 'cuda' (ROCm) device; got {t.device}. There is no CPU fallback.")
     return t.data_ptr()
 
 
-class _Pending(threading.local):
-    """Deferred 'tensor is not on the GPU' messages of the wrapper call in progress -- per thread (autograd runs backward wrappers
-    on its own threads), and short-lived: a message is raised by the SAME wrapper call microseconds later (_stream / _check); one
-    that is still here after two seconds was orphaned by an unrelated exception between a tptr() and its launch and must not
-    fail a later, valid call."""
+class _NotOnGpu:
+    """What tptr returns instead of an address for a tensor that is not on the GPU.  The fact travels with the argument: the marker
+    has no `_as_parameter_`, so ctypes refuses it for a `void*` parameter before the foreign function is entered, and `launch`
+    turns that refusal into the marker's message.  `+ offset` (an address inside a weight image) keeps the marker."""
+    __slots__ = ("msg",)
 
-    def __init__(self):
-        self.msgs = []
+    def __init__(self, msg: str):
+        self.msg = msg
 
-    def append(self, m):
-        self.msgs.append((time.monotonic(), m))
-
-    def clear(self):
-        self.msgs.clear()
-
-    def __bool__(self):
-        now = time.monotonic()
-        self.msgs = [e for e in self.msgs if now - e[0] < 2.0]
-        return bool(self.msgs)
-
-    def __getitem__(self, i):
-        return self.msgs[i][1]
+    def __add__(self, _offset):
+        return self
 
 
-_NOT_ON_GPU = _Pending()
+def on_gpu(ptr):
+    """a tptr() result that reaches the kernel some other way than as an argument of `launch` (inside a pointer array, a launch
+    table): the marker of a tensor that is not on the GPU raises here"""
+    if type(ptr) is _NotOnGpu:
+        raise HipLibraryError(ptr.msg)
+    return ptr
 
 
-def _raise_if_not_on_gpu() -> None:
-    if _NOT_ON_GPU:
-        msg = _NOT_ON_GPU[0]
-        _NOT_ON_GPU.clear()
-        raise HipLibraryError(msg)
-
-
-def _dev(t: torch.Tensor, dtype: torch.dtype, name: str, numel: Optional[int] = None) -> int:
+def _dev(t: torch.Tensor, dtype: torch.dtype, name: str, numel: Optional[int] = None):
     if t is None:
         raise HipLibraryError(f"{name}: expected a tensor, got None")
     return tptr(t, name, dtype=dtype, numel=numel)
 
 
-def on_device(dev):
-    """`torch.cuda.device(dev)` for the launch; a no-op for a non-GPU device, so that the argument checks (tptr) are what raises
-    when a CPU tensor reaches a wrapper."""
-    dev = torch.device(dev) if not isinstance(dev, torch.device) else dev
-    return torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()
-
-
 def _stream() -> int:
-    _raise_if_not_on_gpu()
     return torch.cuda.current_stream().cuda_stream
+
+
+def _failed(L, name: str, rc: int) -> HipLibraryError:
+    return HipLibraryError(f"{name} failed (code {rc}): {L.vqseg_last_error().decode(errors='replace')}")
+
+
+def launch(name: str, dev, *args, handle=None) -> None:
+    """THE way a kernel is launched: entry point `name` of lib() (or of `handle`, another build of the same ABI) with `args` and,
+    as its last argument, the current stream of `dev`, under that device's guard.  A non-zero return code raises HipLibraryError
+    with `name` and vqseg_last_error().  A tensor that is not on the GPU raises before the entry point is entered -- tptr's marker
+    among `args` is refused by ctypes itself -- so nothing is enqueued, and a null pointer can only mean an absent argument.  For a
+    `dev` that is no GPU the marker's message is raised before any stream is asked for (a box without a GPU has none); on a 'cuda'
+    device the stream handle is read while the arguments are put together, which enqueues nothing."""
+    L = handle or lib()
+    if type(dev) is not torch.device:
+        dev = torch.device(dev)
+    if dev.type == "cuda":
+        try:
+            with torch.cuda.device(dev):
+                rc = getattr(L, name)(*args, _stream())
+        except ctypes.ArgumentError:                         # costs the success path nothing
+            for a in args:
+                on_gpu(a)
+            raise
+        if rc != 0:
+            raise _failed(L, name, rc)
+        return
+    for a in args:
+        on_gpu(a)
+    raise HipLibraryError(f"{name}: the HIP path needs tensors on a 'cuda' (ROCm) device; got {dev}. There is no CPU fallback.")
 
 
 def _workspace(nbytes: int, device) -> torch.Tensor:
@@ -281,9 +286,7 @@ def vq_prepare(codebook: torch.Tensor) -> torch.Tensor:
     wp = _dev(codebook, torch.float32, "codebook")
     nbytes = L.vqseg_vq_prepared_bytes(c, k)
     blob = _workspace(nbytes, codebook.device)
-    with on_device(codebook.device):
-        rc = L.vqseg_vq_prepare_f32(wp, c, k, blob.data_ptr(), nbytes, _stream())
-    _check(rc, "vqseg_vq_prepare_f32")
+    launch("vqseg_vq_prepare_f32", codebook.device, wp, c, k, blob.data_ptr(), nbytes)
     return blob
 
 
@@ -302,13 +305,10 @@ def vq_forward(rows: torch.Tensor, codebook: torch.Tensor, training: bool, commi
     dmin = torch.empty(n, dtype=torch.float32, device=dev) if want_dmin else None
     nbytes = L.vqseg_vq_workspace_bytes(n, c, k)
     ws = _workspace(nbytes, dev)
-    with on_device(dev):
-        fwd = L.vqseg_vq_forward_bf16 if bf16 else L.vqseg_vq_forward_f32
-        rc = fwd(xp, wp, tptr(prepared, "prepared codebook", dtype=torch.uint8, numel=L.vqseg_vq_prepared_bytes(c, k)), n, c, k,
-                 int(bool(training)), float(commitment_weight), quant.data_ptr(),
-                 idx.data_ptr(), scal.data_ptr(), scal.data_ptr() + 4,
-                 dmin.data_ptr() if want_dmin else None, ws.data_ptr(), nbytes, _stream())
-    _check(rc, "vqseg_vq_forward_f32")
+    launch("vqseg_vq_forward_bf16" if bf16 else "vqseg_vq_forward_f32", dev, xp, wp,               # the entry point must match the row type
+           tptr(prepared, "prepared codebook", dtype=torch.uint8, numel=L.vqseg_vq_prepared_bytes(c, k)), n, c, k,
+           int(bool(training)), float(commitment_weight), quant.data_ptr(), idx.data_ptr(), scal.data_ptr(), scal.data_ptr() + 4,
+           dmin.data_ptr() if want_dmin else None, ws.data_ptr(), nbytes)
     out = (quant, idx, scal[0:1], scal[1])
     return out + (dmin,) if want_dmin else out
 
@@ -326,31 +326,28 @@ def vq_forward_group(rows_list, codebooks, prepared_list, training: bool, commit
     nl = len(rows_list)
     bf16 = rows_list[0].dtype == torch.bfloat16
     dev = rows_list[0].device
-    outs, keep = [], []
-    ptr = lambda ts: (c_void_p * nl)(*[t.data_ptr() for t in ts])
+    ptr = lambda ps: (c_void_p * nl)(*map(on_gpu, ps))         # the pointers travel inside a host array: a CPU tensor raises here
     ns = np.array([r.shape[0] for r in rows_list], dtype=np.int64)
     cs = np.array([r.shape[1] for r in rows_list], dtype=np.int32)
     ks = np.array([w.shape[0] for w in codebooks], dtype=np.int32)
     cw = np.array([float(w) for w in commitment_weights], dtype=np.float32)
-    quants, idxs, scals, wss = [], [], [], []
+    xs, wps, preps, quants, idxs, scals, wss = [], [], [], [], [], [], []
     for r, w in zip(rows_list, codebooks):
         if r.dtype != rows_list[0].dtype:
             raise HipLibraryError("vq_forward_group: one row type per call")
-        tptr(r, "rows", bf=int(bf16)), _dev(w, torch.float32, "codebook", w.shape[0] * r.shape[1])
+        xs.append(tptr(r, "rows", bf=int(bf16)))
+        wps.append(_dev(w, torch.float32, "codebook", w.shape[0] * r.shape[1]))
         quants.append(torch.empty_like(r))
         idxs.append(torch.empty(r.shape[0], dtype=torch.int64, device=dev))
         scals.append(torch.empty(2, dtype=torch.float32, device=dev))
         wss.append(_workspace(L.vqseg_vq_workspace_bytes(r.shape[0], r.shape[1], w.shape[0]), dev))
-    wsb = (c_size_t * nl)(*[w.numel() for w in wss])
-    loss_p = (c_void_p * nl)(*[s.data_ptr() for s in scals])
-    dead_p = (c_void_p * nl)(*[s.data_ptr() + 4 for s in scals])
     for w, p_ in zip(codebooks, prepared_list):
-        tptr(p_, "prepared codebook", dtype=torch.uint8, numel=L.vqseg_vq_prepared_bytes(w.shape[1], w.shape[0]))
-    with on_device(dev):
-        rc = L.vqseg_vq_forward_group(nl, int(bf16), ptr(rows_list), ptr(codebooks), ptr(prepared_list), ns.ctypes.data, cs.ctypes.data,
-                                      ks.ctypes.data, int(bool(training)), cw.ctypes.data, ptr(quants), ptr(idxs), loss_p, dead_p,
-                                      ptr(wss), ctypes.cast(wsb, c_void_p), _stream())
-    _check(rc, "vqseg_vq_forward_group")
+        preps.append(tptr(p_, "prepared codebook", dtype=torch.uint8, numel=L.vqseg_vq_prepared_bytes(w.shape[1], w.shape[0])))
+    wsb = (c_size_t * nl)(*[w.numel() for w in wss])
+    launch("vqseg_vq_forward_group", dev, nl, int(bf16), ptr(xs), ptr(wps), ptr(preps), ns.ctypes.data, cs.ctypes.data, ks.ctypes.data,
+           int(bool(training)), cw.ctypes.data, ptr(q.data_ptr() for q in quants), ptr(i.data_ptr() for i in idxs),
+           ptr(s.data_ptr() for s in scals), ptr(s.data_ptr() + 4 for s in scals), ptr(w.data_ptr() for w in wss),
+           ctypes.cast(wsb, c_void_p), handle=handle)
     if FILTER_DIAG is not None and bf16:                     # diagnostics (tools/vq_filter_diag.py): per level (rows, channels, codes, counter of candidate pairs)
         for r, w, ws_ in zip(rows_list, codebooks, wss):
             off = L.vqseg_vq_filter_counter_offset(r.shape[0], r.shape[1], w.shape[0])
@@ -378,11 +375,9 @@ def vq_assign(rows: torch.Tensor, codebook: torch.Tensor, want_dmin: bool = Fals
     dmin = torch.empty(n, dtype=torch.float32, device=dev) if want_dmin else None
     nbytes = L.vqseg_vq_workspace_bytes(n, c, k)
     ws = _workspace(nbytes, dev)
-    with on_device(dev):
-        fn = L.vqseg_vq_assign_bf16 if bf16 else L.vqseg_vq_assign_f32        # the entry point must match the row type
-        rc = fn(xp, wp, tptr(prepared, "prepared codebook", dtype=torch.uint8, numel=L.vqseg_vq_prepared_bytes(c, k)), n, c, k,
-                idx.data_ptr(), dmin.data_ptr() if want_dmin else None, ws.data_ptr(), nbytes, _stream())
-    _check(rc, "vqseg_vq_assign_bf16" if bf16 else "vqseg_vq_assign_f32")
+    launch("vqseg_vq_assign_bf16" if bf16 else "vqseg_vq_assign_f32", dev, xp, wp,                 # the entry point must match the row type
+           tptr(prepared, "prepared codebook", dtype=torch.uint8, numel=L.vqseg_vq_prepared_bytes(c, k)), n, c, k,
+           idx.data_ptr(), dmin.data_ptr() if want_dmin else None, ws.data_ptr(), nbytes)
     if want_filter_count:                                    # diagnostics: candidate pairs the bf16 filter handed to the exact re-score (None: no filter)
         off = L.vqseg_vq_filter_counter_offset(n, c, k) if bf16 else 0
         amb = ws[off:off + 256].view(torch.int32).sum() if off else None      # 64 sub-list counters
@@ -392,33 +387,26 @@ def vq_assign(rows: torch.Tensor, codebook: torch.Tensor, want_dmin: bool = Fals
 
 def vq_backward(grad_quant: torch.Tensor, grad_loss: Optional[torch.Tensor], rows: torch.Tensor, quant: torch.Tensor,
                 commitment_weight: float) -> torch.Tensor:
-    L = lib()
     n, c = rows.shape
     gq = _dev(grad_quant, torch.float32, "grad_quant", n * c)
     gl = _dev(grad_loss, torch.float32, "grad_loss", 1) if grad_loss is not None else None
     gx = torch.empty_like(rows)
-    with on_device(rows.device):
-        rc = L.vqseg_vq_backward_f32(gq, gl, _dev(rows, torch.float32, "rows", n * c), _dev(quant, torch.float32, "quant", n * c),
-                                     n, c, float(commitment_weight), gx.data_ptr(), _stream())
-    _check(rc, "vqseg_vq_backward_f32")
+    launch("vqseg_vq_backward_f32", rows.device, gq, gl, _dev(rows, torch.float32, "rows", n * c), _dev(quant, torch.float32, "quant", n * c),
+           n, c, float(commitment_weight), gx.data_ptr())
     return gx
 
 
 def vq_backward_bf16(grad_quant: torch.Tensor, grad_loss: Optional[torch.Tensor], rows: torch.Tensor, idx: torch.Tensor,
                      codebook: torch.Tensor, commitment_weight: float) -> torch.Tensor:
     """bf16 activations: grad_x = grad_quant + (2 w grad_loss / (N C)) (x - codebook[idx]), e re-read in fp32."""
-    L = lib()
     n, c = rows.shape
     gq = _dev(grad_quant, torch.bfloat16, "grad_quant", n * c)
     gl = _dev(grad_loss, torch.float32, "grad_loss", 1) if grad_loss is not None else None
     gx = torch.empty_like(rows)
     if codebook.dim() != 2 or codebook.shape[1] != c:
         raise HipLibraryError(f"codebook: expected (K, {c}), got {tuple(codebook.shape)}")
-    with on_device(rows.device):
-        rc = L.vqseg_vq_backward_bf16(gq, gl, _dev(rows, torch.bfloat16, "rows", n * c), _dev(idx, torch.int64, "idx", n),
-                                      _dev(codebook, torch.float32, "codebook"), n, c, float(commitment_weight), gx.data_ptr(),
-                                      _stream())
-    _check(rc, "vqseg_vq_backward_bf16")
+    launch("vqseg_vq_backward_bf16", rows.device, gq, gl, _dev(rows, torch.bfloat16, "rows", n * c), _dev(idx, torch.int64, "idx", n),
+           _dev(codebook, torch.float32, "codebook"), n, c, float(commitment_weight), gx.data_ptr())
     return gx
 
 
@@ -431,9 +419,7 @@ def kmeans(samples: torch.Tensor, means: torch.Tensor, iters: int) -> Tuple[torc
     bins = torch.zeros(k, dtype=torch.int64, device=samples.device)
     nbytes = L.vqseg_kmeans_workspace_bytes(n, c, k)
     ws = _workspace(nbytes, samples.device)
-    with on_device(samples.device):
-        rc = L.vqseg_kmeans_f32(sp, mp, bins.data_ptr(), n, c, k, int(iters), ws.data_ptr(), nbytes, _stream())
-    _check(rc, "vqseg_kmeans_f32")
+    launch("vqseg_kmeans_f32", samples.device, sp, mp, bins.data_ptr(), n, c, k, int(iters), ws.data_ptr(), nbytes)
     return means, bins
 
 
@@ -447,20 +433,14 @@ def kmeans_accumulate(samples: torch.Tensor, means: torch.Tensor) -> Tuple[torch
     counts = torch.empty(k, dtype=torch.int64, device=samples.device)
     nbytes = L.vqseg_kmeans_workspace_bytes(n, c, k)
     ws = _workspace(nbytes, samples.device)
-    with on_device(samples.device):
-        rc = L.vqseg_kmeans_accumulate_f32(sp, mp, n, c, k, sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes,
-                                           _stream())
-    _check(rc, "vqseg_kmeans_accumulate_f32")
+    launch("vqseg_kmeans_accumulate_f32", samples.device, sp, mp, n, c, k, sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes)
     return sums, counts
 
 
 def kmeans_finalize(sums: torch.Tensor, counts: torch.Tensor, means: torch.Tensor) -> torch.Tensor:
-    L = lib()
     k, c = means.shape
-    with on_device(means.device):
-        rc = L.vqseg_kmeans_finalize_f32(_dev(sums, torch.float32, "sums", k * c), _dev(counts, torch.int64, "counts", k),
-                                         _dev(means, torch.float32, "means", k * c), c, k, _stream())
-    _check(rc, "vqseg_kmeans_finalize_f32")
+    launch("vqseg_kmeans_finalize_f32", means.device, _dev(sums, torch.float32, "sums", k * c), _dev(counts, torch.int64, "counts", k),
+           _dev(means, torch.float32, "means", k * c), c, k)
     return means
 
 
@@ -475,27 +455,22 @@ def vq_code_sums(rows: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.T
     counts = torch.empty(k, dtype=torch.int64, device=rows.device)
     nbytes = L.vqseg_kmeans_workspace_bytes(n, c, k)
     ws = _workspace(nbytes, rows.device)
-    with on_device(rows.device):
-        rc = L.vqseg_vq_code_sums(int(rows.dtype == torch.bfloat16), tptr(rows, "rows", bf=int(rows.dtype == torch.bfloat16), numel=n * c), ip, n, c, k, sums.data_ptr(), counts.data_ptr(),
-                                  ws.data_ptr(), nbytes, _stream())
-    _check(rc, "vqseg_vq_code_sums")
+    bf = int(rows.dtype == torch.bfloat16)
+    launch("vqseg_vq_code_sums", rows.device, bf, tptr(rows, "rows", bf=bf, numel=n * c), ip, n, c, k, sums.data_ptr(), counts.data_ptr(),
+           ws.data_ptr(), nbytes)
     return sums, counts
 
 
 def vq_ema_update(cluster_size: torch.Tensor, embed_avg: torch.Tensor, codebook: torch.Tensor, sums: torch.Tensor,
                   counts: torch.Tensor, decay: float, eps: float) -> None:
     """In place: moving counts / sums and the codebook they imply (include/vqseg.h: vqseg_vq_ema_update_f32)."""
-    L = lib()
     k, c = codebook.shape
     if cluster_size.shape != (k,) or embed_avg.shape != (k, c) or sums.shape != (k, c) or counts.shape != (k,):
         raise ValueError("vq_ema_update: shapes must be (K,), (K, C), (K, C), (K, C), (K,)")
     scratch = torch.empty(1, dtype=torch.float32, device=codebook.device)
-    with on_device(codebook.device):
-        rc = L.vqseg_vq_ema_update_f32(_dev(cluster_size, torch.float32, "cluster_size"), _dev(embed_avg, torch.float32, "embed_avg"),
-                                       _dev(codebook, torch.float32, "codebook"), _dev(sums, torch.float32, "sums"),
-                                       _dev(counts, torch.int64, "counts"), c, k, float(decay), float(eps), scratch.data_ptr(),
-                                       _stream())
-    _check(rc, "vqseg_vq_ema_update_f32")
+    launch("vqseg_vq_ema_update_f32", codebook.device, _dev(cluster_size, torch.float32, "cluster_size"),
+           _dev(embed_avg, torch.float32, "embed_avg"), _dev(codebook, torch.float32, "codebook"), _dev(sums, torch.float32, "sums"),
+           _dev(counts, torch.int64, "counts"), c, k, float(decay), float(eps), scratch.data_ptr())
 
 
 def batch_u8(img_cache: torch.Tensor, img_offsets, hw: Tuple[int, int], f32_lut: torch.Tensor, img_out: torch.Tensor,
@@ -504,7 +479,6 @@ def batch_u8(img_cache: torch.Tensor, img_offsets, hw: Tuple[int, int], f32_lut:
              label_out: Optional[torch.Tensor] = None) -> None:
     """Gather n cached uint8 samples into a batch (include/vqseg.h: vqseg_batch_u8_f): img_out (n, 3, h, w) f32 channels_last,
     target_out (n, mh, mw) u8, label_out (n, mh, mw) i64.  Offsets are host sequences of byte offsets into the caches."""
-    L = lib()
     n = len(img_offsets)
     (h, w), (mh, mw) = hw, mask_hw
     io = np.ascontiguousarray(img_offsets, dtype=np.int64)
@@ -518,16 +492,12 @@ def batch_u8(img_cache: torch.Tensor, img_offsets, hw: Tuple[int, int], f32_lut:
             raise HipLibraryError("batch_u8: a mask offset lies outside the mask cache")
     if img_out.dim() != 4 or not img_out.is_contiguous(memory_format=torch.channels_last):
         raise HipLibraryError("batch_u8: img_out must be a channels_last (n, 3, h, w) tensor")
-    dev = img_out.device
-    with on_device(dev):
-        rc = L.vqseg_batch_u8_f(n, tptr(img_cache, "img_cache", dtype=torch.uint8), tptr(mask_cache, "mask_cache", dtype=torch.uint8),
-                                io.ctypes.data, mo.ctypes.data if mo is not None else None, h, w, mh, mw,
-                                tptr(f32_lut, "f32_lut", dtype=torch.float32, numel=256),
-                                tptr(label_lut, "label_lut", dtype=torch.int64, numel=256),
-                                tptr(img_out, "img_out", dtype=torch.float32, numel=n * 3 * h * w),
-                                tptr(target_out, "target_out", dtype=torch.uint8, numel=n * mh * mw),
-                                tptr(label_out, "label_out", dtype=torch.int64, numel=n * mh * mw), _stream())
-    _check(rc, "vqseg_batch_u8_f")
+    launch("vqseg_batch_u8_f", img_out.device, n, tptr(img_cache, "img_cache", dtype=torch.uint8), tptr(mask_cache, "mask_cache", dtype=torch.uint8),
+           io.ctypes.data, mo.ctypes.data if mo is not None else None, h, w, mh, mw,
+           tptr(f32_lut, "f32_lut", dtype=torch.float32, numel=256), tptr(label_lut, "label_lut", dtype=torch.int64, numel=256),
+           tptr(img_out, "img_out", dtype=torch.float32, numel=n * 3 * h * w),
+           tptr(target_out, "target_out", dtype=torch.uint8, numel=n * mh * mw),
+           tptr(label_out, "label_out", dtype=torch.int64, numel=n * mh * mw))
 
 
 BOX_MIX_DTYPES = (torch.uint8, torch.bfloat16, torch.float32, torch.int64)       # element widths 1, 2, 4, 8: the kernel selects by bits
@@ -539,7 +509,6 @@ def box_mix(src: torch.Tensor, boxes, mode: str = "mix", fill=0, out: Optional[t
     (n, h, w), out[s] = src[s] outside box[s] and, inside it, src[(s + 1) % n] (`mode` "mix") or `fill` ("fill").  `boxes`: n host rows
     (y1, x1, cut_h, cut_w).  Out of place: returns `out` (default: a new tensor of src's layout); src is not written."""
     global BOX_MIX_CALLS
-    L = lib()
     if mode not in ("mix", "fill"):
         raise HipLibraryError(f"box_mix: mode must be 'mix' or 'fill', got {mode!r}")
     if not isinstance(src, torch.Tensor) or src.dim() not in (3, 4):
@@ -562,19 +531,26 @@ def box_mix(src: torch.Tensor, boxes, mode: str = "mix", fill=0, out: Optional[t
     # tptr admits two dense layouts; the strides are stated from the layout (a size-1 dimension's own stride is arbitrary)
     strides = (planes * h * w, h * w, 1) if src.is_contiguous() else (planes * h * w, 1, planes)
     bits = int.from_bytes(torch.tensor([fill], dtype=src.dtype).view(torch.uint8).numpy().tobytes(), "little") if mode == "fill" else 0
-    with on_device(src.device):
-        rc = L.vqseg_box_mix_f(int(mode == "fill"), src.element_size(), sp, op, n, planes, h, w, *strides, bx.ctypes.data, bits, _stream())
-    _check(rc, "vqseg_box_mix_f")
+    launch("vqseg_box_mix_f", src.device, int(mode == "fill"), src.element_size(), sp, op, n, planes, h, w, *strides, bx.ctypes.data, bits)
     BOX_MIX_CALLS += 1
     return out
 
 
+def _checked(name: str, *args, counts: bool = False) -> int:
+    """an entry point that takes no stream: any non-zero return code is an error (a HIP error code is positive); with `counts`
+    the entry point answers a count (>= 0) and only a negative code is one"""
+    rc = getattr(lib(), name)(*args)
+    if rc < 0 or (rc and not counts):
+        raise _failed(lib(), name, rc)
+    return rc
+
+
 def profile_begin(capacity: int = 4096) -> None:
-    _check(lib().vqseg_profile_begin(int(capacity)), "vqseg_profile_begin")
+    _checked("vqseg_profile_begin", int(capacity))
 
 
 def conv_profile_begin(capacity: int = 65536) -> None:
-    _check(lib().vqseg_conv_profile_begin(int(capacity)), "vqseg_conv_profile_begin")
+    _checked("vqseg_conv_profile_begin", int(capacity))
 
 
 def conv_profile_collect(capacity: int = 65536, with_shape: bool = False):
@@ -583,9 +559,7 @@ def conv_profile_collect(capacity: int = 65536, with_shape: bool = False):
     kd = np.zeros(capacity, dtype=np.int32)
     ms = np.zeros(capacity, dtype=np.float32)
     sh = np.zeros((capacity, 4), dtype=np.int32)
-    cnt = lib().vqseg_conv_profile_collect(capacity, fl.ctypes.data, kd.ctypes.data, ms.ctypes.data, sh.ctypes.data if with_shape else None)
-    if cnt < 0:
-        _check(cnt, "vqseg_conv_profile_collect")
+    cnt = _checked("vqseg_conv_profile_collect", capacity, fl.ctypes.data, kd.ctypes.data, ms.ctypes.data, sh.ctypes.data if with_shape else None, counts=True)
     if with_shape:
         return [(float(fl[i]), int(kd[i]), float(ms[i]), tuple(int(v) for v in sh[i])) for i in range(cnt)]
     return [(float(fl[i]), int(kd[i]), float(ms[i])) for i in range(cnt)]
@@ -599,9 +573,7 @@ def profile_collect(capacity: int = 4096, with_kind: bool = False):
     k = np.zeros(capacity, dtype=np.int32)
     ms = np.zeros(capacity, dtype=np.float32)
     kd = np.zeros(capacity, dtype=np.int32)
-    cnt = lib().vqseg_profile_collect(capacity, n.ctypes.data, c.ctypes.data, k.ctypes.data, ms.ctypes.data, kd.ctypes.data)
-    if cnt < 0:
-        _check(cnt, "vqseg_profile_collect")
+    cnt = _checked("vqseg_profile_collect", capacity, n.ctypes.data, c.ctypes.data, k.ctypes.data, ms.ctypes.data, kd.ctypes.data, counts=True)
     if with_kind:
         return [(int(n[i]), int(c[i]), int(k[i]), float(ms[i]), int(kd[i])) for i in range(cnt)]
     return [(int(n[i]), int(c[i]), int(k[i]), float(ms[i])) for i in range(cnt)]

@@ -95,6 +95,7 @@ int vqseg_vq_prepare_f32(const float* codebook, int c, int k, void* prepared, si
 static int vq_assign_any(const void* x, int x_bf16, const float* codebook, const void* prepared, int64_t n, int c, int k,
                          int64_t* idx, float* dmin, void* ws, size_t ws_bytes, void* stream) {
     if (int rc = check_shape(n, c, k)) return rc;
+    if (x_bf16 && c % 8) return fail(VQSEG_EINVAL, "bf16 rows need channels %% 8 == 0");
     if (!x || !idx || !ws || (!codebook && !prepared)) return fail(VQSEG_EINVAL, "null pointer argument");
     if (!aligned16(x) || !aligned16(ws) || !aligned16(prepared) || !aligned16(codebook))
         return fail(VQSEG_EINVAL, "x, codebook, prepared and workspace must be 16-byte aligned");
@@ -119,7 +120,6 @@ int vqseg_vq_assign_f32(const float* x, const float* codebook, const void* prepa
 
 int vqseg_vq_assign_bf16(const void* x, const float* codebook, const void* prepared, int64_t n, int c, int k,
                          int64_t* idx, float* dmin, void* ws, size_t ws_bytes, void* stream) {
-    if (c % 8) return fail(VQSEG_EINVAL, "bf16 rows need channels %% 8 == 0");
     return vq_assign_any(x, 1, codebook, prepared, n, c, k, idx, dmin, ws, ws_bytes, stream);
 }
 
@@ -145,7 +145,6 @@ int vqseg_vq_forward_f32(const float* x, const float* codebook, const void* prep
 int vqseg_vq_forward_bf16(const void* x, const float* codebook, const void* prepared, int64_t n, int c, int k,
                           int training, float cw, void* quant, int64_t* idx, float* loss, float* dead_pct, float* dmin,
                           void* ws, size_t ws_bytes, void* stream) {
-    if (c % 8) return fail(VQSEG_EINVAL, "bf16 rows need channels %% 8 == 0");
     return vq_forward_any(x, 1, codebook, prepared, n, c, k, training, cw, quant, idx, loss, dead_pct, dmin, ws, ws_bytes, stream);
 }
 

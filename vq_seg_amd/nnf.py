@@ -18,7 +18,7 @@ import weakref
 import torch
 
 from . import _hip
-from ._hip import _check, _dev, _stream, lib
+from ._hip import lib
 from ._wcache import cache_of as _cache_of, invalidate as invalidate_weight_caches  # noqa: F401
 
 
@@ -44,6 +44,7 @@ def _is_bf16(t: torch.Tensor) -> int:
 
 
 _T = _hip.tptr                # every tensor handed to the library goes through this (dtype / density / element count / device checks)
+_launch = _hip.launch         # ... and every kernel launch through this (device guard, current stream, return code)
 
 
 def _w16(t, name, numel=None, at_least=False):
@@ -58,16 +59,7 @@ def _f32(t, name, numel=None):
 def _strided_f32(t, name, numel):
     """(B, C, H, W) fp32 logits addressed through the explicit (batch, class, pixel) strides passed along (NCHW and NHWC storage both
     qualify): a valid torch view bounds every such address by construction, so only type, element count and device are checked."""
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise _hip.HipLibraryError(f"{name}: expected a float32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if t.numel() != numel:
-        raise _hip.HipLibraryError(f"{name}: the sizes passed along need {numel} elements, the tensor has {t.numel()}")
-    if not t.is_cuda:                                        # deferred like _hip.tptr's: the call's other tensors are checked first
-        _hip._NOT_ON_GPU.append(f"{name}: the HIP path needs a tensor on a 'cuda' (ROCm) device; got {t.device}. There is no CPU fallback.")
-        return 0
-    return t.data_ptr()
+    return _T(t, name, dtype=torch.float32, numel=numel, dense=False)
 
 
 def act_dtype() -> torch.dtype:
@@ -109,12 +101,9 @@ def _pack_all(weight: torch.Tensor, kind):
             imgs["tr"] = torch.empty(cin * k * k * cout_p, dtype=torch.int16, device=w.device)
         if s3k is not None:
             imgs[s3k] = torch.empty(cout * k * k * 3 * cin, dtype=torch.int16, device=w.device)
-        with _hip.on_device(w.device):
-            _check(lib().vqseg_conv_pack_all_f32(_f32(w, "weight", cout * cin * k * k), cout, cin, k, s3k[1] if s3k is not None else cin,
-                                                 _w16(imgs.get("fwd"), "fwd image", cout * k * k * cin_p),
-                                                 _w16(imgs.get("tr"), "transposed image", cin * k * k * cout_p),
-                                                 _w16(imgs.get(s3k), "split-3 image", cout * k * k * 3 * cin) if s3k is not None else None,
-                                                 _stream()), "vqseg_conv_pack_all_f32")
+        _launch("vqseg_conv_pack_all_f32", w.device, _f32(w, "weight", cout * cin * k * k), cout, cin, k, s3k[1] if s3k is not None else cin,
+                _w16(imgs.get("fwd"), "fwd image", cout * k * k * cin_p), _w16(imgs.get("tr"), "transposed image", cin * k * k * cout_p),
+                _w16(imgs.get(s3k), "split-3 image", cout * k * k * 3 * cin) if s3k is not None else None)
         cache["all"] = imgs
     return imgs[kind]
 
@@ -135,9 +124,8 @@ def packed_weights(weight: torch.Tensor, precise: bool, transpose_flip: bool):
         n = lib().vqseg_conv_packed_elems(cout, cin, kh, kw, int(transpose_flip))
         hi = torch.empty(n, dtype=torch.int16, device=w.device)
         lo = torch.empty(n, dtype=torch.int16, device=w.device) if precise else None
-        with _hip.on_device(w.device):
-            _check(lib().vqseg_conv_pack_weights_f32(_f32(w, "weight", cout * cin * kh * kw), cout, cin, kh, kw, int(transpose_flip),
-                                                     _w16(hi, "packed hi", n), _w16(lo, "packed lo", n), _stream()), "vqseg_conv_pack_weights_f32")
+        _launch("vqseg_conv_pack_weights_f32", w.device, _f32(w, "weight", cout * cin * kh * kw), cout, cin, kh, kw, int(transpose_flip),
+                _w16(hi, "packed hi", n), _w16(lo, "packed lo", n))
         cache[k] = (hi, lo)
     return cache[k]
 
@@ -196,14 +184,12 @@ def _conv_raw(x_rows, x2_rows, w_hi, w_lo, stat, g: ConvGeom, up=1, w_offset_ele
     bfa = 0 if precise else 1
     wneed = w_offset_elems + g.packed
     nin = g.n * g.h * g.w
-    with _hip.on_device(x_rows.device):
-        rc = lib().vqseg_conv2d_f(_T(x_rows, "conv input", bf=bfa, numel=nin * g.c1), _T(x2_rows, "conv input 2", bf=bfa, numel=nin * (g.cin - g.c1)),
-                                  g.c1, _w16(w_hi, "packed weights", wneed, at_least=True) + w_offset_elems * esz,
-                                  (_w16(w_lo, "packed weights (lo)", wneed, at_least=True) + w_offset_elems * esz) if w_lo is not None else None,
-                                  _T(y, "conv output", bf=bfa, numel=g.m * g.cout),
-                                  _f32(stat, "BN partials", _stat_elems(g.m, g.cout) if stat is not None else None),
-                                  g.n, g.h, g.w, g.cin, g.cout, g.kh, g.kw, g.stride, g.pad, int(g.reflect), up, g.ho, g.wo, int(precise), _stream())
-    _check(rc, "vqseg_conv2d_f")
+    _launch("vqseg_conv2d_f", x_rows.device, _T(x_rows, "conv input", bf=bfa, numel=nin * g.c1),
+            _T(x2_rows, "conv input 2", bf=bfa, numel=nin * (g.cin - g.c1)), g.c1,
+            _w16(w_hi, "packed weights", wneed, at_least=True) + w_offset_elems * esz,
+            (_w16(w_lo, "packed weights (lo)", wneed, at_least=True) + w_offset_elems * esz) if w_lo is not None else None,
+            _T(y, "conv output", bf=bfa, numel=g.m * g.cout), _f32(stat, "BN partials", _stat_elems(g.m, g.cout) if stat is not None else None),
+            g.n, g.h, g.w, g.cin, g.cout, g.kh, g.kw, g.stride, g.pad, int(g.reflect), up, g.ho, g.wo, int(precise))
     return y
 
 
@@ -214,26 +200,21 @@ def _conv_affine(x_rows, x2_rows, w_hi, w_lo, scale, shift, res, relu, g: ConvGe
     wneed = g.cout * g.kh * g.kw * 3 * g.cin if mode == 2 else g.packed
     out = torch.empty((g.n, g.ho, g.wo, f * g.cout), dtype=_hip._BF_DTYPE[bf], device=x_rows.device)
     nin = g.n * g.h * g.w * f
-    with _hip.on_device(x_rows.device):
-        _check(lib().vqseg_conv2d_affine_f(_T(x_rows, "conv input", bf=bf, numel=nin * g.c1), _T(x2_rows, "conv input 2", bf=bf, numel=nin * (g.cin - g.c1)),
-                                           g.c1, _w16(w_hi, "packed weights", wneed), _w16(w_lo, "packed weights (lo)", wneed),
-                                           _f32(scale, "scale", g.cout), _f32(shift, "shift", g.cout),
-                                           _T(res, "residual", bf=bf, numel=g.m * g.cout * f), int(relu), _T(out, "conv output", bf=bf, numel=g.m * g.cout * f),
-                                           g.n, g.h, g.w, g.cin, g.cout, g.kh, g.kw, g.stride, g.pad, int(g.reflect), g.ho, g.wo, mode, _stream()),
-               "vqseg_conv2d_affine_f")
+    _launch("vqseg_conv2d_affine_f", x_rows.device, _T(x_rows, "conv input", bf=bf, numel=nin * g.c1),
+            _T(x2_rows, "conv input 2", bf=bf, numel=nin * (g.cin - g.c1)), g.c1, _w16(w_hi, "packed weights", wneed),
+            _w16(w_lo, "packed weights (lo)", wneed), _f32(scale, "scale", g.cout), _f32(shift, "shift", g.cout),
+            _T(res, "residual", bf=bf, numel=g.m * g.cout * f), int(relu), _T(out, "conv output", bf=bf, numel=g.m * g.cout * f), g.n, g.h, g.w,
+            g.cin, g.cout, g.kh, g.kw, g.stride, g.pad, int(g.reflect), g.ho, g.wo, mode)
     return out
 
 
 def _conv_affine_bits(x_rows, w_hi, scale, shift, res, bits, g: ConvGeom):
     """vqseg_conv2d_affine_bits_f (bf16, stride 1, zero padding) -> conv * scale + shift + res .* bits (a ReLU mask bit field)"""
     out = torch.empty((g.n, g.ho, g.wo, g.cout), dtype=torch.bfloat16, device=x_rows.device)
-    with _hip.on_device(x_rows.device):
-        _check(lib().vqseg_conv2d_affine_bits_f(_T(x_rows, "conv input", bf=1, numel=g.n * g.h * g.w * g.cin), _w16(w_hi, "packed weights", g.packed),
-                                                _f32(scale, "scale", g.cout), _f32(shift, "shift", g.cout),
-                                                _T(res, "residual", bf=1, numel=g.m * g.cout),
-                                                _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=g.m * g.cout // 8),
-                                                _T(out, "conv output", bf=1, numel=g.m * g.cout), g.n, g.h, g.w, g.cin, g.cout, g.kh, g.kw, g.pad,
-                                                g.ho, g.wo, _stream()), "vqseg_conv2d_affine_bits_f")
+    _launch("vqseg_conv2d_affine_bits_f", x_rows.device, _T(x_rows, "conv input", bf=1, numel=g.n * g.h * g.w * g.cin),
+            _w16(w_hi, "packed weights", g.packed), _f32(scale, "scale", g.cout), _f32(shift, "shift", g.cout),
+            _T(res, "residual", bf=1, numel=g.m * g.cout), _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=g.m * g.cout // 8),
+            _T(out, "conv output", bf=1, numel=g.m * g.cout), g.n, g.h, g.w, g.cin, g.cout, g.kh, g.kw, g.pad, g.ho, g.wo)
     return out
 
 
@@ -244,12 +225,10 @@ def _stem7_conv(xr, w_img, stat, coef, relu, stem: StemGeom, cout: int, s3: bool
     m = n * stem.fused[0] * stem.fused[1]
     out = torch.empty((n, stem.fused[0], stem.fused[1], f * cout), dtype=torch.bfloat16, device=xr.device)
     scale, shift = (coef[0], coef[1]) if coef is not None else (None, None)
-    with _hip.on_device(xr.device):
-        _check(lib().vqseg_stem7_conv_f(int(s3), _f32(xr, "image", n * stem.h * stem.w * stem.cin), _w16(w_img, "stem weight image", cout * f * 176),
-                                        _T(out, "conv output", bf=2 if s3 else 1, numel=m * cout * f),
-                                        _f32(stat, "BN partials", _stat_elems(m, cout) if stat is not None else None),
-                                        _f32(scale, "scale", cout), _f32(shift, "shift", cout), int(relu), n, stem.h, stem.w, int(stem.reflect),
-                                        _stream()), "vqseg_stem7_conv_f")
+    _launch("vqseg_stem7_conv_f", xr.device, int(s3), _f32(xr, "image", n * stem.h * stem.w * stem.cin),
+            _w16(w_img, "stem weight image", cout * f * 176), _T(out, "conv output", bf=2 if s3 else 1, numel=m * cout * f),
+            _f32(stat, "BN partials", _stat_elems(m, cout) if stat is not None else None), _f32(scale, "scale", cout), _f32(shift, "shift", cout),
+            int(relu), n, stem.h, stem.w, int(stem.reflect))
     return out
 
 
@@ -257,14 +236,13 @@ def _bn_finalize(stat, m, cout, gamma, beta, bn, training, dev):
     """vqseg_bn_finalize_f -> coef (4, C) f32 = scale, shift, mean, invstd: from the convolution's partial sums (`stat`; training also
     updates the running statistics and num_batches_tracked in the kernel) or, stat None, from the running statistics."""
     coef = torch.empty(4, cout, dtype=torch.float32, device=dev)
-    with _hip.on_device(dev):
-        _check_fused_bn(lib().vqseg_bn_finalize_f(
-            _f32(stat, "BN partials", _stat_elems(m, cout) if stat is not None else None), m, cout, _f32(gamma, "bn.weight", cout),
-            _f32(beta, "bn.bias", cout), _f32(bn.running_mean, "bn.running_mean", cout), _f32(bn.running_var, "bn.running_var", cout),
-            float(bn.momentum), float(bn.eps), int(training), _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout),
-            _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout),
-            _T(bn.num_batches_tracked, "bn.num_batches_tracked", dtype=torch.int64, numel=1) if training else None,
-            _T(_bn_sync(bn, False), "bn sync", dtype=torch.int32) if training else None, _stream()), "vqseg_bn_finalize_f", bn)
+    _check_fused_bn(
+        "vqseg_bn_finalize_f", dev, bn, _f32(stat, "BN partials", _stat_elems(m, cout) if stat is not None else None), m, cout,
+        _f32(gamma, "bn.weight", cout), _f32(beta, "bn.bias", cout), _f32(bn.running_mean, "bn.running_mean", cout),
+        _f32(bn.running_var, "bn.running_var", cout), float(bn.momentum), float(bn.eps), int(training), _f32(coef[0], "scale", cout),
+        _f32(coef[1], "shift", cout), _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout),
+        _T(bn.num_batches_tracked, "bn.num_batches_tracked", dtype=torch.int64, numel=1) if training else None,
+        _T(_bn_sync(bn, False), "bn sync", dtype=torch.int32) if training else None)
     return coef
 
 
@@ -272,10 +250,8 @@ def _bn_apply(y, rr, coef, m, cout, relu):
     """vqseg_bn_apply_f -> relu?(y * scale + shift [+ rr])"""
     bf = _is_bf16(y)
     out = torch.empty_like(y)
-    with _hip.on_device(y.device):
-        _check(lib().vqseg_bn_apply_f(bf, _T(y, "conv output", bf=bf, numel=m * cout), _T(rr, "residual", bf=bf, numel=m * cout),
-                                      _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout, int(relu),
-                                      _T(out, "BN output", bf=bf, numel=m * cout), _stream()), "vqseg_bn_apply_f")
+    _launch("vqseg_bn_apply_f", y.device, bf, _T(y, "conv output", bf=bf, numel=m * cout), _T(rr, "residual", bf=bf, numel=m * cout),
+            _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout, int(relu), _T(out, "BN output", bf=bf, numel=m * cout))
     return out
 
 
@@ -283,11 +259,9 @@ def _bn_apply_bits(y, rr, coef, m, cout):
     """vqseg_bn_apply_bits_f (bf16) -> relu(y * scale + shift + rr) and its ReLU mask as a bit field (1/16 of the output's bytes)"""
     out = torch.empty_like(y)
     bits = torch.empty(m * cout // 8, dtype=torch.uint8, device=y.device)
-    with _hip.on_device(y.device):
-        _check(lib().vqseg_bn_apply_bits_f(_T(y, "conv output", bf=1, numel=m * cout), _T(rr, "residual", bf=1, numel=m * cout),
-                                           _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout,
-                                           _T(out, "BN output", bf=1, numel=m * cout),
-                                           _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=m * cout // 8), _stream()), "vqseg_bn_apply_bits_f")
+    _launch("vqseg_bn_apply_bits_f", y.device, _T(y, "conv output", bf=1, numel=m * cout), _T(rr, "residual", bf=1, numel=m * cout),
+            _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout, _T(out, "BN output", bf=1, numel=m * cout),
+            _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=m * cout // 8))
     return out, bits
 
 
@@ -300,24 +274,22 @@ def _bn_backward(g, out, bits, y, coef, gamma, m, cout, relu, training, sink, dg
     g_y = torch.empty_like(y)
     nws = L.vqseg_bn_backward_workspace_floats(m, cout)
     ws = torch.empty(nws, dtype=torch.float32, device=y.device)
-    with _hip.on_device(y.device):
-        if bits is not None:
-            _check_fused_bn(L.vqseg_bn_backward_bits_f(
-                _T(g, "output gradient", bf=1, numel=m * cout), _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=m * cout // 8),
-                _T(y, "conv output", bf=1, numel=m * cout), _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout),
-                _f32(gamma.detach(), "bn.weight", cout), m, cout, int(training), int(sink), _f32(ws, "BN backward workspace", nws),
-                _f32(dgamma, "bn.weight.grad", cout), _f32(dbeta, "bn.bias.grad", cout),
-                _T(g_y, "conv output gradient", bf=1, numel=m * cout), _T(g_res, "residual gradient", bf=1, numel=m * cout),
-                _T(_bn_sync(bn, True), "bn sync", dtype=torch.int32), _stream()), "vqseg_bn_backward_bits_f", bn)
-        else:
-            _check_fused_bn(L.vqseg_bn_backward_f(
-                bf, _T(g, "output gradient", bf=bf, numel=m * cout), _T(out, "BN output", bf=bf, numel=m * cout),
-                _T(y, "conv output", bf=bf, numel=m * cout), _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout),
-                _f32(gamma.detach(), "bn.weight", cout), _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout), m, cout, int(relu),
-                int(training), int(sink), _f32(ws, "BN backward workspace", nws), _f32(dgamma, "bn.weight.grad", cout),
-                _f32(dbeta, "bn.bias.grad", cout), _T(g_y, "conv output gradient", bf=bf, numel=m * cout),
-                _T(g_res, "residual gradient", bf=bf, numel=m * cout), _T(_bn_sync(bn, True), "bn sync", dtype=torch.int32), _stream()),
-                "vqseg_bn_backward_f", bn)
+    if bits is not None:
+        _check_fused_bn(
+            "vqseg_bn_backward_bits_f", y.device, bn, _T(g, "output gradient", bf=1, numel=m * cout),
+            _T(bits, "ReLU mask bits", dtype=torch.uint8, numel=m * cout // 8), _T(y, "conv output", bf=1, numel=m * cout),
+            _f32(coef[2], "mean", cout), _f32(coef[3], "invstd", cout), _f32(gamma.detach(), "bn.weight", cout), m, cout, int(training),
+            int(sink), _f32(ws, "BN backward workspace", nws), _f32(dgamma, "bn.weight.grad", cout), _f32(dbeta, "bn.bias.grad", cout),
+            _T(g_y, "conv output gradient", bf=1, numel=m * cout), _T(g_res, "residual gradient", bf=1, numel=m * cout),
+            _T(_bn_sync(bn, True), "bn sync", dtype=torch.int32))
+    else:
+        _check_fused_bn(
+            "vqseg_bn_backward_f", y.device, bn, bf, _T(g, "output gradient", bf=bf, numel=m * cout),
+            _T(out, "BN output", bf=bf, numel=m * cout), _T(y, "conv output", bf=bf, numel=m * cout), _f32(coef[2], "mean", cout),
+            _f32(coef[3], "invstd", cout), _f32(gamma.detach(), "bn.weight", cout), _f32(coef[0], "scale", cout), _f32(coef[1], "shift", cout),
+            m, cout, int(relu), int(training), int(sink), _f32(ws, "BN backward workspace", nws), _f32(dgamma, "bn.weight.grad", cout),
+            _f32(dbeta, "bn.bias.grad", cout), _T(g_y, "conv output gradient", bf=bf, numel=m * cout),
+            _T(g_res, "residual gradient", bf=bf, numel=m * cout), _T(_bn_sync(bn, True), "bn sync", dtype=torch.int32))
     return g_y
 
 
@@ -326,10 +298,9 @@ def _reflect_ring(g_y, t_hi, gp, dg: ConvGeom):
     correlation and folded onto rows 1 / H-2 and columns 1 / W-2 of gp (the zero-padded data gradient) in place"""
     n, h, w, c = dg.n, dg.ho, dg.wo, dg.cout
     rbuf = torch.empty((n, 2 * (w + 2) + 2 * h, c), dtype=g_y.dtype, device=g_y.device)
-    with _hip.on_device(g_y.device):
-        _check(lib().vqseg_reflect_ring_f(_T(g_y, "conv output gradient", bf=1, numel=n * dg.h * dg.w * dg.cin), _w16(t_hi, "transposed image", dg.packed),
-                                          _T(rbuf, "gradient ring", bf=1, numel=rbuf.numel()), _T(gp, "input gradient", bf=1, numel=n * h * w * c),
-                                          n, h, w, dg.cin, c, _stream()), "vqseg_reflect_ring_f")
+    _launch("vqseg_reflect_ring_f", g_y.device, _T(g_y, "conv output gradient", bf=1, numel=n * dg.h * dg.w * dg.cin),
+            _w16(t_hi, "transposed image", dg.packed), _T(rbuf, "gradient ring", bf=1, numel=rbuf.numel()),
+            _T(gp, "input gradient", bf=1, numel=n * h * w * c), n, h, w, dg.cin, c)
 
 
 def _reflect_fold(gp, g: ConvGeom, c: int):
@@ -341,9 +312,8 @@ def _reflect_fold(gp, g: ConvGeom, c: int):
         raise NotImplementedError("reflect-padding data gradient is implemented for pad == 1")
     bf = _is_bf16(gp)
     gx = torch.empty((g.n, g.h, g.w, c), dtype=gp.dtype, device=gp.device)
-    with _hip.on_device(gp.device):
-        _check(lib().vqseg_reflect_fold_f(bf, _T(gp, "padded input gradient", bf=bf, numel=g.n * (g.h + 2) * (g.w + 2) * c), g.n, g.h, g.w, c,
-                                          _T(gx, "input gradient", bf=bf, numel=g.n * g.h * g.w * c), _stream()), "vqseg_reflect_fold_f")
+    _launch("vqseg_reflect_fold_f", gp.device, bf, _T(gp, "padded input gradient", bf=bf, numel=g.n * (g.h + 2) * (g.w + 2) * c), g.n, g.h, g.w, c,
+            _T(gx, "input gradient", bf=bf, numel=g.n * g.h * g.w * c))
     return gx
 
 
@@ -353,12 +323,10 @@ def _dgrad_s2(g_y, s_hi, s_lo, acc, g: ConvGeom, c: int, gh: int, gw: int):
     L = lib()
     bf = _is_bf16(g_y)
     gp = acc if acc is not None else torch.empty((g.n, gh, gw, c), dtype=g_y.dtype, device=g_y.device)
-    with _hip.on_device(g_y.device):
-        sneed = L.vqseg_conv_packed_s2_elems(g.cout, c, g.kh)
-        _check(L.vqseg_conv2d_dgrad_s2_f(_T(g_y, "conv output gradient", bf=bf, numel=g.m * g.cout), _w16(s_hi, "parity-class image", sneed),
-                                         _w16(s_lo, "parity-class image (lo)", sneed), _T(gp, "input gradient", bf=bf, numel=g.n * gh * gw * c),
-                                         g.n, g.ho, g.wo, g.cout, c, g.kh, gh, gw, int(not bf), int(acc is not None), _stream()),
-               "vqseg_conv2d_dgrad_s2_f")
+    sneed = L.vqseg_conv_packed_s2_elems(g.cout, c, g.kh)
+    _launch("vqseg_conv2d_dgrad_s2_f", g_y.device, _T(g_y, "conv output gradient", bf=bf, numel=g.m * g.cout),
+            _w16(s_hi, "parity-class image", sneed), _w16(s_lo, "parity-class image (lo)", sneed),
+            _T(gp, "input gradient", bf=bf, numel=g.n * gh * gw * c), g.n, g.ho, g.wo, g.cout, c, g.kh, gh, gw, int(not bf), int(acc is not None))
     return gp
 
 
@@ -369,11 +337,9 @@ def _dgrad_s2_fold(g_y, s_hi, g: ConvGeom, c: int):
     L = lib()
     rows = int(L.vqseg_conv2d_dgrad_s2_fold_rows(g.n, g.h, g.w, int(g.reflect)))
     buf = torch.empty((rows, c), dtype=g_y.dtype, device=g_y.device)
-    with _hip.on_device(g_y.device):
-        _check(L.vqseg_conv2d_dgrad_s2_fold_f(_T(g_y, "conv output gradient", bf=1, numel=g.m * g.cout),
-                                              _w16(s_hi, "parity-class image", L.vqseg_conv_packed_s2_elems(g.cout, c, 3)),
-                                              _T(buf, "input gradient (+ ring)", bf=1, numel=rows * c),
-                                              g.n, g.ho, g.wo, g.cout, c, g.h, g.w, int(g.reflect), _stream()), "vqseg_conv2d_dgrad_s2_fold_f")
+    _launch("vqseg_conv2d_dgrad_s2_fold_f", g_y.device, _T(g_y, "conv output gradient", bf=1, numel=g.m * g.cout),
+            _w16(s_hi, "parity-class image", L.vqseg_conv_packed_s2_elems(g.cout, c, 3)), _T(buf, "input gradient (+ ring)", bf=1, numel=rows * c),
+            g.n, g.ho, g.wo, g.cout, c, g.h, g.w, int(g.reflect))
     return buf[:g.n * g.h * g.w].view(g.n, g.h, g.w, c)
 
 
@@ -395,15 +361,17 @@ def _bn_sync(bn, backward: bool):
     return buf[g:] if backward else buf[:g]
 
 
-def _check_fused_bn(rc: int, what: str, bn) -> None:
-    """`_check` for the two entry points that take a module's hand-over counters: a launch that failed midway may leave them
-    non-zero, and every later fused launch on that module would then never elect a last workgroup (scale / shift / dgamma / dbeta
-    silently stale).  On a non-zero return code the module's counters are zeroed before the error is raised."""
-    if rc != 0:
+def _check_fused_bn(name: str, dev, bn, *args) -> None:
+    """`_launch` for the entry points that take a module's hand-over counters: a launch that failed midway may leave them non-zero,
+    and every later fused launch on that module would then never elect a last workgroup (scale / shift / dgamma / dbeta silently
+    stale).  When the launch raises, the module's counters are zeroed before the error propagates."""
+    try:
+        _launch(name, dev, *args)
+    except _hip.HipLibraryError:
         buf = getattr(bn, "_vq_sync", None)
         if buf is not None:
             buf.zero_()
-    _check(rc, what)
+        raise
 
 
 # Side streams for the weight-gradient kernels: {cuda_stream handle of a network's stream: torch.cuda.Stream}.  A trainer that owns
@@ -457,15 +425,12 @@ def _wgrad_launch(key: _WgradKey, a, b, gw, accumulate, stream):
             im2col, cin_out, st_, pd_, rf_ = 0, g.cin, g.stride, g.pad, int(g.reflect)
         nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n + nb, g.h, g.w, g.cin, g.ho, g.wo, g.cout, wkh, wkw)
         wsw = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with _hip.on_device(dev):
-            _check(L.vqseg_conv2d_wgrad2_f(_T(g_y, "conv output gradient", bf=bf, numel=n * nout), _T(xr, "conv input", bf=bf, numel=n * nin * g.c1),
-                                           _T(x2r, "conv input 2", bf=bf, numel=n * nin * (g.cin - g.c1)), n,
-                                           _T(gb, "conv output gradient (second use)", bf=bf, numel=nb * nout),
-                                           _T(xb, "conv input (second use)", bf=bf, numel=nb * nin * g.c1),
-                                           _T(x2b, "conv input 2 (second use)", bf=bf, numel=nb * nin * (g.cin - g.c1)), nb,
-                                           g.c1, g.h, g.w, g.cin, g.ho, g.wo, g.cout, okh, okw, st_, pd_, rf_, int(precise), cin_out, im2col, int(accumulate),
-                                           _T(wsw, "wgrad workspace", dtype=torch.uint8, numel=nbytes), nbytes,
-                                           _f32(gw, "weight gradient", g.cout * cin_out * okh * okw), _stream()), "vqseg_conv2d_wgrad2_f")
+        _launch("vqseg_conv2d_wgrad2_f", dev, _T(g_y, "conv output gradient", bf=bf, numel=n * nout),
+                _T(xr, "conv input", bf=bf, numel=n * nin * g.c1), _T(x2r, "conv input 2", bf=bf, numel=n * nin * (g.cin - g.c1)), n,
+                _T(gb, "conv output gradient (second use)", bf=bf, numel=nb * nout), _T(xb, "conv input (second use)", bf=bf, numel=nb * nin * g.c1),
+                _T(x2b, "conv input 2 (second use)", bf=bf, numel=nb * nin * (g.cin - g.c1)), nb, g.c1, g.h, g.w, g.cin, g.ho, g.wo, g.cout, okh, okw,
+                st_, pd_, rf_, int(precise), cin_out, im2col, int(accumulate), _T(wsw, "wgrad workspace", dtype=torch.uint8, numel=nbytes), nbytes,
+                _f32(gw, "weight gradient", g.cout * cin_out * okh * okw))
 
 
 def flush_pending_wgrads() -> int:
@@ -650,9 +615,8 @@ class S3:
         """merge back: logical (N, C, H, W) fp32 tensor (channels_last in memory)"""
         n, h, w, _ = self.rows.shape
         out = torch.empty((n, h, w, self.c), dtype=torch.float32, device=self.rows.device)
-        with _hip.on_device(out.device):
-            _check(lib().vqseg_s3_merge_f(_T(self.rows, "split-3 rows", bf=2, numel=n * h * w * 2 * self.c), n * h * w, self.c,
-                                          _f32(out, "merged rows", n * h * w * self.c), _stream()), "vqseg_s3_merge_f")
+        _launch("vqseg_s3_merge_f", out.device, _T(self.rows, "split-3 rows", bf=2, numel=n * h * w * 2 * self.c), n * h * w, self.c,
+                _f32(out, "merged rows", n * h * w * self.c))
         return _nchw(out)
 
 
@@ -685,9 +649,7 @@ def to_s3(x) -> "S3":
     xr = _rows(x.float())
     n, h, w, c = xr.shape
     out = torch.empty((n, h, w, 2 * c), dtype=torch.bfloat16, device=xr.device)
-    with _hip.on_device(xr.device):
-        _check(lib().vqseg_s3_split_f(_f32(xr, "rows", n * h * w * c), n * h * w, c, _T(out, "split-3 rows", bf=2, numel=n * h * w * 2 * c), _stream()),
-               "vqseg_s3_split_f")
+    _launch("vqseg_s3_split_f", xr.device, _f32(xr, "rows", n * h * w * c), n * h * w, c, _T(out, "split-3 rows", bf=2, numel=n * h * w * 2 * c))
     return S3(out, c)
 
 
@@ -713,10 +675,8 @@ def _s3_weights(weight: torch.Tensor, c1: int, as_1x1_cols: int = 0) -> torch.Te
         w = w if w.is_contiguous() else w.contiguous()
         cout, cin, kh, kw = w.shape
         out = torch.empty(cout * kh * kw * 3 * cin, dtype=torch.int16, device=w.device)
-        with _hip.on_device(w.device):
-            _check(lib().vqseg_conv_pack_weights_s3_f32(_f32(w, "weight", cout * cin * kh * kw), cout, cin, c1, kh, kw,
-                                                        _w16(out, "split-3 image", cout * kh * kw * 3 * cin), _stream()),
-                   "vqseg_conv_pack_weights_s3_f32")
+        _launch("vqseg_conv_pack_weights_s3_f32", w.device, _f32(w, "weight", cout * cin * kh * kw), cout, cin, c1, kh, kw,
+                _w16(out, "split-3 image", cout * kh * kw * 3 * cin))
         cache[k] = out
     return cache[k]
 
@@ -1038,10 +998,8 @@ def _s2_weights(weight, precise):
         nel = lib().vqseg_conv_packed_s2_elems(cout, cin, kh)
         hi = torch.empty(nel, dtype=torch.int16, device=w.device)
         lo = torch.empty(nel, dtype=torch.int16, device=w.device) if precise else None
-        with _hip.on_device(w.device):
-            _check(lib().vqseg_conv_pack_weights_s2_f32(_f32(w, "weight", cout * cin * kh * kh), cout, cin, kh, _w16(hi, "parity-class image", nel),
-                                                        _w16(lo, "parity-class image (lo)", nel), _stream()),
-                   "vqseg_conv_pack_weights_s2_f32")
+        _launch("vqseg_conv_pack_weights_s2_f32", w.device, _f32(w, "weight", cout * cin * kh * kh), cout, cin, kh,
+                _w16(hi, "parity-class image", nel), _w16(lo, "parity-class image (lo)", nel))
         cache[k] = (hi, lo)
     return cache[k]
 
@@ -1129,9 +1087,8 @@ def _stem_patches(xr, dt, kh, kw, s, p, reflect, ho, wo, kp):
     """the stem's im2col patch matrix [n][ho][wo][kp] of the fp32 image rows xr"""
     n, h, w, cin = xr.shape
     out = torch.empty((n, ho, wo, kp), dtype=dt, device=xr.device)
-    with _hip.on_device(xr.device):
-        _check(lib().vqseg_im2col_f(int(dt == torch.bfloat16), _f32(xr, "image", n * h * w * cin), n, h, w, cin, kh, kw, s, p, int(reflect), ho, wo, kp,
-                                    _T(out, "patches", bf=int(dt == torch.bfloat16), numel=n * ho * wo * kp), _stream()), "vqseg_im2col_f")
+    _launch("vqseg_im2col_f", xr.device, int(dt == torch.bfloat16), _f32(xr, "image", n * h * w * cin), n, h, w, cin, kh, kw, s, p, int(reflect), ho,
+            wo, kp, _T(out, "patches", bf=int(dt == torch.bfloat16), numel=n * ho * wo * kp))
     return out
 
 
@@ -1176,9 +1133,8 @@ def stem_conv_bn_act(x, conv, bn):
 
         def make3():
             out = torch.empty((n, ho, wo, 2 * kp3), dtype=torch.bfloat16, device=x.device)
-            with _hip.on_device(x.device):
-                _check(lib().vqseg_im2col_f(2, _f32(xr, "image", n * h * w * cin), n, h, w, cin, kh, kw, s, p, int(reflect), ho, wo, kp3,
-                                            _T(out, "split-3 patches", bf=2, numel=n * ho * wo * 2 * kp3), _stream()), "vqseg_im2col_f (split-3)")
+            _launch("vqseg_im2col_f", x.device, 2, _f32(xr, "image", n * h * w * cin), n, h, w, cin, kh, kw, s, p, int(reflect), ho, wo, kp3,
+                    _T(out, "split-3 patches", bf=2, numel=n * ho * wo * 2 * kp3))
             return out
 
         if fused_ok:                                             # no split-3 patch matrix (1.6 GB written, read by both networks)
@@ -1209,11 +1165,9 @@ class _MaxPool(torch.autograd.Function):
         ho, wo = _out_size(h, 3, 2, 1), _out_size(w, 3, 2, 1)
         y = torch.empty((n, ho, wo, c), dtype=xr.dtype, device=xr.device)
         idx = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=xr.device) if ctx.needs_input_grad[0] else None
-        with _hip.on_device(xr.device):
-            bf = _is_bf16(xr)
-            _check(lib().vqseg_maxpool3x3s2_f(bf, 0, _T(xr, "pool input", bf=bf, numel=n * h * w * c), None, n, h, w, c,
-                                              _T(y, "pool output", bf=bf, numel=n * ho * wo * c),
-                                              _T(idx, "pool argmax", dtype=torch.uint8, numel=n * ho * wo * c), _stream()), "vqseg_maxpool3x3s2_f")
+        bf = _is_bf16(xr)
+        _launch("vqseg_maxpool3x3s2_f", xr.device, bf, 0, _T(xr, "pool input", bf=bf, numel=n * h * w * c), None, n, h, w, c,
+                _T(y, "pool output", bf=bf, numel=n * ho * wo * c), _T(idx, "pool argmax", dtype=torch.uint8, numel=n * ho * wo * c))
         ctx.save_for_backward(idx)                          # window position of every maximum: the input is not kept
         ctx.cfg = (n, h, w, c, xr.dtype)
         ctx.fan = fan
@@ -1227,16 +1181,13 @@ class _MaxPool(torch.autograd.Function):
         gx = torch.empty((n, h, w, c), dtype=dt, device=gr.device)
         bf = int(dt == torch.bfloat16)
         add = _fanin_take(ctx.fan, (n, h, w, c), dt)       # the pooled tensor's other consumer deposited its gradient: added in the kernel
-        with _hip.on_device(gr.device):
-            if add is not None:
-                _check(lib().vqseg_maxpool3x3s2_backward_add_f(bf, _T(gr, "pool output gradient", bf=bf, numel=idx.numel()),
-                                                               _T(idx, "pool argmax", dtype=torch.uint8), _T(add, "fan-in gradient", bf=bf, numel=n * h * w * c),
-                                                               n, h, w, c, _T(gx, "pool input gradient", bf=bf, numel=n * h * w * c), _stream()),
-                       "vqseg_maxpool3x3s2_backward_add_f")
-            else:
-                _check(lib().vqseg_maxpool3x3s2_f(bf, 1, None, _T(gr, "pool output gradient", bf=bf, numel=idx.numel()), n, h, w, c,
-                                                  _T(gx, "pool input gradient", bf=bf, numel=n * h * w * c),
-                                                  _T(idx, "pool argmax", dtype=torch.uint8), _stream()), "vqseg_maxpool3x3s2_f")
+        if add is not None:
+            _launch("vqseg_maxpool3x3s2_backward_add_f", gr.device, bf, _T(gr, "pool output gradient", bf=bf, numel=idx.numel()),
+                    _T(idx, "pool argmax", dtype=torch.uint8), _T(add, "fan-in gradient", bf=bf, numel=n * h * w * c), n, h, w, c,
+                    _T(gx, "pool input gradient", bf=bf, numel=n * h * w * c))
+        else:
+            _launch("vqseg_maxpool3x3s2_f", gr.device, bf, 1, None, _T(gr, "pool output gradient", bf=bf, numel=idx.numel()), n, h, w, c,
+                    _T(gx, "pool input gradient", bf=bf, numel=n * h * w * c), _T(idx, "pool argmax", dtype=torch.uint8))
         if ctx.fan is not None and ctx.fan.leftover is not None:
             gx = gx + ctx.fan.leftover.reshape(gx.shape).to(dt)
             ctx.fan.leftover = None
@@ -1248,9 +1199,8 @@ def max_pool_3x3_s2(x):
         n, h, w, _ = x.rows.shape
         ho, wo = _out_size(h, 3, 2, 1), _out_size(w, 3, 2, 1)
         y = torch.empty((n, ho, wo, 2 * x.c), dtype=torch.bfloat16, device=x.rows.device)
-        with _hip.on_device(y.device):
-            _check(lib().vqseg_s3_maxpool3x3s2_f(_T(x.rows, "split-3 pool input", bf=2, numel=n * h * w * 2 * x.c), n, h, w, x.c,
-                                                 _T(y, "split-3 pool output", bf=2, numel=n * ho * wo * 2 * x.c), _stream()), "vqseg_s3_maxpool3x3s2_f")
+        _launch("vqseg_s3_maxpool3x3s2_f", y.device, _T(x.rows, "split-3 pool input", bf=2, numel=n * h * w * 2 * x.c), n, h, w, x.c,
+                _T(y, "split-3 pool output", bf=2, numel=n * ho * wo * 2 * x.c))
         return S3(y, x.c)
     return _MaxPool.apply(x, _fanin_of(x))
 
@@ -1261,10 +1211,9 @@ class _Bilinear(torch.autograd.Function):
         xr = _rows(x)
         n, h, w, c = xr.shape
         y = torch.empty((n, ho, wo, c), dtype=xr.dtype, device=xr.device)
-        with _hip.on_device(xr.device):
-            bf = _is_bf16(xr)
-            _check(lib().vqseg_bilinear_f(bf, 0, _T(xr, "resize input", bf=bf, numel=n * h * w * c), n, h, w, c, ho, wo, int(align),
-                                          _T(y, "resize output", bf=bf, numel=n * ho * wo * c), _stream()), "vqseg_bilinear_f")
+        bf = _is_bf16(xr)
+        _launch("vqseg_bilinear_f", xr.device, bf, 0, _T(xr, "resize input", bf=bf, numel=n * h * w * c), n, h, w, c, ho, wo, int(align),
+                _T(y, "resize output", bf=bf, numel=n * ho * wo * c))
         ctx.cfg = (n, h, w, c, ho, wo, int(align), xr.dtype)
         return _nchw(y)
 
@@ -1273,10 +1222,9 @@ class _Bilinear(torch.autograd.Function):
         n, h, w, c, ho, wo, align, dt = ctx.cfg
         gr = _rows(g).to(dt)
         gx = torch.empty((n, h, w, c), dtype=dt, device=gr.device)
-        with _hip.on_device(gr.device):
-            bf = int(dt == torch.bfloat16)
-            _check(lib().vqseg_bilinear_f(bf, 1, _T(gr, "resize output gradient", bf=bf, numel=n * ho * wo * c), n, h, w, c, ho, wo, align,
-                                          _T(gx, "resize input gradient", bf=bf, numel=n * h * w * c), _stream()), "vqseg_bilinear_f")
+        bf = int(dt == torch.bfloat16)
+        _launch("vqseg_bilinear_f", gr.device, bf, 1, _T(gr, "resize output gradient", bf=bf, numel=n * ho * wo * c), n, h, w, c, ho, wo, align,
+                _T(gx, "resize input gradient", bf=bf, numel=n * h * w * c))
         return _nchw(gx), None, None, None
 
 
@@ -1286,9 +1234,8 @@ def upsample_bilinear(x, size=None, scale_factor=None, align_corners=False):
     if isinstance(x, S3):
         n, h, w, _ = x.rows.shape
         y = torch.empty((n, int(size[0]), int(size[1]), 2 * x.c), dtype=torch.bfloat16, device=x.rows.device)
-        with _hip.on_device(y.device):
-            _check(lib().vqseg_s3_bilinear_f(_T(x.rows, "split-3 resize input", bf=2, numel=n * h * w * 2 * x.c), n, h, w, x.c, int(size[0]), int(size[1]),
-                                             int(bool(align_corners)), _T(y, "split-3 resize output", bf=2, numel=y.numel()), _stream()), "vqseg_s3_bilinear_f")
+        _launch("vqseg_s3_bilinear_f", y.device, _T(x.rows, "split-3 resize input", bf=2, numel=n * h * w * 2 * x.c), n, h, w, x.c, int(size[0]),
+                int(size[1]), int(bool(align_corners)), _T(y, "split-3 resize output", bf=2, numel=y.numel()))
         return S3(y, x.c)
     return _Bilinear.apply(x, int(size[0]), int(size[1]), bool(align_corners))
 
@@ -1304,10 +1251,9 @@ class _Head1x1(torch.autograd.Function):
         cout = weight.shape[0]
         wt = weight.detach().reshape(cout, cin).contiguous()
         y = torch.empty((n, h, w, cout), dtype=torch.float32, device=xr.device)
-        with _hip.on_device(xr.device):
-            bf = _is_bf16(xr)
-            _check(lib().vqseg_head1x1_forward_f(bf, _T(xr, "head input", bf=bf, numel=n * h * w * cin), _f32(wt, "head weight", cout * cin), n * h * w, cin,
-                                                 cout, _f32(y, "logits", n * h * w * cout), _stream()), "vqseg_head1x1_forward_f")
+        bf = _is_bf16(xr)
+        _launch("vqseg_head1x1_forward_f", xr.device, bf, _T(xr, "head input", bf=bf, numel=n * h * w * cin), _f32(wt, "head weight", cout * cin),
+                n * h * w, cin, cout, _f32(y, "logits", n * h * w * cout))
         ctx.save_for_backward(xr, wt)
         return _nchw(y)
 
@@ -1322,12 +1268,10 @@ class _Head1x1(torch.autograd.Function):
         gw = torch.empty((cout, cin), dtype=torch.float32, device=xr.device)
         ws = torch.empty(lib().vqseg_head1x1_backward_workspace_floats(m, cin, cout), dtype=torch.float32, device=xr.device)
         add = _fanin_take(ctx.fan, xr.shape, xr.dtype)      # the prototype loss's gradient of the same decoder output, if it came first
-        with _hip.on_device(xr.device):
-            bf = _is_bf16(xr)
-            _check(lib().vqseg_head1x1_backward_add_f(bf, _T(xr, "head input", bf=bf, numel=m * cin), _f32(wt, "head weight", cout * cin),
-                                                      _f32(gr, "logit gradient", m * cout), m, cin, cout, _T(gx, "head input gradient", bf=bf, numel=m * cin),
-                                                      _f32(gw, "head weight gradient", cout * cin), _f32(ws, "head workspace"),
-                                                      _T(add, "fan-in gradient", bf=bf, numel=m * cin), _stream()), "vqseg_head1x1_backward_add_f")
+        bf = _is_bf16(xr)
+        _launch("vqseg_head1x1_backward_add_f", xr.device, bf, _T(xr, "head input", bf=bf, numel=m * cin), _f32(wt, "head weight", cout * cin),
+                _f32(gr, "logit gradient", m * cout), m, cin, cout, _T(gx, "head input gradient", bf=bf, numel=m * cin),
+                _f32(gw, "head weight gradient", cout * cin), _f32(ws, "head workspace"), _T(add, "fan-in gradient", bf=bf, numel=m * cin))
         if ctx.fan is not None and ctx.fan.leftover is not None:
             gx = gx + ctx.fan.leftover.reshape(gx.shape).to(gx.dtype)
             ctx.fan.leftover = None
@@ -1340,9 +1284,8 @@ def head_conv1x1(x, weight):
         cout = weight.shape[0]
         wt = weight.detach().reshape(cout, x.c).contiguous()
         y = torch.empty((n, h, w, cout), dtype=torch.float32, device=x.rows.device)
-        with _hip.on_device(y.device):
-            _check(lib().vqseg_head1x1_forward_f(2, _T(x.rows, "split-3 head input", bf=2, numel=n * h * w * 2 * x.c), _f32(wt, "head weight", cout * x.c),
-                                                 n * h * w, x.c, cout, _f32(y, "logits", n * h * w * cout), _stream()), "vqseg_head1x1_forward_f")
+        _launch("vqseg_head1x1_forward_f", y.device, 2, _T(x.rows, "split-3 head input", bf=2, numel=n * h * w * 2 * x.c),
+                _f32(wt, "head weight", cout * x.c), n * h * w, x.c, cout, _f32(y, "logits", n * h * w * cout))
         return _nchw(y)
     return _Head1x1.apply(from_s3(x), weight, _fanin_of(x))
 
@@ -1355,10 +1298,8 @@ class _Cast(torch.autograd.Function):
             return x
         xr = _rows(x)
         y = torch.empty(xr.shape, dtype=dtype, device=xr.device)
-        with _hip.on_device(xr.device):
-            to_bf = int(dtype == torch.bfloat16)
-            _check(lib().vqseg_cast_f(to_bf, _T(xr, "cast input", bf=1 - to_bf), xr.numel(), _T(y, "cast output", bf=to_bf, numel=xr.numel()), _stream()),
-                   "vqseg_cast_f")
+        to_bf = int(dtype == torch.bfloat16)
+        _launch("vqseg_cast_f", xr.device, to_bf, _T(xr, "cast input", bf=1 - to_bf), xr.numel(), _T(y, "cast output", bf=to_bf, numel=xr.numel()))
         return _nchw(y)
 
     @staticmethod
@@ -1395,13 +1336,11 @@ class _ProtoLoss(torch.autograd.Function):
         nbytes = L.vqseg_proto_loss_workspace_bytes(m, c, k)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=xr.device)
         loss = torch.empty((), dtype=torch.float64, device=xr.device)
-        with _hip.on_device(xr.device):
-            bf = _is_bf16(xr)
-            _check(L.vqseg_proto_loss_forward_f(bf, _T(xr, "decoder features", bf=bf, numel=m * c), _f32(proto, "prototypes", k * c),
-                                                _T(labels, "labels", dtype=torch.int64, numel=m), _T(keep, "keep mask", dtype=torch.uint8, numel=m),
-                                                _f32(conf, "confidence", m), m, c, k, variant, float(scale), float(margin), int(easy_margin),
-                                                _T(ws, "workspace", dtype=torch.uint8, numel=nbytes), nbytes,
-                                                _T(loss, "loss", dtype=torch.float64, numel=1), _stream()), "vqseg_proto_loss_forward_f")
+        bf = _is_bf16(xr)
+        _launch("vqseg_proto_loss_forward_f", xr.device, bf, _T(xr, "decoder features", bf=bf, numel=m * c), _f32(proto, "prototypes", k * c),
+                _T(labels, "labels", dtype=torch.int64, numel=m), _T(keep, "keep mask", dtype=torch.uint8, numel=m), _f32(conf, "confidence", m), m,
+                c, k, variant, float(scale), float(margin), int(easy_margin), _T(ws, "workspace", dtype=torch.uint8, numel=nbytes), nbytes,
+                _T(loss, "loss", dtype=torch.float64, numel=1))
         ctx.save_for_backward(xr, proto, labels, keep, conf)
         ctx.cfg = (m, c, k, variant, float(scale), float(margin), int(easy_margin))
         return loss
@@ -1416,13 +1355,11 @@ class _ProtoLoss(torch.autograd.Function):
         gproto = torch.empty_like(proto) if ctx.needs_input_grad[1] else None
         nbytes = L.vqseg_proto_loss_workspace_bytes(m, c, k)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=xr.device)
-        with _hip.on_device(xr.device):
-            bf = _is_bf16(xr)
-            _check(L.vqseg_proto_loss_backward_f(bf, _T(xr, "decoder features", bf=bf, numel=m * c), _f32(proto, "prototypes", k * c),
-                                                 _T(labels, "labels", dtype=torch.int64, numel=m), _T(keep, "keep mask", dtype=torch.uint8, numel=m),
-                                                 _f32(conf, "confidence", m), m, c, k, variant, scale, margin, easy, _f32(g32, "loss gradient", 1),
-                                                 _T(gx, "feature gradient", bf=bf, numel=m * c), _f32(gproto, "prototype gradient", k * c),
-                                                 _T(ws, "workspace", dtype=torch.uint8, numel=nbytes), nbytes, _stream()), "vqseg_proto_loss_backward_f")
+        bf = _is_bf16(xr)
+        _launch("vqseg_proto_loss_backward_f", xr.device, bf, _T(xr, "decoder features", bf=bf, numel=m * c), _f32(proto, "prototypes", k * c),
+                _T(labels, "labels", dtype=torch.int64, numel=m), _T(keep, "keep mask", dtype=torch.uint8, numel=m), _f32(conf, "confidence", m), m,
+                c, k, variant, scale, margin, easy, _f32(g32, "loss gradient", 1), _T(gx, "feature gradient", bf=bf, numel=m * c),
+                _f32(gproto, "prototype gradient", k * c), _T(ws, "workspace", dtype=torch.uint8, numel=nbytes), nbytes)
         if _fanin_deposit(ctx.fan, gx):                      # the head's backward (same decoder output) adds it in its kernel
             return None, gproto, None, None, None, None, None, None, None, None
         return _nchw(gx), gproto, None, None, None, None, None, None, None, None
@@ -1457,11 +1394,9 @@ class _DiceSums(torch.autograd.Function):
         out = torch.empty(2, b, c, dtype=torch.float32, device=pred.device)
         ce = torch.empty(b, 2, dtype=torch.float32, device=pred.device) if want_ce else None
         ign = -(1 << 62) if ignore_index is None else int(ignore_index)
-        with _hip.on_device(pred.device):
-            _check(L.vqseg_dice_ce_sums_forward_f(_strided_f32(pred, "logits", b * c * h * w), sb, sc, sw, _T(tgt, "targets", dtype=torch.int64, numel=b * h * w),
-                                                  b, c, h * w, ign, _T(ws, "workspace", dtype=torch.uint8, numel=nbytes), nbytes,
-                                                  _f32(out[0], "intersections", b * c), _f32(out[1], "set sizes", b * c), _f32(ce, "cross-entropy sums", b * 2),
-                                                  _stream()), "vqseg_dice_ce_sums_forward_f")
+        _launch("vqseg_dice_ce_sums_forward_f", pred.device, _strided_f32(pred, "logits", b * c * h * w), sb, sc, sw,
+                _T(tgt, "targets", dtype=torch.int64, numel=b * h * w), b, c, h * w, ign, _T(ws, "workspace", dtype=torch.uint8, numel=nbytes),
+                nbytes, _f32(out[0], "intersections", b * c), _f32(out[1], "set sizes", b * c), _f32(ce, "cross-entropy sums", b * 2))
         ctx.save_for_backward(pred, tgt)
         ctx.cfg = (b, c, h * w, ign, (sb, sc, sw), want_ce)
         if want_ce:
@@ -1475,11 +1410,9 @@ class _DiceSums(torch.autograd.Function):
         g = torch.empty_strided(pred.shape, pred.stride(), dtype=torch.float32, device=pred.device)
         gi, gs = g_inter.float().contiguous(), g_sets.float().contiguous()
         gc = g_ce.float().contiguous() if (want_ce and g_ce is not None) else None
-        with _hip.on_device(pred.device):
-            _check(lib().vqseg_dice_ce_sums_backward_f(_strided_f32(pred, "logits", b * c * hw), sb, sc, sw, _T(tgt, "targets", dtype=torch.int64, numel=b * hw),
-                                                       b, c, hw, ign, _f32(gi, "d intersections", b * c), _f32(gs, "d set sizes", b * c),
-                                                       _f32(gc, "d cross-entropy sums", b * 2), _strided_f32(g, "logit gradient", b * c * hw), _stream()),
-                   "vqseg_dice_ce_sums_backward_f")
+        _launch("vqseg_dice_ce_sums_backward_f", pred.device, _strided_f32(pred, "logits", b * c * hw), sb, sc, sw,
+                _T(tgt, "targets", dtype=torch.int64, numel=b * hw), b, c, hw, ign, _f32(gi, "d intersections", b * c),
+                _f32(gs, "d set sizes", b * c), _f32(gc, "d cross-entropy sums", b * 2), _strided_f32(g, "logit gradient", b * c * hw))
         return g, None, None, None
 
 
@@ -1523,9 +1456,8 @@ class _ConvBias(torch.autograd.Function):
         def pack(tr):
             ne = L.vqseg_conv_packed_elems(cp, cin, kh, kw, int(tr))
             hi, lo = torch.empty(ne, dtype=torch.int16, device=dev), torch.empty(ne, dtype=torch.int16, device=dev)
-            with _hip.on_device(dev):
-                _check(L.vqseg_conv_pack_weights_f32(_f32(wp, "weight", cp * cin * kh * kw), cp, cin, kh, kw, int(tr), _w16(hi, "packed hi", ne),
-                                                     _w16(lo, "packed lo", ne), _stream()), "vqseg_conv_pack_weights_f32")
+            _launch("vqseg_conv_pack_weights_f32", dev, _f32(wp, "weight", cp * cin * kh * kw), cp, cin, kh, kw, int(tr), _w16(hi, "packed hi", ne),
+                    _w16(lo, "packed lo", ne))
             return hi, lo
 
         g = ConvGeom(n, h, w, cin, cin, cp, kh, kw, 1, pad, False, _out_size(h, kh, 1, pad), _out_size(w, kw, 1, pad))
@@ -1552,11 +1484,9 @@ class _ConvBias(torch.autograd.Function):
             nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n, h, w, cin, ho, wo, cp, kh, kw)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             gw4 = torch.empty((cp, cin, kh, kw), dtype=torch.float32, device=dev)
-            with _hip.on_device(dev):
-                _check(L.vqseg_conv2d_wgrad_f(_T(g4, "conv output gradient", bf=0, numel=n * ho * wo * cp), _T(xr, "conv input", bf=0, numel=n * h * w * cin),
-                                              None, cin, n, h, w, cin, ho, wo, cp, kh, kw, 1, pad, 0, 1, cin, 0, 0,
-                                              _T(ws, "wgrad workspace", dtype=torch.uint8, numel=nbytes), nbytes, _f32(gw4, "weight gradient", cp * cin * kh * kw),
-                                              _stream()), "vqseg_conv2d_wgrad_f")
+            _launch("vqseg_conv2d_wgrad_f", dev, _T(g4, "conv output gradient", bf=0, numel=n * ho * wo * cp),
+                    _T(xr, "conv input", bf=0, numel=n * h * w * cin), None, cin, n, h, w, cin, ho, wo, cp, kh, kw, 1, pad, 0, 1, cin, 0, 0,
+                    _T(ws, "wgrad workspace", dtype=torch.uint8, numel=nbytes), nbytes, _f32(gw4, "weight gradient", cp * cin * kh * kw))
             gw = gw4[:cout]
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = grad.sum(dim=(0, 2, 3))
@@ -1594,7 +1524,7 @@ class _CPSCombine(torch.autograd.Function):
         def arr(tensors, what, dtype=torch.float32):
             a = P4()
             for i, t in enumerate(tensors):
-                a[i] = _T(t, what, dtype=dtype) if t is not None else None
+                a[i] = _hip.on_gpu(_T(t, what, dtype=dtype))
             return a
 
         inter = arr([t[0] for t in terms], "intersections")
@@ -1604,11 +1534,9 @@ class _CPSCombine(torch.autograd.Function):
         g_sets = arr(views[1::per], "gradient of the set sizes")
         g_ce = arr(views[2::per], "gradient of the cross-entropy sums") if has_ce else None
         b_arr = (ctypes.c_int * 4)(*(bs + [0] * (4 - nt)))
-        with _hip.on_device(dev):
-            _check(lib().vqseg_cps_loss_combine_f(n_sup, n_cps, c, inter, sets, ce, b_arr, float(cps_w), float(ce_w), float(eps),
-                                                  arr(commits, "commitment losses"), n_commit, levels, float(commit_w),
-                                                  arr(protos, "prototype losses", dtype=torch.float64), n_proto, float(proto_w),
-                                                  g_inter, g_sets, g_ce, _f32(out, "loss terms", 4 + nt), _stream()), "vqseg_cps_loss_combine_f")
+        _launch("vqseg_cps_loss_combine_f", dev, n_sup, n_cps, c, inter, sets, ce, b_arr, float(cps_w), float(ce_w), float(eps),
+                arr(commits, "commitment losses"), n_commit, levels, float(commit_w), arr(protos, "prototype losses", dtype=torch.float64), n_proto,
+                float(proto_w), g_inter, g_sets, g_ce, _f32(out, "loss terms", 4 + nt))
         ctx.gbuf, ctx.sizes, ctx.shapes = gbuf, sizes, [tuple(x.shape) for t in terms for x in t]
         ctx.tail = (n_commit, n_proto, levels, float(commit_w), float(proto_w), [tuple(x.shape) for x in commits])
         total = out[0].clone()
@@ -1664,9 +1592,8 @@ def softmax_stats(logits, want_label=True, want_entropy=True, want_top=False):
     label = torch.empty((b, h, w), dtype=torch.int64, device=dev) if want_label else None
     ent = torch.empty((b, h, w), dtype=torch.float32, device=dev) if want_entropy else None
     top = torch.empty((b, h, w), dtype=torch.float32, device=dev) if want_top else None
-    with _hip.on_device(dev):
-        _check(lib().vqseg_softmax_stats_f(_strided_f32(x, "logits", b * c * h * w), sb, sc, sw, b, c, h * w, _T(label, "labels", dtype=torch.int64, numel=b * h * w),
-                                           _f32(ent, "entropy", b * h * w), _f32(top, "top probability", b * h * w), _stream()), "vqseg_softmax_stats_f")
+    _launch("vqseg_softmax_stats_f", dev, _strided_f32(x, "logits", b * c * h * w), sb, sc, sw, b, c, h * w,
+            _T(label, "labels", dtype=torch.int64, numel=b * h * w), _f32(ent, "entropy", b * h * w), _f32(top, "top probability", b * h * w))
     return label, ent, top
 
 
@@ -1682,9 +1609,8 @@ def percentile(values, percent: float):
     k = min(max(int(virtual), 0), n - 1)
     ws = torch.empty(lib().vqseg_order_stats_workspace_bytes(), dtype=torch.uint8, device=x.device)
     out = torch.empty(2, dtype=torch.float32, device=x.device)
-    with _hip.on_device(x.device):
-        _check(lib().vqseg_order_stats_f(_f32(x, "values", n), n, k, _T(ws, "workspace", dtype=torch.uint8), ws.numel(), _f32(out, "order statistics", 2),
-                                         _stream()), "vqseg_order_stats_f")
+    _launch("vqseg_order_stats_f", x.device, _f32(x, "values", n), n, k, _T(ws, "workspace", dtype=torch.uint8), ws.numel(),
+            _f32(out, "order statistics", 2))
     frac = virtual - k
     if frac <= 0.0:
         return out[0]

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _hip
-from ._hip import _check, lib
+from ._hip import lib
 
 _REC = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("numel", "<i8"), ("k", "<i4"), ("cout", "<i4"),
                  ("cin", "<i4"), ("c1", "<i4"), ("fwd", "<u8"), ("tr", "<u8"), ("s3", "<u8")])      # == struct VqsegAdamParam
@@ -68,13 +68,14 @@ class HipAdam(torch.optim.Adam):
         items = []
         images = []
         for i, (p, m, v, plan) in enumerate(zip(plist, exp_avgs, exp_avg_sqs, plans)):
+            r = rec[i]
+            r["numel"] = p.numel()
+            ptrs = []
             for t, name in ((p, "parameter"), (p.grad, "gradient"), (m, "exp_avg"), (v, "exp_avg_sq")):
-                _hip.tptr(t, name, dtype=torch.float32, numel=p.numel())
+                ptrs.append(_hip.tptr(t, name, dtype=torch.float32, numel=p.numel()))
                 if not t.is_contiguous():
                     raise _hip.HipLibraryError(f"HipAdam: {name} of a {tuple(p.shape)} parameter is not contiguous")
-            _hip._raise_if_not_on_gpu()
-            r = rec[i]
-            r["p"], r["g"], r["m"], r["v"], r["numel"] = p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+            r["p"], r["g"], r["m"], r["v"] = map(_hip.on_gpu, ptrs)     # the kernel reads them from this table: type / size errors of all four first
             imgs = None
             if plan is not None:
                 k, sizes, c1 = plan
@@ -107,7 +108,6 @@ class HipAdam(torch.optim.Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = lib()
         for gi, group in enumerate(self.param_groups):
             if group["weight_decay"] != 0 or group["amsgrad"] or group["maximize"] or group.get("capturable") or group.get("differentiable"):
                 raise NotImplementedError("HipAdam implements the reference's call: Adam(params, lr, betas) with the defaults")
@@ -133,9 +133,8 @@ class HipAdam(torch.optim.Adam):
                 ms = exp_avgs if len(by_step) == 1 else [exp_avgs[i] for i in idx]
                 vs = exp_avg_sqs if len(by_step) == 1 else [exp_avg_sqs[i] for i in idx]
                 tab = self._table(sub, ps, ms, vs)
-                with _hip.on_device(ps[0].device):
-                    _check(L.vqseg_adam_step_f32(tab["rec"].data_ptr(), tab["items"].data_ptr(), tab["n_items"], lr, float(beta1), float(beta2),
-                                                 float(group["eps"]), step, _hip._stream()), "vqseg_adam_step_f32")
+                _hip.launch("vqseg_adam_step_f32", ps[0].device, tab["rec"].data_ptr(), tab["items"].data_ptr(), tab["n_items"], lr, float(beta1),
+                            float(beta2), float(group["eps"]), step)
                 for p, imgs in zip(ps, tab["images"]):
                     if imgs is not None:
                         # the images ARE those of the new values: install them (the post-step hook of _wcache keeps a "fresh" cache)

@@ -487,6 +487,49 @@ int vqseg_softmax_stats_f(const float* logits, int64_t stride_b, int64_t stride_
 int vqseg_confusion_counts_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px,
                              const int64_t* target, int b, int c, int64_t hw, int64_t* counts, void* stream);
 
+/* Focal loss of loss/focal_loss.py:6-50 in one pass over the logits (layout, 2..4 classes and int64 targets as for the Dice
+ * sums).  Per pixel, with keep = target != ignore_index:
+ *   z = keep ? logits : 0,  t = keep ? target : 0,  p = softmax(z),  l = alpha * w[t] * (1 - p_t)^gamma * (-log p_t)
+ * with -log p_t in log-softmax form (log sum exp(z - max) + max - z_t) and w = `weight`, C floats in DEVICE memory, or NULL = 1.
+ * The reference's quirks are kept: an ignored pixel is not skipped but a zero-logit class-0 pixel that contributes
+ * alpha * w[0] * (1 - 1/C)^gamma * log C (:12-14); 'mean' divides by all b * hw pixels (:43); the weights normalise nothing
+ * (:42 is overwritten by :43).  pre_softmax != 0 is the MODULE FocalLoss.forward (:62-68), which softmaxes before calling
+ * focal_loss: z = keep ? softmax(logits) : 0, then the same; backward goes through both softmaxes in closed form.
+ * A target outside [0, c) other than ignore_index contributes 0 (the reference raises).  gamma == 0 or gamma >= 1 (between
+ * the two the derivative is unbounded at p_t = 1: rejected); integer gamma <= 4 is evaluated by multiplications.
+ *   forward : per_image[b] = sum_px l in double (block partials folded in block order), loss2[0] = sum_b per_image[b]
+ *             ('sum'), loss2[1] = that / (b * hw) ('mean'); loss_map (nullable) [b][hw] = l ('none').
+ *   backward: g_logits (the logits' layout) = d (sum_px g l) / d logits with g = g_scalar[0] * scale (DEVICE scalar; scale = 1
+ *             for 'sum', 1 / (b * hw) for 'mean') or g = g_map[b][px]; exactly one of g_scalar / g_map.  Ignored pixels: 0.
+ * workspace: vqseg_focal_workspace_bytes(b, hw) (also what vqseg_wce_sums_forward_f needs). */
+size_t vqseg_focal_workspace_bytes(int b, int64_t hw);
+int vqseg_focal_forward_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px,
+                          const int64_t* target, int b, int c, int64_t hw, int64_t ignore_index, const float* weight,
+                          float alpha, float gamma, int pre_softmax, void* workspace, size_t workspace_bytes,
+                          double* per_image, float* loss2, float* loss_map, void* stream);
+int vqseg_focal_backward_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px,
+                           const int64_t* target, int b, int c, int64_t hw, int64_t ignore_index, const float* weight,
+                           float alpha, float gamma, int pre_softmax, const float* g_scalar, float scale,
+                           const float* g_map, float* g_logits, void* stream);
+
+/* Class-weighted cross-entropy sums of F.cross_entropy(logits, target, weight=w, ignore_index) with w in DEVICE memory:
+ *   ce[b][0] = sum over kept pixels of w[t] * (-log softmax(logits)[t]),  ce[b][1] = sum over kept pixels of w[t];
+ * the weighted mean is sum_b ce[b][0] / sum_b ce[b][1] on the caller's side.  backward: g_logits = g_ce[b][0] * w[t] *
+ * (softmax - onehot) on kept pixels, 0 elsewhere (g_ce [b][2], [b][0] used).  Layout as for the Dice sums. */
+int vqseg_wce_sums_forward_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px,
+                             const int64_t* target, int b, int c, int64_t hw, int64_t ignore_index, const float* weight,
+                             void* workspace, size_t workspace_bytes, float* ce, void* stream);
+int vqseg_wce_sums_backward_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px,
+                              const int64_t* target, int b, int c, int64_t hw, int64_t ignore_index, const float* weight,
+                              const float* g_ce, float* g_logits, void* stream);
+
+/* compute_class_weight of loss/__init__.py:28-33 without torch.bincount's host round trip: counts[c] = number of labels
+ * equal to c for c < num_classes, counts[num_classes] = number of labels >= 0 (bincount's total: a label >= num_classes grows
+ * its vector, so it counts in the sum, but has no entry here; negative labels, which bincount refuses, are skipped), and
+ *   weight[c] = 1 - (float)counts[c] / (float)counts[num_classes]                                      (float32, as torch divides)
+ * counts [num_classes + 1] i64 and weight [num_classes] f32, both overwritten; 1..256 classes. */
+int vqseg_class_weight_f(const int64_t* labels, int64_t n, int num_classes, int64_t* counts, float* weight, void* stream);
+
 /* Exact order statistics of n floats by radix select: out2[0] = the k-th smallest (0-based), out2[1] = the (k+1)-th
  * (clamped to the last).  The two values bracket the virtual index of np.percentile in make_regularized_pseudo_label
  * (deprecated/train_with_test_pt_pseudo_entropy_reg.py:35); the host interpolates.  Replaces the full device sort of

@@ -95,6 +95,16 @@ SYMBOLS = {
                                              c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqseg_dice_ce_sums_backward_f": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vqseg_focal_workspace_bytes": (c_size_t, [c_int, c_int64]),
+    "vqseg_focal_forward_f": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_float, c_float,
+                                      c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vqseg_focal_backward_f": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_float, c_float,
+                                       c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "vqseg_wce_sums_forward_f": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                                         c_size_t, c_void_p, c_void_p]),
+    "vqseg_wce_sums_backward_f": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
+    "vqseg_class_weight_f": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "vqseg_softmax_stats_f": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqseg_confusion_counts_f": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
     "vqseg_order_stats_workspace_bytes": (c_size_t, []),

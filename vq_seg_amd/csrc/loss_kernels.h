@@ -47,6 +47,26 @@ hipError_t launch_dice_forward(const DiceArgs& a, double* partial, float* inter,
 hipError_t launch_dice_backward(const DiceArgs& a, const float* g_inter, const float* g_sets, const float* g_ce, float* g_logits,
                                 hipStream_t st);
 
+// ---- focal loss (loss/focal_loss.py:6-68), class-weighted cross-entropy sums, class weights (loss/__init__.py:28-33).  Same pixel
+// walk and block / image folds as the Dice sums (dice_blocks(HW) partials per image, fixed order).
+struct FocalArgs {
+    DiceArgs d;
+    const float* w;              // [C] class weights on the device (nullable = 1)
+    float alpha, gamma;
+    int pre_softmax;             // the module form FocalLoss.forward: z = keep ? softmax(logits) : 0 before the loss's own softmax
+};
+// per_image[b] = sum_px l (double), loss2 = (sum over images, that / (B HW)) as float; map (nullable): l per pixel [B][HW]
+hipError_t launch_focal_forward(const FocalArgs& a, double* partial, double* per_image, float* loss2, float* map, hipStream_t st);
+// d (sum_px g l) / d logits with g = g_scalar[0] * scale (reduced forms) or g_map[b][px] (reduction 'none'); exactly one of the two
+hipError_t launch_focal_backward(const FocalArgs& a, const float* g_scalar, float scale, const float* g_map, float* g_logits,
+                                 hipStream_t st);
+// ce[b] = (sum_kept w[t] nll, sum_kept w[t]);  backward: g_ce[b][0] * w[t] * (softmax - onehot) on kept pixels, 0 elsewhere
+hipError_t launch_wce_forward(const DiceArgs& a, const float* w, double* partial, float* ce, hipStream_t st);
+hipError_t launch_wce_backward(const DiceArgs& a, const float* w, const float* g_ce, float* g_logits, hipStream_t st);
+// counts[c] (c < num_classes) and counts[num_classes] = number of labels >= 0 (zeroed here first); weight[c] = 1 - counts[c] / total
+constexpr int CLASS_WEIGHT_MAX_CLASSES = 256;
+hipError_t launch_class_weight(const long long* labels, long n, int num_classes, long long* counts, float* weight, hipStream_t st);
+
 // ---- the CPS step's loss combination in one launch (r4): term_i = ce_weight * CE_i + (1 - mean_c mean_b 2 inter / (sets + eps)), i over
 // n_sup supervised terms then n_cps CPS terms; total = ((sum of sup terms + cps_weight * sum of cps terms) + commitment) + prototype with
 // commitment = sum_l (sum_k commit[k][l]) * commit_weight, prototype = (sum_k proto[k]) * proto_weight; and d total / d every input.

@@ -700,6 +700,300 @@ hipError_t launch_dice_backward(const DiceArgs& a, const float* g_inter, const f
     return hipGetLastError();
 }
 
+// =====================================================================================================
+// Focal loss (loss/focal_loss.py:6-68), class-weighted cross-entropy sums, class weights (loss/__init__.py:28-33).
+// The Dice pass's walk: one thread per pixel with stride 256 inside a span of DICE_PX_PER_BLOCK pixels, block sums in
+// double, per-image folds in fixed order.  HBM-bound: one read of logits + targets (+ one write of the gradient).
+// Reference quirks kept by the focal pass:
+//   * ignored pixels are not skipped (:12-14): logits * mask and target * mask make them zero-logit class-0 pixels, which
+//     contribute alpha * w[0] * (1 - 1/C)^gamma * log C;
+//   * 'mean' is torch.mean over every pixel (:43), B * HW, the ignored ones included;
+//   * with weights the division by sum(weight) on :42 is dead code (:43 overwrites `loss`): nothing normalises by the weights;
+//   * the module FocalLoss.forward (:62-68) softmaxes and then calls focal_loss, which masks and softmaxes AGAIN (`pre_softmax`).
+// Not the reference's: -log p_t is taken in log-softmax form (finite where a probability underflows to 0; the reference's
+// (-log p) * onehot is inf * 0 there), and 1 - p_t as the sum of the other classes' shares (no cancellation near p_t = 1).
+// A target outside [0, C) that is not the ignore index has no one-hot row (the reference's torch.eye(C)[target] raises):
+// such a pixel contributes nothing and gets no gradient.
+// =====================================================================================================
+namespace {
+// sum over the workgroup's 256 threads in a fixed tree; every thread gets the result
+__device__ __forceinline__ double block_sum(double* red, double v) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
+        __syncthreads();
+    }
+    const double s = red[0];
+    __syncthreads();
+    return s;
+}
+
+// gamma as a small integer (0..4: multiplications), else -1 (powf)
+__device__ __forceinline__ int focal_gamma_int(float gamma) {
+    return (gamma >= 0.0f && gamma <= 4.0f && gamma == floorf(gamma)) ? (int)gamma : -1;
+}
+__device__ __forceinline__ float focal_pow(float x, float gamma, int gi) {
+    switch (gi) {
+        case 0: return 1.0f;                                    // torch.pow(0, 0) = 1
+        case 1: return x;
+        case 2: return x * x;
+        case 3: return x * x * x;
+        case 4: { const float s = x * x; return s * s; }
+    }
+    return powf(x, gamma);
+}
+
+struct FocalPx {
+    float p[DMAXC];              // softmax(z): what the loss is taken of
+    float q[DMAXC];              // pre_softmax: softmax(logits) = z of a kept pixel
+    float om, pt, nlp, k;        // 1 - p_t, p_t, -log p_t, alpha * w[t] (0: no one-hot row)
+    int tgt;
+    bool keep;
+};
+
+__device__ __forceinline__ void focal_pixel(const FocalArgs& a, int b, long px, FocalPx& r) {
+    const DiceArgs& d = a.d;
+    const long long t = d.target[(long)b * d.HW + px];
+    r.keep = t != d.ignore_index;
+    const long long tl = r.keep ? t : 0;                        // target * mask (:14)
+    const bool valid = tl >= 0 && tl < d.C;
+    r.tgt = valid ? (int)tl : 0;
+    float z[DMAXC];
+#pragma unroll
+    for (int c = 0; c < DMAXC; ++c)
+        if (c < d.C) z[c] = r.keep ? d.logits[(long)b * d.sb + c * d.sc + px * d.sp] : 0.0f;     // pred * mask (:13)
+    if (a.pre_softmax) {                                        // FocalLoss.forward:66, then the mask of :13 on the probabilities
+        float mx = -__builtin_inff(), sum = 0.0f;
+#pragma unroll
+        for (int c = 0; c < DMAXC; ++c)
+            if (c < d.C) mx = fmaxf(mx, z[c]);
+#pragma unroll
+        for (int c = 0; c < DMAXC; ++c)
+            if (c < d.C) {
+                r.q[c] = expf(z[c] - mx);
+                sum += r.q[c];
+            }
+        const float inv = 1.0f / sum;
+#pragma unroll
+        for (int c = 0; c < DMAXC; ++c)
+            if (c < d.C) {
+                r.q[c] *= inv;
+                z[c] = r.keep ? r.q[c] : 0.0f;
+            }
+    }
+    float mx = -__builtin_inff();
+#pragma unroll
+    for (int c = 0; c < DMAXC; ++c)
+        if (c < d.C) mx = fmaxf(mx, z[c]);
+    float sum = 0.0f, rest = 0.0f, et = 0.0f, zt = 0.0f;
+#pragma unroll
+    for (int c = 0; c < DMAXC; ++c)
+        if (c < d.C) {
+            r.p[c] = expf(z[c] - mx);
+            sum += r.p[c];
+            if (c == r.tgt) {
+                et = r.p[c];
+                zt = z[c];
+            } else {
+                rest += r.p[c];
+            }
+        }
+    const float inv = 1.0f / sum;
+#pragma unroll
+    for (int c = 0; c < DMAXC; ++c)
+        if (c < d.C) r.p[c] *= inv;
+    r.om = rest * inv;
+    r.pt = et * inv;
+    r.nlp = logf(sum) + mx - zt;
+    r.k = valid ? a.alpha * (a.w ? a.w[r.tgt] : 1.0f) : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void focal_fwd_kernel(const FocalArgs a, double* __restrict__ partial, float* __restrict__ map) {
+    __shared__ double red[256];
+    const int b = blockIdx.y, gi = focal_gamma_int(a.gamma);
+    const long p0 = (long)blockIdx.x * DICE_PX_PER_BLOCK;
+    double acc = 0.0;
+    for (long px = p0 + threadIdx.x; px < p0 + DICE_PX_PER_BLOCK && px < a.d.HW; px += 256) {
+        FocalPx r;
+        focal_pixel(a, b, px, r);
+        const float l = r.k * focal_pow(r.om, a.gamma, gi) * r.nlp;
+        if (map) map[(long)b * a.d.HW + px] = l;
+        acc += (double)l;
+    }
+    const double s = block_sum(red, acc);
+    if (threadIdx.x == 0) partial[(long)b * gridDim.x + blockIdx.x] = s;
+}
+
+// one workgroup: image by image the block partials in block order, then the images in image order
+__global__ __launch_bounds__(256) void focal_final_kernel(const double* __restrict__ partial, long n_blocks, int B, long HW,
+                                                          double* __restrict__ per_image, float* __restrict__ loss2) {
+    for (int b = threadIdx.x; b < B; b += 256) {
+        double s = 0.0;
+        for (long i = 0; i < n_blocks; ++i) s += partial[(long)b * n_blocks + i];
+        per_image[b] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int b = 0; b < B; ++b) s += per_image[b];
+        loss2[0] = (float)s;                                    // 'sum' (:46)
+        loss2[1] = (float)(s / ((double)B * (double)HW));       // 'mean' (:43)
+    }
+}
+
+// d l / d z_c = k * A * (p_c - 1[c == t]),  A = gamma * om^(gamma-1) * p_t * nlp + om^gamma   (d om / d z_c = p_t (p_c - 1[c == t]))
+__global__ __launch_bounds__(256) void focal_bwd_kernel(const FocalArgs a, const float* __restrict__ g_scalar, float scale,
+                                                        const float* __restrict__ g_map, float* __restrict__ g_logits) {
+    const int b = blockIdx.y, gi = focal_gamma_int(a.gamma);
+    const DiceArgs& d = a.d;
+    const long p0 = (long)blockIdx.x * DICE_PX_PER_BLOCK;
+    const float g0 = g_scalar ? g_scalar[0] * scale : 0.0f;
+    for (long px = p0 + threadIdx.x; px < p0 + DICE_PX_PER_BLOCK && px < d.HW; px += 256) {
+        FocalPx r;
+        focal_pixel(a, b, px, r);
+        const float g = g_map ? g_map[(long)b * d.HW + px] : g0;
+        float A = 1.0f;                                         // gamma == 0: the weighted cross-entropy
+        if (gi != 0) A = a.gamma * focal_pow(r.om, a.gamma - 1.0f, gi > 0 ? gi - 1 : -1) * r.pt * r.nlp + focal_pow(r.om, a.gamma, gi);
+        const float ka = g * r.k * A;
+        float u[DMAXC], dot = 0.0f;
+#pragma unroll
+        for (int c = 0; c < DMAXC; ++c)
+            if (c < d.C) {
+                u[c] = ka * (c == r.tgt ? -r.om : r.p[c]);
+                if (a.pre_softmax) dot = __builtin_fmaf(u[c], r.q[c], dot);
+            }
+#pragma unroll
+        for (int c = 0; c < DMAXC; ++c)
+            if (c < d.C) {
+                const float v = a.pre_softmax ? r.q[c] * (u[c] - dot) : u[c];        // back through the first softmax
+                g_logits[(long)b * d.sb + c * d.sc + px * d.sp] = r.keep ? v : 0.0f;     // ignored: the logits were multiplied by 0
+            }
+    }
+}
+
+__global__ __launch_bounds__(256) void wce_fwd_kernel(const DiceArgs a, const float* __restrict__ w, double* __restrict__ partial) {
+    __shared__ double red[256];
+    const int b = blockIdx.y;
+    const long p0 = (long)blockIdx.x * DICE_PX_PER_BLOCK;
+    double s0 = 0.0, s1 = 0.0;
+    for (long px = p0 + threadIdx.x; px < p0 + DICE_PX_PER_BLOCK && px < a.HW; px += 256) {
+        float p[DMAXC], nll;
+        int tgt;
+        bool keep;
+        dice_pixel(a, b, px, p, tgt, keep, nll);
+        const float wt = (keep && tgt >= 0 && tgt < a.C) ? w[tgt] : 0.0f;
+        s0 += (double)(wt * nll);
+        s1 += (double)wt;
+    }
+    double* out = partial + ((long)b * gridDim.x + blockIdx.x) * 2;
+    s0 = block_sum(red, s0);
+    s1 = block_sum(red, s1);
+    if (threadIdx.x == 0) out[0] = s0, out[1] = s1;
+}
+
+__global__ __launch_bounds__(64) void wce_final_kernel(const double* __restrict__ partial, long n_blocks, float* __restrict__ ce) {
+    const int b = blockIdx.x, q = threadIdx.x;
+    if (q >= 2) return;
+    double s = 0.0;
+    for (long i = 0; i < n_blocks; ++i) s += partial[((long)b * n_blocks + i) * 2 + q];
+    ce[b * 2 + q] = (float)s;
+}
+
+__global__ __launch_bounds__(256) void wce_bwd_kernel(const DiceArgs a, const float* __restrict__ w, const float* __restrict__ g_ce,
+                                                      float* __restrict__ g_logits) {
+    const int b = blockIdx.y;
+    const long p0 = (long)blockIdx.x * DICE_PX_PER_BLOCK;
+    const float g = g_ce[b * 2];
+    for (long px = p0 + threadIdx.x; px < p0 + DICE_PX_PER_BLOCK && px < a.HW; px += 256) {
+        float p[DMAXC], nll;
+        int tgt;
+        bool keep;
+        dice_pixel(a, b, px, p, tgt, keep, nll);
+        const float gw = (keep && tgt >= 0 && tgt < a.C) ? g * w[tgt] : 0.0f;
+#pragma unroll
+        for (int c = 0; c < DMAXC; ++c)
+            if (c < a.C) g_logits[(long)b * a.sb + c * a.sc + px * a.sp] = gw * (p[c] - (c == tgt ? 1.0f : 0.0f));
+    }
+}
+
+// Label histogram of compute_class_weight (loss/__init__.py:30: torch.bincount, which synchronises with the host to size its
+// output).  Classes 0..3 are counted in registers, the rest in the workgroup's LDS histogram; integer counts, then one integer
+// atomic per non-empty bin and workgroup: order-independent.  counts[num_classes] = labels >= 0 (bincount's total: labels
+// >= num_classes grow its vector and so count in the sum, but have no entry here).
+constexpr int CW_PER_THREAD = 8;
+__global__ __launch_bounds__(256) void class_count_kernel(const long long* __restrict__ labels, long n, int num_classes,
+                                                          unsigned long long* __restrict__ counts) {
+    __shared__ unsigned cnt[CLASS_WEIGHT_MAX_CLASSES + 1];
+    for (int i = threadIdx.x; i <= num_classes; i += 256) cnt[i] = 0;
+    __syncthreads();
+    unsigned c0 = 0, c1 = 0, c2 = 0, c3 = 0, tot = 0;
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const long long t = labels[i];
+        tot += t >= 0;
+        c0 += t == 0;
+        c1 += t == 1;
+        c2 += t == 2;
+        c3 += t == 3;
+        if (t >= 4 && t < num_classes) atomicAdd(&cnt[(int)t], 1u);
+    }
+    if (c0 && 0 < num_classes) atomicAdd(&cnt[0], c0);
+    if (c1 && 1 < num_classes) atomicAdd(&cnt[1], c1);
+    if (c2 && 2 < num_classes) atomicAdd(&cnt[2], c2);
+    if (c3 && 3 < num_classes) atomicAdd(&cnt[3], c3);
+    if (tot) atomicAdd(&cnt[num_classes], tot);
+    __syncthreads();
+    for (int i = threadIdx.x; i <= num_classes; i += 256)
+        if (cnt[i]) atomicAdd(&counts[i], (unsigned long long)cnt[i]);
+}
+
+// weight = 1. - count / sum(count) in float32, as torch divides two int64 tensors (:31-32)
+__global__ __launch_bounds__(256) void class_weight_kernel(const unsigned long long* __restrict__ counts, int num_classes,
+                                                           float* __restrict__ weight) {
+    const float total = (float)counts[num_classes];
+    for (int c = threadIdx.x; c < num_classes; c += 256) weight[c] = 1.0f - (float)counts[c] / total;
+}
+}  // namespace
+
+hipError_t launch_focal_forward(const FocalArgs& a, double* partial, double* per_image, float* loss2, float* map, hipStream_t st) {
+    const long nb = dice_blocks(a.d.HW);
+    hipLaunchKernelGGL(focal_fwd_kernel, dim3((unsigned)nb, (unsigned)a.d.B), dim3(256), 0, st, a, partial, map);
+    hipLaunchKernelGGL(focal_final_kernel, dim3(1), dim3(256), 0, st, partial, nb, a.d.B, a.d.HW, per_image, loss2);
+    return hipGetLastError();
+}
+
+hipError_t launch_focal_backward(const FocalArgs& a, const float* g_scalar, float scale, const float* g_map, float* g_logits,
+                                 hipStream_t st) {
+    hipLaunchKernelGGL(focal_bwd_kernel, dim3((unsigned)dice_blocks(a.d.HW), (unsigned)a.d.B), dim3(256), 0, st, a, g_scalar, scale, g_map,
+                       g_logits);
+    return hipGetLastError();
+}
+
+hipError_t launch_wce_forward(const DiceArgs& a, const float* w, double* partial, float* ce, hipStream_t st) {
+    const long nb = dice_blocks(a.HW);
+    hipLaunchKernelGGL(wce_fwd_kernel, dim3((unsigned)nb, (unsigned)a.B), dim3(256), 0, st, a, w, partial);
+    hipLaunchKernelGGL(wce_final_kernel, dim3((unsigned)a.B), dim3(64), 0, st, partial, nb, ce);
+    return hipGetLastError();
+}
+
+hipError_t launch_wce_backward(const DiceArgs& a, const float* w, const float* g_ce, float* g_logits, hipStream_t st) {
+    hipLaunchKernelGGL(wce_bwd_kernel, dim3((unsigned)dice_blocks(a.HW), (unsigned)a.B), dim3(256), 0, st, a, w, g_ce, g_logits);
+    return hipGetLastError();
+}
+
+hipError_t launch_class_weight(const long long* labels, long n, int num_classes, long long* counts, float* weight, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)(num_classes + 1) * sizeof(long long), st);
+    if (e != hipSuccess) return e;
+    long blocks = (n + 256 * CW_PER_THREAD - 1) / (256 * CW_PER_THREAD);
+    blocks = blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks;
+    hipLaunchKernelGGL(class_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, labels, n, num_classes,
+                       reinterpret_cast<unsigned long long*>(counts));
+    hipLaunchKernelGGL(class_weight_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const unsigned long long*>(counts), num_classes,
+                       weight);
+    return hipGetLastError();
+}
+
 namespace {
 // one workgroup: the inputs are a few hundred numbers; what this replaces is ~45 scalar autograd nodes forward and ~70 tiny kernels
 // backward, issued one by one with the chip idle (0.3 + 0.6 ms per step, tools/micro/scalar_graph.py)

@@ -516,6 +516,71 @@ int vqseg_dice_sums_backward_f(const float* logits, int64_t stride_b, int64_t st
                                          g_logits, stream);
 }
 
+static int focal_args(vqseg::FocalArgs& a, const float* logits, int64_t sb, int64_t sc, int64_t sp, const int64_t* target, int b, int c,
+                      int64_t hw, int64_t ignore_index, const float* weight, float alpha, float gamma, int pre_softmax) {
+    if (int rc = dice_args(a.d, logits, sb, sc, sp, target, b, c, hw, ignore_index)) return rc;
+    if (!(gamma == 0.0f || gamma >= 1.0f) || !isfinite(gamma) || !isfinite(alpha))
+        return bad("focal: gamma must be 0 or >= 1 (0 < gamma < 1 has an unbounded derivative at p = 1)");
+    a.w = weight; a.alpha = alpha; a.gamma = gamma; a.pre_softmax = pre_softmax ? 1 : 0;
+    return 0;
+}
+
+size_t vqseg_focal_workspace_bytes(int b, int64_t hw) {
+    if (b <= 0 || hw <= 0) return 0;
+    return (size_t)b * vqseg::dice_blocks(hw) * 2 * sizeof(double);       // block partials (two per block: the weighted CE sums)
+}
+
+int vqseg_focal_forward_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px, const int64_t* target, int b, int c,
+                          int64_t hw, int64_t ignore_index, const float* weight, float alpha, float gamma, int pre_softmax,
+                          void* workspace, size_t workspace_bytes, double* per_image, float* loss2, float* loss_map, void* stream) {
+    vqseg::FocalArgs a;
+    if (int rc = focal_args(a, logits, stride_b, stride_c, stride_px, target, b, c, hw, ignore_index, weight, alpha, gamma, pre_softmax))
+        return rc;
+    if (!workspace || !per_image || !loss2) return bad("focal: null pointer");
+    if (workspace_bytes < vqseg_focal_workspace_bytes(b, hw)) return vqseg_set_error(VQSEG_ENOSPC, "focal: workspace too small");
+    hipError_t e = vqseg::launch_focal_forward(a, static_cast<double*>(workspace), per_image, loss2, loss_map, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hipfail(e, "focal_fwd_kernel");
+}
+
+int vqseg_focal_backward_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px, const int64_t* target, int b, int c,
+                           int64_t hw, int64_t ignore_index, const float* weight, float alpha, float gamma, int pre_softmax,
+                           const float* g_scalar, float scale, const float* g_map, float* g_logits, void* stream) {
+    vqseg::FocalArgs a;
+    if (int rc = focal_args(a, logits, stride_b, stride_c, stride_px, target, b, c, hw, ignore_index, weight, alpha, gamma, pre_softmax))
+        return rc;
+    if (!g_logits || (g_scalar == nullptr) == (g_map == nullptr)) return bad("focal: exactly one of the scalar and the per-pixel cotangent");
+    hipError_t e = vqseg::launch_focal_backward(a, g_scalar, scale, g_map, g_logits, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hipfail(e, "focal_bwd_kernel");
+}
+
+int vqseg_wce_sums_forward_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px, const int64_t* target, int b, int c,
+                             int64_t hw, int64_t ignore_index, const float* weight, void* workspace, size_t workspace_bytes, float* ce,
+                             void* stream) {
+    vqseg::DiceArgs a;
+    if (int rc = dice_args(a, logits, stride_b, stride_c, stride_px, target, b, c, hw, ignore_index)) return rc;
+    if (!weight || !workspace || !ce) return bad("wce_sums: null pointer");
+    if (workspace_bytes < vqseg_focal_workspace_bytes(b, hw)) return vqseg_set_error(VQSEG_ENOSPC, "wce_sums: workspace too small");
+    hipError_t e = vqseg::launch_wce_forward(a, weight, static_cast<double*>(workspace), ce, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hipfail(e, "wce_fwd_kernel");
+}
+
+int vqseg_wce_sums_backward_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px, const int64_t* target, int b, int c,
+                              int64_t hw, int64_t ignore_index, const float* weight, const float* g_ce, float* g_logits, void* stream) {
+    vqseg::DiceArgs a;
+    if (int rc = dice_args(a, logits, stride_b, stride_c, stride_px, target, b, c, hw, ignore_index)) return rc;
+    if (!weight || !g_ce || !g_logits) return bad("wce_sums: null pointer");
+    hipError_t e = vqseg::launch_wce_backward(a, weight, g_ce, g_logits, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hipfail(e, "wce_bwd_kernel");
+}
+
+int vqseg_class_weight_f(const int64_t* labels, int64_t n, int num_classes, int64_t* counts, float* weight, void* stream) {
+    if (!labels || !counts || !weight || n <= 0) return bad("class_weight: null pointer or no labels");
+    if (num_classes < 1 || num_classes > vqseg::CLASS_WEIGHT_MAX_CLASSES) return bad("class_weight: 1..256 classes");
+    hipError_t e = vqseg::launch_class_weight(reinterpret_cast<const long long*>(labels), n, num_classes, reinterpret_cast<long long*>(counts),
+                                              weight, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hipfail(e, "class_count_kernel");
+}
+
 int vqseg_softmax_stats_f(const float* logits, int64_t stride_b, int64_t stride_c, int64_t stride_px, int b, int c, int64_t hw,
                           int64_t* label, float* entropy, float* top, void* stream) {
     if (!logits || b <= 0 || hw <= 0 || c < 2 || c > 4) return bad("softmax_stats: bad argument (2..4 classes)");

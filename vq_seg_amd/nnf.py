@@ -1432,6 +1432,133 @@ def dice_ce_sums(pred, target, ignore_index):
     return _DiceSums.apply(pred, target, ignore_index, True)
 
 
+def _loss_inputs(pred, target, ignore_index):
+    """what every pass over (B, C, H, W) logits + targets takes: the logits with linear pixels, the (B, HW) int64 targets, the
+    (batch, class, pixel) strides and the ignore index as an integer (None: a value no label has)"""
+    b, c, h, w = pred.shape
+    sb, sc, sh, sw = pred.stride()
+    if sh != w * sw:                                       # pixels must be linear in memory (NCHW and NHWC both are)
+        pred = pred.contiguous()
+        sb, sc, sh, sw = pred.stride()
+    tgt = target.reshape(b, h * w).long().contiguous()
+    ign = -(1 << 62) if ignore_index is None else int(ignore_index)
+    return pred, tgt, (sb, sc, sw), ign
+
+
+def _class_weights(weight, c, dev):
+    """the C class weights as the kernels read them: float32 on the logits' device (a device tensor stays where it is)"""
+    if weight is None:
+        return None
+    w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if w.numel() != c:
+        raise _hip.HipLibraryError(f"class weights: the sizes passed along need {c} elements, the tensor has {w.numel()} (shape {tuple(w.shape)})")
+    return w
+
+
+# ------------------------------------------------------------------------------------------------
+# Focal loss (loss/focal_loss.py): one pass forward, one backward (vqseg_focal_*)
+# ------------------------------------------------------------------------------------------------
+class _Focal(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, weight, alpha, gamma, ignore_index, reduction, pre_softmax):
+        if reduction not in ("none", "mean", "sum"):
+            raise NotImplementedError(f"Invalid reduction mode: {reduction}")
+        b, c, h, w = pred.shape
+        hw = h * w
+        pred, tgt, (sb, sc, sw), ign = _loss_inputs(pred, target, ignore_index)
+        dev = pred.device
+        wt = _class_weights(weight, c, dev)
+        L = lib()
+        nbytes = L.vqseg_focal_workspace_bytes(b, hw)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        per_image = torch.empty(b, dtype=torch.float64, device=dev)
+        loss2 = torch.empty(2, dtype=torch.float32, device=dev)
+        lmap = torch.empty(b, hw, dtype=torch.float32, device=dev) if reduction == "none" else None
+        _launch("vqseg_focal_forward_f", dev, _strided_f32(pred, "logits", b * c * hw), sb, sc, sw, _T(tgt, "targets", dtype=torch.int64, numel=b * hw),
+                b, c, hw, ign, _f32(wt, "class weights", c), float(alpha), float(gamma), int(bool(pre_softmax)),
+                _T(ws, "workspace", dtype=torch.uint8, numel=nbytes), nbytes, _T(per_image, "per-image sums", dtype=torch.float64, numel=b),
+                _f32(loss2, "loss", 2), _f32(lmap, "loss map", b * hw))
+        ctx.save_for_backward(pred, tgt, wt)
+        ctx.cfg = (b, c, hw, ign, (sb, sc, sw), float(alpha), float(gamma), int(bool(pre_softmax)), reduction)
+        if reduction == "none":
+            return lmap                                        # (B, HW), as the reference returns it
+        return loss2[0] if reduction == "sum" else loss2[1]
+
+    @staticmethod
+    def backward(ctx, g_out):
+        pred, tgt, wt = ctx.saved_tensors
+        b, c, hw, ign, (sb, sc, sw), alpha, gamma, pre, reduction = ctx.cfg
+        g = torch.empty_strided(pred.shape, pred.stride(), dtype=torch.float32, device=pred.device)
+        if reduction == "none":
+            g_scalar, scale, g_map = None, 0.0, g_out.float().contiguous()
+        else:
+            g_scalar, scale, g_map = g_out.float().reshape(1).contiguous(), (1.0 if reduction == "sum" else 1.0 / (b * hw)), None
+        _launch("vqseg_focal_backward_f", pred.device, _strided_f32(pred, "logits", b * c * hw), sb, sc, sw,
+                _T(tgt, "targets", dtype=torch.int64, numel=b * hw), b, c, hw, ign, _f32(wt, "class weights", c), alpha, gamma, pre,
+                _f32(g_scalar, "loss gradient", 1), scale, _f32(g_map, "loss map gradient", b * hw), _strided_f32(g, "logit gradient", b * c * hw))
+        return g, None, None, None, None, None, None, None
+
+
+def focal(pred, target, alpha, gamma, ignore_index, reduction="sum", weight=None, pre_softmax=False):
+    """focal_loss (loss/focal_loss.py:6-50; `pre_softmax`: the module FocalLoss.forward, :62-68) of (B, C, H, W) float32 logits that pass
+    dice_sums_supported, gamma == 0 or >= 1: a 0-d float32 tensor ('sum', 'mean') or the (B, HW) map ('none')."""
+    return _Focal.apply(pred, target, weight, alpha, gamma, ignore_index, reduction, pre_softmax)
+
+
+class _WceSums(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, weight, ignore_index):
+        b, c, h, w = pred.shape
+        hw = h * w
+        pred, tgt, (sb, sc, sw), ign = _loss_inputs(pred, target, ignore_index)
+        dev = pred.device
+        wt = _class_weights(weight, c, dev)
+        L = lib()
+        nbytes = L.vqseg_focal_workspace_bytes(b, hw)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ce = torch.empty(b, 2, dtype=torch.float32, device=dev)
+        _launch("vqseg_wce_sums_forward_f", dev, _strided_f32(pred, "logits", b * c * hw), sb, sc, sw, _T(tgt, "targets", dtype=torch.int64, numel=b * hw),
+                b, c, hw, ign, _f32(wt, "class weights", c), _T(ws, "workspace", dtype=torch.uint8, numel=nbytes), nbytes,
+                _f32(ce, "cross-entropy sums", b * 2))
+        ctx.save_for_backward(pred, tgt, wt)
+        ctx.cfg = (b, c, hw, ign, (sb, sc, sw))
+        return ce
+
+    @staticmethod
+    def backward(ctx, g_ce):
+        pred, tgt, wt = ctx.saved_tensors
+        b, c, hw, ign, (sb, sc, sw) = ctx.cfg
+        g = torch.empty_strided(pred.shape, pred.stride(), dtype=torch.float32, device=pred.device)
+        gc = g_ce.float().contiguous()
+        _launch("vqseg_wce_sums_backward_f", pred.device, _strided_f32(pred, "logits", b * c * hw), sb, sc, sw,
+                _T(tgt, "targets", dtype=torch.int64, numel=b * hw), b, c, hw, ign, _f32(wt, "class weights", c),
+                _f32(gc, "d cross-entropy sums", b * 2), _strided_f32(g, "logit gradient", b * c * hw))
+        return g, None, None, None
+
+
+def wce_sums(pred, target, weight, ignore_index):
+    """ce (B, 2) = (sum of w[t] * -log softmax[t], sum of w[t]) over the pixels whose target != ignore_index:
+    F.cross_entropy(pred, target, weight=w, ignore_index)'s mean is ce[:, 0].sum() / ce[:, 1].sum() (vqseg_wce_sums_*)."""
+    if weight is None:
+        raise _hip.HipLibraryError("class weights: expected a tensor, got None")
+    return _WceSums.apply(pred, target, weight, ignore_index)
+
+
+def class_weight(num_classes: int, y):
+    """(weight (num_classes,) f32, counts (num_classes + 1,) i64) of the labels `y` on their device, no host synchronisation
+    (vqseg_class_weight_f): counts[c] for c < num_classes, counts[-1] = the labels >= 0, weight = 1 - counts[:-1] / counts[-1]."""
+    nc = int(num_classes)
+    labels = y.reshape(-1)
+    if labels.dtype != torch.int64 or not labels.is_contiguous():
+        labels = labels.long().contiguous()
+    n = labels.numel()
+    counts = torch.empty(nc + 1, dtype=torch.int64, device=labels.device)
+    weight = torch.empty(nc, dtype=torch.float32, device=labels.device)
+    _launch("vqseg_class_weight_f", labels.device, _T(labels, "labels", dtype=torch.int64, numel=n), n, nc,
+            _T(counts, "class counts", dtype=torch.int64, numel=nc + 1), _f32(weight, "class weights", nc))
+    return weight, counts
+
+
 class _ConvBias(torch.autograd.Function):
     """k x k / stride 1 convolution WITH bias and a handful of output channels, fp32 (the plain Unet's segmentation head: 32 -> 3,
     segmentation_head.py:78-83) on the precise-mode kernels: output channels zero-padded to the kernels' 4-channel granule, the bias in

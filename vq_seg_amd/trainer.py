@@ -11,7 +11,7 @@ wandb / image dumps of the reference trainer are out of scope.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence, Union
 
 import contextlib
 import torch
@@ -21,8 +21,9 @@ from torch import nn
 
 from . import dist as vdist
 from .data import augmentations
-from .loss import make_loss
-from .loss.dice_loss import DiceLoss, ce_dice_loss
+from .loss import compute_class_weight, cross_entropy, make_loss
+from .loss.dice_loss import DiceLoss, ce_dice_loss, dice_loss
+from .loss.focal_loss import FocalLoss
 from .measurement import confusion_matrix_device, miou_device
 from . import nnf
 from .models import init_weight
@@ -213,7 +214,24 @@ class CPSConfig:
                                               # unlabelled TRAINING forwards see box-mixed images, the pseudo targets are mixed with the same boxes
                                               # (area ratio of the box); None = the plain step, the mixing code is not entered
     cutmix_boxes: str = "batch"               # "batch": one box per step for all samples (CutMix.__call__); "sample": one per sample (augmentation())
+    focal_alpha: float = 0.25                 # criterion "focal_loss": FocalLoss(num_classes, alpha, gamma, ignore_index=255), the module form
+    focal_gamma: float = 2.0                  # (deprecated/train_vq_pt_unet_withtest.py:81,281-282)
+    class_weight: Optional[Union[str, Sequence[float]]] = None
+                                              # recipe v1 only.  "balanced": compute_class_weight(num_classes, l_target) once per step, handed to both
+                                              # supervised and both CPS terms (deprecated/train_vq_pt_unet_balncedweightedloss.py:135-141); made and kept on
+                                              # the device, per rank under data parallelism; nothing of it is checkpointed.  A sequence: fixed weights
+                                              # (train_vq_pt_unet_withtest.py:283).  None = today's step
     extra: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        if self.recipe != "v1" and (self.criterion != "dice_loss" or self.class_weight is not None):
+            raise ValueError("criterion / class_weight apply to recipe 'v1', the single-criterion recipe; the reference has no weighted or "
+                             "focal form of recipe 'v2' (CE + Dice)")
+        if isinstance(self.class_weight, str):
+            if self.class_weight != "balanced":
+                raise ValueError(f"class_weight must be None, 'balanced' or {self.num_classes} numbers, got {self.class_weight!r}")
+        elif self.class_weight is not None and len(self.class_weight) != self.num_classes:
+            raise ValueError(f"class_weight: one weight per class required ({self.num_classes}), got {len(self.class_weight)}")
 
 
 def broadcast_module_state(m: nn.Module, src: int = 0) -> None:
@@ -307,7 +325,13 @@ class CPSTrainer:
                      for m in self.models]
         self.sched = CosineAnnealingLR(cfg.learning_rate, cfg.min_lr, cfg.total_iters, cfg.warmup_steps)
         self.ce = nn.CrossEntropyLoss(ignore_index=255)
-        self.criterion = make_loss(cfg.criterion, cfg.num_classes, ignore_index=255)
+        fixed = None
+        if cfg.class_weight is not None and not isinstance(cfg.class_weight, str):
+            fixed = torch.tensor([float(v) for v in cfg.class_weight], dtype=torch.float32, device=device)
+        self._fixed_weight = fixed
+        self.criterion = make_loss(cfg.criterion, cfg.num_classes, ignore_index=255, weight=fixed)
+        if isinstance(self.criterion, FocalLoss):
+            self.criterion.alpha, self.criterion.gamma = cfg.focal_alpha, cfg.focal_gamma
         self.iter = 0
 
     # -- one model forward under the configured precision
@@ -503,6 +527,18 @@ class CPSTrainer:
         if not split:
             self._join()
         crit = self.criterion if cfg.recipe == "v1" else self._ce_dice
+        cls_weight = self._fixed_weight
+        if cfg.class_weight == "balanced":
+            # this step's labelled targets weigh all four terms, as train_vq_pt_unet_balncedweightedloss.py:135-141 does; the counting
+            # kernel leaves the weights on the device (no bincount, no host round trip).  One tensor for both networks' streams.
+            cls_weight = compute_class_weight(cfg.num_classes, l_target)
+            if split:
+                for s_ in streams:
+                    s_.wait_stream(main)
+                    cls_weight.record_stream(s_)
+        if cls_weight is not None or not isinstance(self.criterion, DiceLoss):
+            def crit(pred, target):                                     # noqa: F811  (cfg.__post_init__: recipe v1 only)
+                return self._weighted(pred, target, cls_weight)
 
         def own_mask(ps, pu):
             ps, pu = ps.float(), pu.float()
@@ -519,7 +555,7 @@ class CPSTrainer:
         # r4: with the Dice criterion (no class weights) the four terms stay as their (inter, sets[, ce]) sums and the whole combination
         # -- terms, commitment, prototype, total, and its gradient -- is one launch (nnf.cps_loss_combine); else scalar torch ops
         crt = self.criterion
-        fuse = (isinstance(crt, DiceLoss) and crt.weight is None and crt.ignore_index is not None and pred_1.is_cuda
+        fuse = (isinstance(crt, DiceLoss) and crt.weight is None and cls_weight is None and crt.ignore_index is not None and pred_1.is_cuda
                 and nnf.dice_sums_supported(pred_1, crt.num_classes) and nnf.py_opt("py_loss_combine", 1) == 1)
         if fuse:
             def crit(pred, target):                                     # noqa: F811  (the sums; combined below)
@@ -538,6 +574,10 @@ class CPSTrainer:
                     x.record_stream(main)
         if cfg.keep_aux:
             self.aux = dict(mask_1=mask_1, mask_2=mask_2, score_1=score_1, score_2=score_2, pred_sup_1=ps1.detach(), pred_ul_2=pu2.detach())
+            if cls_weight is not None or not isinstance(crt, DiceLoss):    # what the criterion arms' terms are restated from
+                self.aux.update(pred_1=pred_1.detach(), pred_2=pred_2.detach(), class_weight=cls_weight)
+                if split:
+                    pred_1.record_stream(main), pred_2.record_stream(main)
             if cfg.cutmix_ratio is not None:                            # score_1 / score_2 stay the clean maps; what the step used comes beside them
                 if split:
                     clean_1.record_stream(main), clean_2.record_stream(main)
@@ -665,6 +705,19 @@ class CPSTrainer:
                         off += n
         self.iter = int(state.get("iter", self.iter))
         return state.get("epoch", 0), state.get("batch_idx", 0)
+
+    def _weighted(self, pred, target, weight):
+        """the configured criterion with this step's class weights: the module's own parameters (ignore index 255, the focal
+        alpha / gamma and its module form), only the weights come from outside"""
+        crt = self.criterion
+        if isinstance(crt, DiceLoss):
+            return dice_loss(pred, target, crt.num_classes, weight=weight, ignore_index=crt.ignore_index)
+        if isinstance(crt, FocalLoss):
+            return FocalLoss(crt.num_classes, crt.alpha, crt.gamma, crt.ignore_index, crt.reduction, weight)(pred, target)
+        if weight is None and nnf.dice_sums_supported(pred, pred.shape[1]):
+            ce = nnf.dice_ce_sums(pred, target, crt.ignore_index)[2]     # the unweighted mean from the fused pass's CE sums
+            return ce[:, 0].sum() / ce[:, 1].sum()
+        return cross_entropy(pred, target, weight=weight, ignore_index=crt.ignore_index)
 
     def _ce_dice(self, pred, target):
         """0.5 * CE(ignore 255) + criterion (train_vqreptunet1x1v2.py:165-187); with the Dice criterion both terms come from

@@ -1,6 +1,14 @@
-"""Fused prototype-loss kernels (vqseg_proto_loss_*) against the module's own tensor-op formulation of the reference
-(models/modules/prototype.py), which the golden fixtures pin on the CPU: both variants, margins, scales, margin modes,
-fp32 and bf16 features, with and without the entropy / confidence masks; forward value and gradients."""
+"""The fused loss kernels of csrc/loss_kernels.hip through the modules that use them, against the same formulas written with fp32
+torch ops on the same GPU (the modules' own unfused paths, which the golden fixtures pin on the CPU):
+  * the prototype losses (vqseg_proto_loss_*): both variants, margins, scales, margin modes, fp32 and bf16 features, with and
+    without the entropy / confidence masks, forward value and gradients; the prototype gradient over many row tiles;
+  * the Dice and CE + Dice sums (vqseg_dice_sums_*, vqseg_dice_ce_sums_*) in three layouts, weighted and not;
+  * vqseg_softmax_stats_f; the exact radix-select percentile (vqseg_order_stats_f) and its argument checks;
+  * the confusion counts (vqseg_confusion_counts_f) against Measurement on the host;
+  * nnf.cps_loss_combine (vqseg_cps_loss_combine_f) against the scalar torch graph.
+The direct float64 parity of these kernels through the C ABI -- every class count, the span edges of the Dice fold, the LDS fold of
+the prototype gradient at every group count, batches over 256 in the combine kernel, with bars counted from the source -- is in
+tests/test_loss_kernels_gpu.py; the focal / weighted-CE / class-weight kernels are in test_focal_gpu.py and test_class_weight_gpu.py."""
 import pytest
 import torch
 

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import cases, golden_io, synth
+from tests import cases, golden_io, synth, vq_poison
 
 pytestmark = pytest.mark.gpu
 
@@ -63,7 +63,8 @@ def test_filter_equals_exact_kernel_and_chain_oracle_at_baseline_row_counts():
     print("\n".join(report))
 
 
-ADVERSARIAL = ["duplicated_codes", "midpoints", "zero_rows", "rows_are_codes", "collapsed", "nearly_collapsed", "large_magnitude", "signed", "ragged"]
+ADVERSARIAL = ["duplicated_codes", "midpoints", "zero_rows", "rows_are_codes", "collapsed", "nearly_collapsed", "large_magnitude", "signed", "ragged",
+               "nan_rows", "inf_rows", "norm_overflow"]
 
 
 @pytest.mark.parametrize("kind", ADVERSARIAL)
@@ -93,6 +94,8 @@ def test_filter_on_adversarial_inputs_equals_the_exact_kernel(kind):
     elif kind == "ragged":
         n = 2999 - 128 + 5
         rows = rows[:n]
+    elif kind in ("nan_rows", "inf_rows", "norm_overflow"):       # rows a diverged bf16 step hands over (tests/test_vq_nonfinite_gpu.py has the full set)
+        rows, W, _ = vq_poison.poison_rows(rows, W, {"nan_rows": "nan_one", "inf_rows": "pos_inf"}.get(kind, kind))
     rows = rows.bfloat16().float()                               # the layer's bf16 activations: exact bf16 values
     f, e = both_paths(rows.to(dev()).bfloat16(), W.to(dev()))
     assert f[3] == 1

@@ -52,6 +52,7 @@ struct VqLevel {
     // (*gate > gate_cap) -- degenerate codebooks; otherwise every workgroup exits at once
     const int* gate = nullptr;
     int gate_cap = 0;
+    int K = 0;                  // real codes: codes K .. Kp - 1 are padding and never win, whatever the row holds (set by the host)
 };
 // one level of the bf16 candidate filter launch (vq_filter_bf16_kernel)
 struct VqFilterLevel {

@@ -111,15 +111,20 @@ __global__ __launch_bounds__(256) void vq_pack_codebook_bf16(const float* __rest
     }
 }
 
-// max_k |e_k|^2 over the real codes (one workgroup; the padding entries of enorm are +inf)
+// the larger of two values, NaN if either is one (fmaxf would drop it)
+__device__ __forceinline__ float max_keep_nan(float a, float b) { return a != a ? a : (!(b <= a) ? b : a); }
+
+// max_k |e_k|^2 over the real codes (one workgroup; the padding entries of enorm are +inf).  A NaN or +inf |e_k|^2 (a code with a
+// non-finite entry, or one whose norm overflows) REACHES the result: the filter's band is then not finite and vq_resolve_kernel
+// hands the level to the exact kernel -- the filter has no error bound for such a code and must not rank it.
 __global__ __launch_bounds__(256) void vq_enorm_max(const float* __restrict__ enorm, int K, float* __restrict__ out) {
     __shared__ float sh[256];
     float m = 0.0f;
-    for (int k = threadIdx.x; k < K; k += 256) m = __builtin_fmaxf(m, enorm[k]);
+    for (int k = threadIdx.x; k < K; k += 256) m = max_keep_nan(m, enorm[k]);
     sh[threadIdx.x] = m;
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] = __builtin_fmaxf(sh[threadIdx.x], sh[threadIdx.x + w]);
+        if ((int)threadIdx.x < w) sh[threadIdx.x] = max_keep_nan(sh[threadIdx.x], sh[threadIdx.x + w]);
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = sh[0];
@@ -346,6 +351,12 @@ __global__ __launch_bounds__(256, 2) void vq_assign_f32_kernel(const VqGroup g) 
     float en[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) en[t] = enorm[code0 + t * 32 + r];
+    // the clamp's lower bound: 0 for a real code (a NaN distance becomes 0, like the oracle's `d > 0 ? d : 0`), +inf for a padding
+    // code K .. Kp - 1.  Padding has zero entries and |e|^2 = +inf, so its distance is +inf for a finite row -- but NaN for a row
+    // with a NaN or an Inf (inf * 0), which the clamp to 0 would turn into a winner.  max(d2, +inf) = +inf whatever d2 is.
+    float floor_t[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) floor_t[t] = code0 + t * 32 + r < g.lv[lvl].K ? 0.0f : __builtin_inff();
     TL_STAMP(2)                                                // main loop issued (the last MFMAs are still draining)
     // ---- epilogue: distances -> (min, code) per row over this workgroup's codes
     {
@@ -373,17 +384,21 @@ __global__ __launch_bounds__(256, 2) void vq_assign_f32_kernel(const VqGroup g) 
     // a tie" is the tie rule.  One wave-uniform branch per row instead of one per (row, tile); the tiles' |e|^2 come from en[] (they
     // used to be loaded tile by tile behind that branch: eight serialised L2 latencies, 19 us of a 141 us workgroup --
     // profiles/r03_vq_wg_timeline_before.md).
+    // The holder starts at the lane's FIRST code with distance +inf: a row whose distances are all +inf (|x|^2 overflows, or a
+    // -Inf entry against positive codes) moves no holder, every lane hands its first code to the merge, and the lowest key of the
+    // row is (bits(+inf), code 0) -- the oracle's answer.  A padding lane's start code is >= K but loses to that key (code 0 is real
+    // and every row gets a key from its lane); for a row with any finite distance nothing changes: a start holder never survives.
     const int code_r = code0 + r;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         float b2 = __builtin_inff(), thr = __builtin_inff();
-        int bi = 0x7fffffff;
+        int bi = code_r;
         bool band = false;
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             float d2 = __builtin_fmaf(-2.0f, acc[t][i], xnr[i]);
             d2 = d2 + en[t];
-            d2 = __builtin_fmaxf(d2, 0.0f);
+            d2 = __builtin_fmaxf(d2, floor_t[t]);
             const bool clear = d2 < thr;                                       // better by more than the collapse band
             band = band || (!clear && d2 < b2);                                // inside the band
             bi = clear ? code_r + 32 * t : bi;
@@ -393,12 +408,12 @@ __global__ __launch_bounds__(256, 2) void vq_assign_f32_kernel(const VqGroup g) 
         if (__builtin_expect(__any(band), 0)) {
             b2 = __builtin_inff();
             thr = __builtin_inff();
-            bi = 0x7fffffff;
+            bi = code_r;
 #pragma unroll
             for (int t = 0; t < T; ++t) {
                 float d2 = __builtin_fmaf(-2.0f, acc[t][i], xnr[i]);
                 d2 = d2 + en[t];
-                d2 = __builtin_fmaxf(d2, 0.0f);
+                d2 = __builtin_fmaxf(d2, floor_t[t]);
                 const bool clear = d2 < thr;
                 const bool near = !clear && d2 < b2;
                 if (near) {
@@ -759,7 +774,15 @@ __global__ __launch_bounds__(256) void vq_resolve_kernel(const VqFilterGroup g, 
         if (j < n_sub && __uint_as_float((unsigned)(v[j] & 0xffffffffull)) <= thr) cnt += (unsigned)(v[j] >> 48), ++alive;
     for (int j = F_MAX_SUB; j < n_sub; ++j)
         if (__uint_as_float((unsigned)(sm[j] & 0xffffffffull)) <= thr) cnt += (unsigned)(sm[j] >> 48), ++alive;
-    const bool open = valid && !(cnt == 1 && !force_all);
+    // Non-finite rows and codebooks.  A NaN score is never below a minimum nor inside a band, so a row with a NaN / Inf entry, a
+    // row whose |x|^2 overflows, or any row under a codebook with a non-finite |e_k|^2 (en_max, hence the band) would end "open"
+    // with no candidate -- its key never written.  Every such row has a threshold that is not finite (m = +-inf / NaN, or band =
+    // inf / NaN; the band holds |x|^2 and en_max).  Chosen remedy: it sets the overflow flag pair_count[F_LISTS], i.e. the level
+    // goes to the gated exact launch, which writes the exact kernel's key for every row (the other option, writing that key here,
+    // would repeat the exact chain in this kernel).  Costs the filter's speed only while non-finite values are present.
+    const bool bad = valid && !(__builtin_fabsf(thr) < __builtin_inff());
+    if (__any(bad) && (threadIdx.x & 63) == 0) L.pair_count[F_LISTS] = 1;
+    const bool open = valid && (bad || !(cnt == 1 && !force_all));
     if (valid) {
         if (!open) L.keys[row] = (unsigned long long)best;    // distance word 0: decided rows carry no exact distance (see vq_exact_dist_kernel)
         L.brow[row] = open ? thr : -__builtin_inff();
@@ -946,7 +969,8 @@ __global__ __launch_bounds__(256) void vq_unpack_keys(const unsigned long long* 
     __syncthreads();
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long)gridDim.x * 256) {
         const unsigned long long k = keys[i];
-        const unsigned code = (unsigned)(k & 0xffffffffull);
+        unsigned code = (unsigned)(k & 0xffffffffull);
+        if (code >= (unsigned)K) code = 0u;                       // last line of defence (no path should leave such a key): idx feeds unchecked gathers
         idx[i] = (long long)code;
         if (dmin) dmin[i] = __uint_as_float((unsigned int)(k >> 32));
         if (hist && code < (unsigned)K) atomicAdd((lds_hist ? lh : hist) + code, 1);   // K beyond the LDS budget: global bins
@@ -1531,6 +1555,7 @@ hipError_t launch_assign_group(int n, const void* const* x, int x_bf16, const in
         }
         end += assign_workgroups(N[i], plans[i].Kp, T);
         g.lv[q] = VqLevel{x[i], E4, enorm, keys, (long)N[i], C[i], plans[i].Kp, end};
+        g.lv[q].K = K[i];
         if (filter) {
             int* amb = reinterpret_cast<int*>(ws[i] + plans[i].off_amb);
             ig.lv[q].amb = amb;                                   // the sub-lists' counters and the overflow flag: zeroed by the init launch

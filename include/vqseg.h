@@ -61,6 +61,16 @@ const char* vqseg_kernel_name(const char* entry_point);
  *                                   "conv3x3_patch_tile512_min_workgroups" their minimum grid (default 512);
  *                                   "conv3x3_patch_tile512_launches" returns the number of launches that took such a tile so far and
  *                                   sets the counter to the value passed (tests)
+ *   "conv_last_variant"             returns the id of the kernel instantiation the last convolution / weight-gradient launch took (0: none
+ *                                   since it was last set to 0) and sets it to the value passed (tests).  One hexadecimal digit per
+ *                                   template argument, the kernel family in the top digit:
+ *                                     0x1TBWUMf  LDS-DMA implicit GEMM: T = pixel tile / 128, B = Cout tile / 32, W = waves, U = buffers, M = min
+ *                                                waves per SIMD, f = split-3 * 8 + linear-pixel prologue * 4 + parity classes * 2 + XCD-pair 1-D grid
+ *                                     0x20B0KPf  generic implicit GEMM: B = Cout tile / 32, K = K step / 32, P = precise, f = split-3 * 8
+ *                                     0x3TBWKUf  3x3 patch kernel: T = pixel tile / 256, B = Cout tile / 32, W = weight ring slots (0: chunk stages),
+ *                                                K = channel chunk / 32, U = taps unrolled, f = split-3 * 8 + XCD-pair 1-D grid
+ *                                     0x40OIS0f  nine-tap weight gradient: O, I = Cout / Cin tile / 32, S = stride, f = XCD-aware 1-D grid
+ *                                     0x50OI00f  1x1 weight gradient: the same digits;  0x60MN0P0  per-tap weight gradient: tiles / 32, P = precise
  *   "conv3x3_patch_xcd_pair"        1: the Cout chunks of a pixel tile are dispatched onto the same XCD (default 0:
  *                                   measured equal; the kernel does not wait on HBM for its patches)
  *   "conv_short_k_small_tile", "conv_short_k_single_buffer"   K loops of up to that many 64-channel stages take the
@@ -145,6 +155,11 @@ int vqseg_vq_forward_group(int n_levels, int bf16, const void* const* x, const f
  * valid after the call's stream work has finished; a 65th int is the overflow flag: the exact kernel served the level); 0 if the shape does not take the filter
  * (needs n_codes % 256 == 0 and channels % 32 == 0). */
 size_t vqseg_vq_filter_counter_offset(int64_t n_rows, int channels, int n_codes);
+
+/* Host-only query: the code tiles per wave (T = 8, 4, 2 or 1) the distance + argmin launch of these levels takes under the current
+ * options ("vq_max_tiles_per_wave", "vq_fine_split") -- one level: a single call of that shape; several: vqseg_vq_forward_group.
+ * HOST arrays of n_levels (1..4) entries.  VQSEG_EINVAL for a bad argument.  Touches no device. */
+int vqseg_vq_tiles_per_wave(int n_levels, const int64_t* n_rows_host, const int* n_codes_host);
 
 /* Assignment only (no gather): used by k-means and by tests. */
 int vqseg_vq_assign_f32(const float* x, const float* codebook, const void* prepared,

@@ -318,6 +318,7 @@ OPTIONS = {
     "conv3x3_patch_tile512_min_workgroups": (512, 1, 1),
     "conv3x3_patch_wide_tile_s3": (1, 0, 0),
     "conv3x3_patch_wide_tile": (1, 0, 0),
+    "conv_last_variant": (0, 0x1248314, 0x1248314),
     "vq_max_tiles_per_wave": (8, 2, 2),
     "vq_fine_split": (1, 0, 0),
     "vq_bf16_filter": (1, 0, 0),
@@ -407,3 +408,63 @@ def test_option_table_of_the_integration_guide_lists_the_same_keys_and_defaults(
     assert {k: int(d) for k, d, _ in rows} == {k: v[0] for k, v in OPTIONS.items()}
     assert len(rows) == len(OPTIONS)
     assert sorted(k for k, _, kind in rows if kind == "flag") == sorted(FLAGS)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# vqseg_vq_tiles_per_wave: the code tiles per wave T of the distance launch (vq_group_tiles, vq_kernels.hip).  The rule, with
+# groups_i = ceil(N_i / 128) row groups and tiles_i = ceil(K_i / 32) code tiles per level, wgs(t) = sum_i groups_i * tiles_i / t, t
+# "divides" when tiles_i % t == 0 for every level:
+#   1. "vq_fine_split" on: the largest t in {cap, cap / 2, ...}, t >= 4, that divides with wgs(t) >= 4096;
+#   2. else the largest t in {cap, ..., 1} that divides with wgs(t) >= 512; t = 1 is taken whatever its wgs.
+# cap = "vq_max_tiles_per_wave" (8).  Every row below is worked out by hand from this rule (the arithmetic in its comment).
+# ---------------------------------------------------------------------------------------------------------------------------
+T_CASES = [
+    # options, rows per level, codes per level, T
+    ({}, [172032], [512], 4),                                     # 1344 groups x 16 tiles: fine split, t=8 2688 < 4096, t=4 5376
+    ({"vq_fine_split": 0}, [172032], [512], 8),                   # rule 2 alone: t=8 2688 >= 512
+    ({}, [172032], [1024], 8),                                    # 32 tiles: fine split already at t=8: 1344 x 4 = 5376
+    ({"vq_max_tiles_per_wave": 4}, [172032], [512], 4),           # fine split from t=4: 5376
+    ({"vq_max_tiles_per_wave": 2}, [172032], [512], 2),           # the fine split never looks below 4; rule 2: t=2 1344 x 8
+    ({}, [32700], [2048], 4),                                     # 256 groups x 64 tiles: t=8 2048 < 4096, t=4 exactly 4096
+    ({"vq_fine_split": 0}, [32700], [2048], 8),                   # rule 2: t=8 2048 >= 512
+    ({}, [32640], [2048], 8),                                     # 255 groups: t=4 4080 < 4096, no fine split; rule 2 t=8 2040
+    ({}, [8100], [2040], 8),                                      # 64 groups x 64 tiles (2040 -> 2048 codes): t=8 exactly 512
+    ({}, [8064], [2040], 4),                                      # 63 groups: t=8 504 < 512, t=4 1008
+    ({"vq_max_tiles_per_wave": 4}, [8100], [2040], 4),            # t=4 1024
+    ({"vq_max_tiles_per_wave": 2}, [8100], [2040], 2),            # t=2 2048
+    ({"vq_max_tiles_per_wave": 1}, [8100], [2040], 1),
+    ({}, [8100], [1912], 4),                                      # 60 tiles: 60 % 8 = 4, t=4 64 x 15 = 960
+    ({}, [100000], [96], 1),                                      # 3 tiles: neither 8, 4 nor 2 divides
+    ({}, [100000], [192], 2),                                     # 6 tiles: t=2 782 x 3 = 2346
+    ({}, [128], [256], 1),                                        # 1 group x 8 tiles: at most 8 workgroups, t=1 whatever its count
+    ({}, [1000], [1024], 1),                                      # 8 groups x 32 tiles: t=2 128 < 512 -> t=1 (256 workgroups)
+    ({}, [32768, 8192, 2048], [512, 512, 512], 8),                # grouped: 336 groups x 16 tiles: t=8 672 (< 4096: no fine split) >= 512
+    ({}, [131072, 32768, 8192], [512, 512, 512], 4),              # 1344 groups: fine split, t=8 2688, t=4 5376
+    ({}, [32768, 8192], [512, 384], 4),                           # tiles 16 and 12: 12 % 8 != 0; t=4 256 x 4 + 64 x 3 = 1216
+    ({}, [32768, 8192], [512, 96], 1),                            # tiles 16 and 3: only t=1 divides both
+    ({"vq_fine_split": 0}, [131072, 32768, 8192], [512, 512, 512], 8),
+]
+
+
+@pytest.mark.parametrize("opts,rows,codes,want", T_CASES, ids=[f"{i}-T{c[3]}" for i, c in enumerate(T_CASES)])
+def test_vq_tiles_per_wave_follows_the_documented_rule(option_lib, opts, rows, codes, want):
+    for k, v in opts.items():
+        _hip.set_option(k, v)
+    assert _hip.vq_tiles_per_wave(rows, codes) == want
+    if len(rows) == 1:
+        assert _hip.vq_tiles_per_wave(rows[0], codes[0]) == want
+
+
+def test_vq_tiles_per_wave_refuses_bad_arguments(option_lib):
+    import ctypes
+    L = option_lib
+    one_n, one_k = (ctypes.c_int64 * 1)(128), (ctypes.c_int * 1)(64)
+    assert L.vqseg_vq_tiles_per_wave(0, one_n, one_k) == -1 and L.vqseg_vq_tiles_per_wave(5, one_n, one_k) == -1
+    assert L.vqseg_vq_tiles_per_wave(1, None, one_k) == -1 and L.vqseg_vq_tiles_per_wave(1, one_n, None) == -1
+    assert L.vqseg_vq_tiles_per_wave(1, (ctypes.c_int64 * 1)(0), one_k) == -1
+    assert L.vqseg_vq_tiles_per_wave(1, one_n, (ctypes.c_int * 1)(0)) == -1
+    assert b"tiles_per_wave" in L.vqseg_last_error()
+    with pytest.raises(ValueError):
+        _hip.vq_tiles_per_wave([128, 128], [64])
+    with pytest.raises(_hip.HipLibraryError, match="vqseg_vq_tiles_per_wave failed"):
+        _hip.vq_tiles_per_wave([128] * 5, [64] * 5)

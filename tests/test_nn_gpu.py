@@ -212,15 +212,30 @@ def test_conv3x3_patch_kernel_512_pixel_tiles(case, force_patch_kernel):
     prev = L.vqseg_set_option(b"conv3x3_patch_tile512_min_workgroups", 1)
     L.vqseg_set_option(b"conv3x3_patch_tile512_launches", 0)
     try:
-        _patch_case(case)
+        _y, _stat, ids = _patch_case(case)
     finally:
         L.vqseg_set_option(b"conv3x3_patch_tile512_min_workgroups", prev)
     assert L.vqseg_set_option(b"conv3x3_patch_tile512_launches", 0) >= 2, "the 512-pixel tile was not dispatched"
+    assert ids[:2] == [0x3220110 if case[3] == 64 else 0x3210110] * 2      # <64 / 32, 0, true, 32, false, 512>: one Cout chunk, no pair grid
+
+
+# the instantiation each of PATCH_CASES takes (forward launch, default options, the grid bar lowered by force_patch_kernel), in order
+PATCH_IDS = [
+    0x3143210, 0x3182200, 0x3143210, 0x3143210,            # <128, 3, true>; 256 outputs: <256, 2, false>, the 256-channel tile
+    0x3143210, 0x3182200,                                  # 384 outputs: three 128-channel chunks
+    0x3123210, 0x3113210, 0x3113210, 0x3123210,            # <64, 3, true>, <32, 3, true> (64-channel chunks)
+    0x3110110, 0x3143110, 0x3120110, 0x3143110,            # 32-channel chunks: chunk stages <32 / 64, 0, true, 32>; 96 / 32 + 32 -> 128: the tap ring <128, 3, true, 32>
+    0x3110110,
+    0x3140110, 0x3140110, 0x3120110, 0x3110110,            # chunk stages: 32 -> 128 / 256 <128, 0, true, 32>, 96 -> 64, 32 + 64 -> 32
+]
 
 
 @pytest.mark.parametrize("case", PATCH_CASES)
 def test_conv3x3_patch_kernel(case, force_patch_kernel):
-    _patch_case(case)
+    _y, _stat, ids = _patch_case(case)
+    want = PATCH_IDS[PATCH_CASES.index(case)]
+    bn = 32 * (want >> 16 & 15)
+    assert ids[:2] == [want, want | (1 if case[3] > bn else 0)], [hex(i) for i in ids]      # second launch: the XCD-pair grid when there are several Cout chunks
 
 
 def _patch_case(case):
@@ -246,9 +261,12 @@ def _patch_case(case):
     y = torch.full((n, h, w, cout), float("nan"), dtype=torch.bfloat16, device=dev())
     slots = L.vqseg_conv_stat_slots(n * h * w, cout)
     stat = torch.full((slots, 2, cout), float("nan"), dtype=torch.float32, device=dev())
+    ids = []                                               # conv_last_variant of the forward, the XCD-pair and the data-gradient launch
+    L.vqseg_set_option(b"conv_last_variant", 0)
     rc = L.vqseg_conv2d_f(xa.data_ptr(), xb.data_ptr() if c2 else None, c1, hi.data_ptr(), None, y.data_ptr(), stat.data_ptr(),
                           n, h, w, cin, cout, 3, 3, 1, 1, int(reflect), 1, h, w, 0, st)
     assert rc == 0, L.vqseg_last_error()
+    ids.append(L.vqseg_set_option(b"conv_last_variant", 0))
     torch.cuda.synchronize()
     assert rel(y.float(), ref) < 2 ** -7
     # 1-D launch with the Cout chunks of a pixel tile on one XCD (conv3x3_patch_xcd_pair): same workgroups, same bits
@@ -259,6 +277,7 @@ def _patch_case(case):
                           n, h, w, cin, cout, 3, 3, 1, 1, int(reflect), 1, h, w, 0, st)
     L.vqseg_set_option(b"conv3x3_patch_xcd_pair", prev)
     assert rc == 0, L.vqseg_last_error()
+    ids.append(L.vqseg_set_option(b"conv_last_variant", 0))
     torch.cuda.synchronize()
     assert torch.equal(y2, y) and torch.equal(stat2[:n * h * w // (64 if cout >= 64 else 32)], stat[:n * h * w // (64 if cout >= 64 else 32)])
     # BatchNorm partials of the fp32 accumulators: merged mean / biased variance per channel
@@ -283,8 +302,78 @@ def _patch_case(case):
         rc = L.vqseg_conv2d_f(gyd.data_ptr(), None, cout, thi.data_ptr(), None, gx.data_ptr(), None, n, h, w, cout, cin, 3, 3, 1, 1, 0,
                               1, h, w, 0, st)
         assert rc == 0, L.vqseg_last_error()
+        ids.append(L.vqseg_set_option(b"conv_last_variant", 0))
         torch.cuda.synchronize()
         assert rel(gx.float(), gref) < 2 ** -7
+    return y, stat[:n_slots], ids
+
+
+def _same_patch_results(a, b):
+    return torch.equal(a[0].view(torch.int16), b[0].view(torch.int16)) and torch.equal(a[1].view(torch.int32), b[1].view(torch.int32))
+
+
+# the 64-channel-chunk cases with Cout % 128 == 0: n, c1, c2, cout, h, w, reflect
+UNROLL_CASES = [c for c in PATCH_CASES if c[3] % 128 == 0 and (c[1] + c[2]) % 64 == 0 and (c[2] == 0 or c[1] % 64 == 0)]
+UNROLL_IDS = {1: 0x3143210, 2: 0x3144210, 0: 0x3143200}   # <128, 3, true>, <128, 4, true> (four-slot weight ring), <128, 3, false> (tap loop rolled)
+
+
+@pytest.mark.parametrize("unroll", [0, 2])
+@pytest.mark.parametrize("case", UNROLL_CASES)
+def test_conv3x3_patch_kernel_unroll_values(case, unroll, force_patch_kernel):
+    """conv3x3_patch_unroll = 0 and 2 (the 128-channel tile with the tap loop rolled / with a four-slot weight ring; the 256-channel
+    tile switched off so that the 256-output cases reach them): the same checks as the default, the ids of the instantiations, and
+    the default's bits -- every variant feeds each accumulator the same MFMA sequence (chunk, tap, K step in this order); unrolling
+    and the ring depth only change when the weight DMA is issued and waited for."""
+    from vq_seg_amd import _hip
+    assert len(UNROLL_CASES) == 6
+    n, c1, c2, cout, h, w, reflect = case
+    prev_wide = _hip.set_option("conv3x3_patch_wide_tile", 0)
+    try:
+        base = _patch_case(case)
+        prev = _hip.set_option("conv3x3_patch_unroll", unroll)
+        try:
+            got = _patch_case(case)
+        finally:
+            _hip.set_option("conv3x3_patch_unroll", prev)
+    finally:
+        _hip.set_option("conv3x3_patch_wide_tile", prev_wide)
+    pair = 1 if cout > 128 else 0                          # several Cout chunks: the second launch takes the 1-D XCD-pair grid
+    assert base[2][:2] == [UNROLL_IDS[1], UNROLL_IDS[1] | pair]
+    assert got[2][:2] == [UNROLL_IDS[unroll], UNROLL_IDS[unroll] | pair], [hex(i) for i in got[2]]
+    if len(got[2]) > 2 and (c1 + c2) % 128 == 0:           # the data-gradient form has Cout = cin: on the 128-channel tile too
+        assert got[2][2] == UNROLL_IDS[unroll]
+    assert _same_patch_results(base, got)
+
+
+CHUNK_STAGE_CASES = [
+    # the 32-channel-chunk cases whose dispatch "conv3x3_patch_chunk_stage" changes: case, id with chunk stages (default), id with the tap ring
+    ((2, 32, 0, 32, 16, 32, False), 0x3110110, 0x3113110),      # <32, 0, true, 32> / <32, 3, true, 32>
+    ((2, 32, 0, 64, 8, 32, True), 0x3120110, 0x3123110),        # <64, 0, true, 32> / <64, 3, true, 32>
+    ((2, 160, 0, 32, 8, 32, False), 0x3110110, 0x3113110),      # five chunks
+    ((2, 32, 0, 128, 16, 32, False), 0x3140110, 0x3143110),     # one 32-channel chunk into 128 outputs: <128, 0, true, 32> / <128, 3, true, 32>
+    ((1, 32, 0, 256, 8, 32, True), 0x3140110, 0x3143110),       # ... two Cout chunks
+    ((1, 96, 0, 64, 16, 16, False), 0x3120110, 0x3123110),
+    ((2, 32, 64, 32, 16, 32, True), 0x3110110, 0x3113110),      # concat 32 + 64
+]
+
+
+@pytest.mark.parametrize("case,id_stage,id_ring", CHUNK_STAGE_CASES)
+def test_conv3x3_patch_kernel_tap_ring_for_32_channel_chunks(case, id_stage, id_ring, force_patch_kernel):
+    """conv3x3_patch_chunk_stage = 0: the 32-channel-chunk layers on the per-tap weight ring.  Same checks, the ring's ids, and the
+    default's bits: chunk stages load a chunk's nine weight tiles at once instead of tap by tap, the MFMAs and their order per
+    accumulator are the same."""
+    from vq_seg_amd import _hip
+    assert all(c in PATCH_CASES for c, _a, _b in CHUNK_STAGE_CASES)
+    pair = 1 if case[3] > 128 else 0
+    base = _patch_case(case)
+    prev = _hip.set_option("conv3x3_patch_chunk_stage", 0)
+    try:
+        got = _patch_case(case)
+    finally:
+        _hip.set_option("conv3x3_patch_chunk_stage", prev)
+    assert base[2][:2] == [id_stage, id_stage | pair], [hex(i) for i in base[2]]
+    assert got[2][:2] == [id_ring, id_ring | pair], [hex(i) for i in got[2]]
+    assert _same_patch_results(base, got)
 
 
 WGRAD_CASES = [
@@ -293,6 +382,106 @@ WGRAD_CASES = [
     (2, 64, 0, 32, 20, 16, True), (3, 32, 0, 128, 4, 16, False), (2, 32, 0, 64, 8, 16, True), (5, 256, 256, 128, 16, 16, False),
     (4, 128, 0, 128, 32, 32, False), (4, 64, 64, 256, 32, 32, True),      # r4: >= 8 slabs of several (ci, co) tiles: the XCD-aware 1-D grid
 ]
+# conv_wgrad3x3_kernel<COT, CIT> of each case, in order (0x40OI10f; f = 1: the XCD-aware 1-D grid, which the last two take)
+WGRAD_IDS = [0x4042100, 0x4022100, 0x4011100, 0x4011100, 0x4012100, 0x4041100, 0x4021100, 0x4042100, 0x4042101, 0x4042101]
+# enough pixels and tiles that the slab count follows the options instead of the 512-pixels-per-slab floor (the option tests below)
+WGRAD_SLAB_CASES = [(2, 96, 0, 32, 256, 176, False), (2, 256, 0, 512, 68, 64, False)]
+
+
+def _wgrad_ref_by_taps(x, gy, k, stride, reflect):
+    """fp64 weight gradient [cout, cin, k, k] as one matmul per tap (the same sums as torch.nn.grad.conv2d_weight, without its
+    im2col buffer): x [n, h, w, cin], gy [n, ho, wo, cout]"""
+    n, ho, wo, cout = gy.shape
+    pad = k // 2
+    xp = F.pad(x.double().permute(0, 3, 1, 2), (pad,) * 4, mode="reflect" if reflect else "constant").permute(0, 2, 3, 1)
+    g = gy.double().reshape(-1, cout).t().contiguous()
+    ref = torch.empty(cout, x.shape[3], k, k, dtype=torch.float64)
+    for kh in range(k):
+        for kw in range(k):
+            win = xp[:, kh:kh + (ho - 1) * stride + 1:stride, kw:kw + (wo - 1) * stride + 1:stride, :]
+            ref[:, :, kh, kw] = g @ win.reshape(-1, x.shape[3])
+    return ref
+
+
+_WGRAD_OPERANDS = {}
+
+
+def _wgrad_operands(kind, case):
+    """(x, gy, fp64 reference) of a weight-gradient case, built once and shared by the tests that run it under several options"""
+    if (kind, case) in _WGRAD_OPERANDS:
+        return _WGRAD_OPERANDS[kind, case]
+    if kind == "3x3":
+        n, c1, c2, cout, h, w, reflect = case
+        cin, seed = c1 + c2, sum(case[:6])
+        x = synth.uniform(seed, (n, h, w, cin), -1, 1).bfloat16()
+        gy = synth.uniform(seed + 1, (n, h, w, cout), -1, 1).bfloat16()
+        if case in WGRAD_SLAB_CASES:
+            ref = _wgrad_ref_by_taps(x, gy, 3, 1, reflect)
+        else:
+            xp = F.pad(x.double().permute(0, 3, 1, 2), (1, 1, 1, 1), mode="reflect" if reflect else "constant")
+            ref = torch.nn.grad.conv2d_weight(xp, (cout, cin, 3, 3), gy.double().permute(0, 3, 1, 2))
+    elif kind == "3x3s2":
+        n, cin, cout, h, w, reflect, pair = case
+        seed = sum(case[:5]) + 11
+        x = synth.uniform(seed, (n, h, w, cin), -1, 1).bfloat16()
+        gy = synth.uniform(seed + 1, (n, h // 2, w // 2, cout), -1, 1).bfloat16()
+        xp = F.pad(x.double().permute(0, 3, 1, 2), (1, 1, 1, 1), mode="reflect" if reflect else "constant")
+        ref = torch.nn.grad.conv2d_weight(xp, (cout, cin, 3, 3), gy.double().permute(0, 3, 1, 2), stride=2)
+    else:
+        n, cin, cout, h, w, stride = case
+        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+        seed = sum(case) + 5
+        x = synth.uniform(seed, (n, h, w, cin), -1, 1).bfloat16()
+        gy = synth.uniform(seed + 1, (n, ho, wo, cout), -1, 1).bfloat16()
+        xs = x[:, ::stride, ::stride, :].double().reshape(-1, cin)
+        ref = (gy.double().reshape(-1, cout).t() @ xs).reshape(cout, cin, 1, 1)
+    _WGRAD_OPERANDS[kind, case] = (x, gy, ref)
+    return x, gy, ref
+
+
+WS_GUARD = 4096                                            # bytes behind the weight-gradient workspace that no launch may touch
+
+
+def _wgrad_workspace(nbytes):
+    ws = torch.empty(nbytes + WS_GUARD, dtype=torch.uint8, device=dev())
+    ws[nbytes:] = 0xA5
+    return ws
+
+
+def _wgrad_workspace_intact(ws, nbytes):
+    return bool((ws[nbytes:] == 0xA5).all())
+
+
+def _wgrad3x3_case(case):
+    """The body of test_wgrad3x3_fused_taps under whatever options are set: (gw of the first launch, its variant id, workspace bytes)"""
+    from vq_seg_amd import _hip
+    n, c1, c2, cout, h, w, reflect = case
+    cin = c1 + c2
+    L = _hip.lib()
+    x, gy, ref = _wgrad_operands("3x3", case)
+    xa = x[..., :c1].contiguous().to(dev())
+    xb = x[..., c1:].contiguous().to(dev()) if c2 else None
+    gyd = gy.to(dev())
+    nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n, h, w, cin, h, w, cout, 3, 3)
+    ws = _wgrad_workspace(nbytes)
+    gw = torch.full((cout, cin, 3, 3), float("nan"), dtype=torch.float32, device=dev())
+    L.vqseg_set_option(b"conv_last_variant", 0)
+    rc = L.vqseg_conv2d_wgrad_f(gyd.data_ptr(), xa.data_ptr(), xb.data_ptr() if c2 else None, c1, n, h, w, cin, h, w, cout, 3, 3,
+                                1, 1, int(reflect), 0, cin, 0, 0, ws.data_ptr(), nbytes, gw.data_ptr(),
+                                torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, L.vqseg_last_error()
+    vid = L.vqseg_set_option(b"conv_last_variant", 0)
+    torch.cuda.synchronize()
+    assert rel(gw, ref) < 2e-5
+    first = gw.clone()
+    # accumulate = 1 adds the same gradient onto gw (the trainer's bucket view)
+    rc = L.vqseg_conv2d_wgrad_f(gyd.data_ptr(), xa.data_ptr(), xb.data_ptr() if c2 else None, c1, n, h, w, cin, h, w, cout, 3, 3,
+                                1, 1, int(reflect), 0, cin, 0, 1, ws.data_ptr(), nbytes, gw.data_ptr(),
+                                torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, L.vqseg_last_error()
+    assert rel(gw, 2 * ref) < 2e-5
+    assert _wgrad_workspace_intact(ws, nbytes)
+    return first, vid, nbytes
 
 
 @pytest.mark.parametrize("case", WGRAD_CASES)
@@ -300,33 +489,8 @@ def test_wgrad3x3_fused_taps(case):
     """The fused nine-tap bf16 weight-gradient kernel through the C ABI against an fp64 reference on the SAME bf16
     values: products of bf16 pairs are exact in fp32, so only the accumulation order differs (tolerance 2e-5 of
     the tensor scale).  Reference: torch.nn.grad.conv2d_weight on the explicitly padded input."""
-    from vq_seg_amd import _hip
-    n, c1, c2, cout, h, w, reflect = case
-    cin = c1 + c2
-    L = _hip.lib()
-    seed = sum(case[:6])
-    x = synth.uniform(seed, (n, h, w, cin), -1, 1).bfloat16()
-    gy = synth.uniform(seed + 1, (n, h, w, cout), -1, 1).bfloat16()
-    xp = F.pad(x.double().permute(0, 3, 1, 2), (1, 1, 1, 1), mode="reflect" if reflect else "constant")
-    ref = torch.nn.grad.conv2d_weight(xp, (cout, cin, 3, 3), gy.double().permute(0, 3, 1, 2))
-    xa = x[..., :c1].contiguous().to(dev())
-    xb = x[..., c1:].contiguous().to(dev()) if c2 else None
-    gyd = gy.to(dev())
-    nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n, h, w, cin, h, w, cout, 3, 3)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev())
-    gw = torch.full((cout, cin, 3, 3), float("nan"), dtype=torch.float32, device=dev())
-    rc = L.vqseg_conv2d_wgrad_f(gyd.data_ptr(), xa.data_ptr(), xb.data_ptr() if c2 else None, c1, n, h, w, cin, h, w, cout, 3, 3,
-                                1, 1, int(reflect), 0, cin, 0, 0, ws.data_ptr(), nbytes, gw.data_ptr(),
-                                torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, L.vqseg_last_error()
-    torch.cuda.synchronize()
-    assert rel(gw, ref) < 2e-5
-    # accumulate = 1 adds the same gradient onto gw (the trainer's bucket view)
-    rc = L.vqseg_conv2d_wgrad_f(gyd.data_ptr(), xa.data_ptr(), xb.data_ptr() if c2 else None, c1, n, h, w, cin, h, w, cout, 3, 3,
-                                1, 1, int(reflect), 0, cin, 0, 1, ws.data_ptr(), nbytes, gw.data_ptr(),
-                                torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, L.vqseg_last_error()
-    assert rel(gw, 2 * ref) < 2e-5
+    _first, vid, _nbytes = _wgrad3x3_case(case)
+    assert vid == WGRAD_IDS[WGRAD_CASES.index(case)], hex(vid)
 
 
 WGRAD_S2_CASES = [
@@ -337,28 +501,24 @@ WGRAD_S2_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", WGRAD_S2_CASES)
-def test_wgrad3x3_stride2_fused_taps(case):
-    """Stride-2 3x3 layers (first conv2 of a Bottleneck stage, first conv1 of a BasicBlock stage) on the nine-tap kernel (r4: 2 x 16
-    output blocks, the 5 x 33 input patch de-interleaved into column-parity planes by the DMA): fp64 reference on the same bf16 values,
-    2e-5 of the tensor scale; and the r3 per-tap kernel (option off) agrees with the same reference."""
+def _wgrad3x3_s2_case(case, stride2_values=(1, 0)):
+    """The body of test_wgrad3x3_stride2_fused_taps under whatever options are set: [(gw, variant id, workspace bytes)] per value of
+    conv_wgrad3x3_stride2"""
     from vq_seg_amd import _hip
     n, cin, cout, h, w, reflect, pair = case
     ho, wo = h // 2, w // 2
     L = _hip.lib()
-    seed = sum(case[:5]) + 11
-    x = synth.uniform(seed, (n, h, w, cin), -1, 1).bfloat16()
-    gy = synth.uniform(seed + 1, (n, ho, wo, cout), -1, 1).bfloat16()
-    xp = F.pad(x.double().permute(0, 3, 1, 2), (1, 1, 1, 1), mode="reflect" if reflect else "constant")
-    ref = torch.nn.grad.conv2d_weight(xp, (cout, cin, 3, 3), gy.double().permute(0, 3, 1, 2), stride=2)
+    x, gy, ref = _wgrad_operands("3x3s2", case)
     xd, gyd = x.to(dev()), gy.to(dev())
     nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n, h, w, cin, ho, wo, cout, 3, 3)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev())
+    ws = _wgrad_workspace(nbytes)
     st = torch.cuda.current_stream().cuda_stream
-    for opt in (1, 0):
+    out = []
+    for opt in stride2_values:
         prev = _hip.set_option("conv_wgrad3x3_stride2", opt)
         try:
             gw = torch.full((cout, cin, 3, 3), float("nan"), dtype=torch.float32, device=dev())
+            L.vqseg_set_option(b"conv_last_variant", 0)
             if pair:                                    # images [0, na) from the first source, the rest from the second
                 na = 1
                 rc = L.vqseg_conv2d_wgrad2_f(gyd[:na].data_ptr(), xd[:na].data_ptr(), None, na, gyd[na:].data_ptr(), xd[na:].data_ptr(), None,
@@ -368,10 +528,25 @@ def test_wgrad3x3_stride2_fused_taps(case):
                 rc = L.vqseg_conv2d_wgrad_f(gyd.data_ptr(), xd.data_ptr(), None, cin, n, h, w, cin, ho, wo, cout, 3, 3, 2, 1, int(reflect),
                                             0, cin, 0, 0, ws.data_ptr(), nbytes, gw.data_ptr(), st)
             assert rc == 0, L.vqseg_last_error()
+            vid = L.vqseg_set_option(b"conv_last_variant", 0)
             torch.cuda.synchronize()
             assert rel(gw, ref) < 2e-5, opt
+            out.append((gw, vid, nbytes))
         finally:
             _hip.set_option("conv_wgrad3x3_stride2", prev)
+    assert _wgrad_workspace_intact(ws, nbytes)
+    return out
+
+
+@pytest.mark.parametrize("case", WGRAD_S2_CASES)
+def test_wgrad3x3_stride2_fused_taps(case):
+    """Stride-2 3x3 layers (first conv2 of a Bottleneck stage, first conv1 of a BasicBlock stage) on the nine-tap kernel (r4: 2 x 16
+    output blocks, the 5 x 33 input patch de-interleaved into column-parity planes by the DMA): fp64 reference on the same bf16 values,
+    2e-5 of the tensor scale; and the r3 per-tap kernel (option off) agrees with the same reference."""
+    n, cin, cout, h, w, reflect, pair = case
+    nine, per_tap = _wgrad3x3_s2_case(case)
+    assert nine[1] & ~1 == (0x4042200 if cin % 64 == 0 else 0x4041200)     # <4, 2, 2> / <4, 1, 2>, either grid
+    assert per_tap[1] == (0x6044000 if cin % 128 == 0 else 0x6041000)      # conv_wgrad_kernel<4, 4 or 1, false>
 
 
 WGRAD1_CASES = [
@@ -380,31 +555,141 @@ WGRAD1_CASES = [
     (2, 256, 512, 16, 16, 2), (1, 128, 256, 15, 9, 2), (4, 1024, 256, 8, 8, 1),
     (2, 64, 64, 16, 16, 1), (3, 64, 64, 9, 7, 1), (2, 192, 64, 12, 20, 1),      # r4: 64 output channels on four waves (<2, 2>)
     (2, 256, 256, 32, 32, 1), (2, 256, 512, 64, 32, 2),                         # r4: >= 8 slabs of several tiles: the XCD-aware 1-D grid
+    (4, 256, 512, 64, 64, 2),      # (the stride-2 case above has 1024 output pixels = 4 slabs and stays on the 3-D grid: this one has 16)
 ]
+# conv_wgrad1x1_kernel<COT, CIT> of each case, in order (0x50OI00f; f = 1: the XCD-aware 1-D grid)
+WGRAD1_IDS = [0x5084000, 0x5082000, 0x5044000, 0x5042000, 0x5024000, 0x5084000, 0x5084000, 0x5084000, 0x5022000, 0x5022000, 0x5022000,
+              0x5084001, 0x5084000, 0x5084001]
+WGRAD1_SLAB_CASES = [(2, 256, 256, 128, 132, 1)]            # 33792 pixels, two tiles: 106 slabs at the default, 13 at 10 %, 132 at 400 %
+
+
+def _wgrad1x1_case(case):
+    """The body of test_wgrad1x1 under whatever options are set: (gw of the first launch, its variant id, workspace bytes)"""
+    from vq_seg_amd import _hip
+    n, cin, cout, h, w, stride = case
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    L = _hip.lib()
+    x, gy, ref = _wgrad_operands("1x1", case)
+    xd, gyd = x.to(dev()), gy.to(dev())
+    nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n, h, w, cin, ho, wo, cout, 1, 1)
+    ws = _wgrad_workspace(nbytes)
+    gw = torch.full((cout, cin, 1, 1), float("nan"), dtype=torch.float32, device=dev())
+    first = vid = None
+    for acc in (0, 1):
+        L.vqseg_set_option(b"conv_last_variant", 0)
+        rc = L.vqseg_conv2d_wgrad_f(gyd.data_ptr(), xd.data_ptr(), None, cin, n, h, w, cin, ho, wo, cout, 1, 1, stride, 0, 0, 0, cin, 0,
+                                    acc, ws.data_ptr(), nbytes, gw.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, L.vqseg_last_error()
+        if acc == 0:
+            vid = L.vqseg_set_option(b"conv_last_variant", 0)
+        torch.cuda.synchronize()
+        assert rel(gw, (1 + acc) * ref) < 2e-5
+        if acc == 0:
+            first = gw.clone()
+    assert _wgrad_workspace_intact(ws, nbytes)
+    return first, vid, nbytes
 
 
 @pytest.mark.parametrize("case", WGRAD1_CASES)
 def test_wgrad1x1(case):
     """bf16 1x1 weight-gradient kernel through the C ABI against fp64 on the same bf16 values (2e-5 of scale)."""
+    _first, vid, _nbytes = _wgrad1x1_case(case)
+    assert vid == WGRAD1_IDS[WGRAD1_CASES.index(case)], hex(vid)
+
+
+def _slab_bytes(cout, cin, k, slabs):
+    return slabs * cout * cin * k * k * 4
+
+
+WGRAD_OPTION_CASES = [
+    # kind, case, options, id of the launch, slabs the workspace query answers (None: not pinned), same bits as the default?
+    # -- conv_wgrad_xcd = 0: the same workgroups on a 3-D grid instead of the XCD-aware 1-D one (id bit 0): same slabs, same bits
+    ("3x3", (4, 128, 0, 128, 32, 32, False), {"conv_wgrad_xcd": 0}, 0x4042100, None, True),
+    ("3x3", (4, 64, 64, 256, 32, 32, True), {"conv_wgrad_xcd": 0}, 0x4042100, None, True),
+    ("3x3s2", (4, 128, 256, 64, 64, True, False), {"conv_wgrad_xcd": 0}, 0x4042200, None, True),
+    ("3x3s2", (4, 128, 128, 64, 64, False, True), {"conv_wgrad_xcd": 0}, 0x4042200, None, True),
+    ("1x1", (2, 256, 256, 32, 32, 1), {"conv_wgrad_xcd": 0}, 0x5084000, None, True),
+    ("1x1", (4, 256, 512, 64, 64, 2), {"conv_wgrad_xcd": 0}, 0x5084000, None, True),
+    # -- the options below change the number of slabs = how the pixel sum is split: other roundings, the same reference and bar.
+    # 96 -> 32 (<1, 1>, three tiles, 1408 four-row blocks: at most 176 slabs): a full round is 1024 workgroups -> 341 -> 176 slabs;
+    # the earlier split aims at 512 -> 171 -> 157 after evening out; 10 %: 102 / 3 = 34 (the per-tap kernel's 38 sizes the workspace)
+    ("3x3", WGRAD_SLAB_CASES[0], {}, 0x4011101, 176, True),
+    ("3x3", WGRAD_SLAB_CASES[0], {"conv_wgrad3x3_fill": 0}, 0x4011101, 157, False),
+    ("3x3", WGRAD_SLAB_CASES[0], {"conv_wgrad_round_pct": 10}, 0x4011101, 38, False),
+    ("3x3", WGRAD_SLAB_CASES[0], {"conv_wgrad_round_pct": 400}, 0x4011101, 176, False),
+    # 256 -> 512 (<4, 2>, 16 tiles, 136 blocks: at most 17 slabs): 256 / 16 = 16 slabs; 400 %: 64 -> 17; 10 %: 25 / 16 = 1 slab, which
+    # takes the 3-D grid (the per-tap kernel's 15 sizes the workspace); the earlier split is the same 16
+    ("3x3", WGRAD_SLAB_CASES[1], {}, 0x4042101, 16, True),
+    ("3x3", WGRAD_SLAB_CASES[1], {"conv_wgrad3x3_fill": 0}, 0x4042101, 16, False),
+    ("3x3", WGRAD_SLAB_CASES[1], {"conv_wgrad_round_pct": 10}, 0x4042100, 15, False),
+    ("3x3", WGRAD_SLAB_CASES[1], {"conv_wgrad_round_pct": 400}, 0x4042101, 17, False),
+    # stride 2, 128 -> 256 at 64^2 (<4, 2, 2>, 4 tiles, 128 two-row blocks: at most 8 slabs): 10 % -> 25 / 4 = 6 slabs: 3-D grid
+    ("3x3s2", (4, 128, 256, 64, 64, True, False), {"conv_wgrad3x3_fill": 0}, 0x4042201, None, False),
+    ("3x3s2", (4, 128, 256, 64, 64, True, False), {"conv_wgrad_round_pct": 10}, 0x4042200, None, False),
+    ("3x3s2", (4, 128, 256, 64, 64, True, False), {"conv_wgrad_round_pct": 400}, 0x4042201, None, False),
+    # 1x1, 256 -> 256 on 33792 pixels (<8, 4>, two tiles, 528 stages: at most 132 slabs): 128 -> 106 after evening out, 13 at 10 %,
+    # 132 at 400 %; the per-tap kernel's bound (132) sizes the workspace whatever the option
+    ("1x1", WGRAD1_SLAB_CASES[0], {}, 0x5084001, 132, True),
+    ("1x1", WGRAD1_SLAB_CASES[0], {"conv_wgrad_round_pct": 10}, 0x5084001, 132, False),
+    ("1x1", WGRAD1_SLAB_CASES[0], {"conv_wgrad_round_pct": 400}, 0x5084001, 132, False),
+    ("1x1", (4, 256, 512, 64, 64, 2), {"conv_wgrad_round_pct": 10}, 0x5084000, None, False),      # 16 -> 7 slabs: the 3-D grid
+]
+
+
+@pytest.mark.parametrize("kind,case,opts,want_id,want_slabs,same_bits", WGRAD_OPTION_CASES,
+                         ids=[f"{k}-{'x'.join(map(str, c[:5]))}-{'-'.join(f'{a}{b}' for a, b in o.items()) or 'default'}" for k, c, o, *_ in WGRAD_OPTION_CASES])
+def test_wgrad_option_values(kind, case, opts, want_id, want_slabs, same_bits):
+    """conv_wgrad_xcd = 0, conv_wgrad3x3_fill = 0 and conv_wgrad_round_pct = 10 / 400 through the bodies of the three weight-gradient
+    tests: the same fp64 reference and bar as the default, the id of the instantiation and grid that ran, the slab count behind
+    vqseg_conv2d_wgrad_workspace_bytes (queried after the option is set), guard bytes behind the workspace, and bit-identity with
+    the default where the option only changes the grid mapping."""
     from vq_seg_amd import _hip
-    n, cin, cout, h, w, stride = case
-    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    run = {"3x3": _wgrad3x3_case, "3x3s2": lambda c: _wgrad3x3_s2_case(c, (1,))[0], "1x1": _wgrad1x1_case}[kind]
+    cout, cin, k = (case[3], case[1] + case[2], 3) if kind == "3x3" else (case[2], case[1], 3 if kind == "3x3s2" else 1)
+    prev = {key: _hip.set_option(key, v) for key, v in opts.items()}
+    try:
+        gw, vid, nbytes = run(case)
+    finally:
+        for key, v in prev.items():
+            _hip.set_option(key, v)
+    assert vid == want_id, hex(vid)
+    if want_slabs is not None:
+        assert nbytes == _slab_bytes(cout, cin, k, want_slabs), nbytes / _slab_bytes(cout, cin, k, 1)
+    if same_bits and opts:
+        base, base_id, base_bytes = run(case)
+        assert base_id == want_id | 1 and base_bytes == nbytes
+        assert torch.equal(base.view(torch.int32), gw.view(torch.int32))
+
+
+def test_wgrad_workspace_sized_for_another_round_pct_is_refused_not_overrun():
+    """A workspace sized at conv_wgrad_round_pct = 100 (16 slabs) handed to a launch at 400 (17 slabs): vqseg_conv2d_wgrad_f sizes
+    its check with the slab count of the launch it is about to make (wgrad_slabs under the options of that moment, the same plan
+    launch_wgrad_impl takes), so it answers VQSEG_ENOSPC before anything is launched -- or, would the plans ever agree, succeeds
+    with the right gradient; either way nothing behind the workspace is written."""
+    from vq_seg_amd import _hip
     L = _hip.lib()
-    seed = sum(case) + 5
-    x = synth.uniform(seed, (n, h, w, cin), -1, 1).bfloat16()
-    gy = synth.uniform(seed + 1, (n, ho, wo, cout), -1, 1).bfloat16()
-    xs = x[:, ::stride, ::stride, :].double().reshape(-1, cin)
-    ref = (gy.double().reshape(-1, cout).t() @ xs).reshape(cout, cin, 1, 1)
+    case = WGRAD_SLAB_CASES[1]
+    n, c1, c2, cout, h, w, reflect = case
+    x, gy, ref = _wgrad_operands("3x3", case)
     xd, gyd = x.to(dev()), gy.to(dev())
-    nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n, h, w, cin, ho, wo, cout, 1, 1)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev())
-    gw = torch.full((cout, cin, 1, 1), float("nan"), dtype=torch.float32, device=dev())
-    for acc in (0, 1):
-        rc = L.vqseg_conv2d_wgrad_f(gyd.data_ptr(), xd.data_ptr(), None, cin, n, h, w, cin, ho, wo, cout, 1, 1, stride, 0, 0, 0, cin, 0,
-                                    acc, ws.data_ptr(), nbytes, gw.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        assert rc == 0, L.vqseg_last_error()
-        torch.cuda.synchronize()
-        assert rel(gw, (1 + acc) * ref) < 2e-5
+    nbytes = L.vqseg_conv2d_wgrad_workspace_bytes(n, h, w, c1, h, w, cout, 3, 3)
+    assert nbytes == _slab_bytes(cout, c1, 3, 16)
+    ws = _wgrad_workspace(nbytes)
+    gw = torch.full((cout, c1, 3, 3), float("nan"), dtype=torch.float32, device=dev())
+    prev = _hip.set_option("conv_wgrad_round_pct", 400)
+    try:
+        assert L.vqseg_conv2d_wgrad_workspace_bytes(n, h, w, c1, h, w, cout, 3, 3) == _slab_bytes(cout, c1, 3, 17)
+        rc = L.vqseg_conv2d_wgrad_f(gyd.data_ptr(), xd.data_ptr(), None, c1, n, h, w, c1, h, w, cout, 3, 3, 1, 1, 0, 0, c1, 0, 0,
+                                    ws.data_ptr(), nbytes, gw.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    finally:
+        _hip.set_option("conv_wgrad_round_pct", prev)
+    torch.cuda.synchronize()
+    assert rc in (0, -2), L.vqseg_last_error()                      # VQSEG_ENOSPC
+    if rc == 0:
+        assert rel(gw, ref) < 2e-5
+    else:
+        assert b"workspace too small" in L.vqseg_last_error() and bool(torch.isnan(gw).all())
+    assert _wgrad_workspace_intact(ws, nbytes)
 
 
 @pytest.mark.parametrize("reflect", [True, False])
@@ -678,16 +963,24 @@ def test_short_k_dispatch_variants_agree():
         wt = (synth.uniform(cin, (cout, cin, 1, 1), -1, 1) * (2.0 / cin) ** 0.5).to(dev())
         hi = torch.empty(L.vqseg_conv_packed_elems(cout, cin, 1, 1, 0), dtype=torch.int16, device=dev())
         assert L.vqseg_conv_pack_weights_f32(wt.data_ptr(), cout, cin, 1, 1, 0, hi.data_ptr(), None, st) == 0
-        outs = []
+        outs, ids = [], []
         for opts in ({}, {"conv_short_k_single_buffer": 8, "conv_short_k_small_tile": 0}, {"conv_short_k_small_tile": 8},
                      {"conv_xcd_pair": 0}, {"conv_xcd_pair": 16}):       # 2-D grid / Cout chunks of an M tile on one XCD
             prev = {k: L.vqseg_set_option(k.encode(), v) for k, v in opts.items()}
             y = torch.full((n, h, w, cout), float("nan"), dtype=torch.bfloat16, device=dev())
+            L.vqseg_set_option(b"conv_last_variant", 0)
             rc = L.vqseg_conv2d_f(x.data_ptr(), None, cin, hi.data_ptr(), None, y.data_ptr(), None, n, h, w, cin, cout, 1, 1, 1, 0, 0, 1, h, w, 0, st)
+            ids.append(L.vqseg_set_option(b"conv_last_variant", 0))
             for k, v in prev.items():
                 L.vqseg_set_option(k.encode(), v)
             assert rc == 0, L.vqseg_last_error()
             outs.append(y)
+        # <128, 128, 4, NBUF, 4 waves/SIMD> with the linear-pixel prologue (flag 4): two buffers (0x1144244) for one K stage by default
+        # and for all of these under conv_short_k_small_tile = 8, else the single buffer (0x1144144); flag 1: the XCD-pair grid,
+        # which layers of 2..conv_xcd_pair Cout chunks take
+        default = 0x1144244 if cin == 64 else 0x1144144
+        pair = 1 if cout > 128 else 0
+        assert ids == [default | pair, 0x1144144 | pair, 0x1144244 | pair, default, default | pair], [hex(i) for i in ids]
         torch.cuda.synchronize()
         ref = (x.float().reshape(-1, cin) @ wt.reshape(cout, cin).bfloat16().float().t()).reshape(n, h, w, cout)
         assert rel(outs[0].float(), ref) < 2 ** -7
@@ -940,9 +1233,11 @@ def test_conv3x3_patch_kernel_256_channel_tile(case):
         try:
             y = torch.full((n, h, w, cout), float("nan"), dtype=torch.bfloat16, device=dev())
             stat = torch.full((slots, 2, cout), float("nan"), dtype=torch.float32, device=dev())
+            L.vqseg_set_option(b"conv_last_variant", 0)
             rc = L.vqseg_conv2d_f(xa.data_ptr(), None, cin, hi.data_ptr(), None, y.data_ptr(), stat.data_ptr(), n, h, w, cin, cout, 3, 3, 1, 1,
                                   int(reflect), 1, h, w, 0, st)
             assert rc == 0, L.vqseg_last_error()
+            assert L.vqseg_set_option(b"conv_last_variant", 0) == (0x3182200 if wide else 0x3143210)     # <256, 2, false> / <128, 3, true>
             torch.cuda.synchronize()
             res[wide] = (y.cpu(), stat.cpu())
         finally:

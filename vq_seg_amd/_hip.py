@@ -33,6 +33,7 @@ SYMBOLS = {
     "vqseg_conv_profile_collect": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqseg_vq_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "vqseg_vq_filter_counter_offset": (c_size_t, [c_int64, c_int, c_int]),
+    "vqseg_vq_tiles_per_wave": (c_int, [c_int, c_void_p, c_void_p]),
     "vqseg_vq_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vqseg_vq_forward_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p,
@@ -371,6 +372,18 @@ def set_option(key: str, value: int) -> int:
     if prev < 0:
         raise HipLibraryError(f"vqseg_set_option: unknown option {key!r} or bad value {value}")
     return prev
+
+
+def vq_tiles_per_wave(n_rows, n_codes) -> int:
+    """vqseg_vq_tiles_per_wave: the code tiles per wave the distance launch of these levels (one int each, or sequences) takes"""
+    rows = [n_rows] if isinstance(n_rows, int) else list(n_rows)
+    codes = [n_codes] if isinstance(n_codes, int) else list(n_codes)
+    if len(rows) != len(codes):
+        raise ValueError("vq_tiles_per_wave: one code count per row count")
+    t = lib().vqseg_vq_tiles_per_wave(len(rows), (ctypes.c_int64 * len(rows))(*rows), (c_int * len(codes))(*codes))
+    if t < 0:
+        raise _failed(lib(), "vqseg_vq_tiles_per_wave", t)
+    return t
 
 
 def vq_assign(rows: torch.Tensor, codebook: torch.Tensor, want_dmin: bool = False,

@@ -30,6 +30,7 @@ static const Option CONV_OPTIONS[] = {
     {"conv3x3_patch_tile512_min_workgroups", &g_conv_opt.patch_tile512_min_wgs},
     {"conv3x3_patch_wide_tile_s3", &g_conv_opt.patch_wide_s3, OPT_FLAG},
     {"conv3x3_patch_wide_tile", &g_conv_opt.patch_wide, OPT_FLAG},
+    {"conv_last_variant", &g_conv_opt.last_variant},                          // returns the id (conv_internal.h), then sets it to `value`
 };
 
 int conv_set_option(const char* key, int value) { return apply_option(CONV_OPTIONS, key, value); }

@@ -641,11 +641,13 @@ static void launch_glds_lin(const ConvArgs& a, hipStream_t st) {
         b.pair_chunks = chunks;
         b.pair_tiles = (int)m_tiles;
         const dim3 grid1((unsigned)((m_tiles + 7) / 8 * 8 * chunks));
+        g_conv_opt.last_variant = conv_variant_glds(TBM, BN, NW, NBUF, MINW, a.out_s3, LIN, false, true);
         if (a.out_s3) hipLaunchKernelGGL((conv_igemm_glds_kernel<TBM, BN, NW, NBUF, MINW, true, LIN>), grid1, dim3(NW * 64), lds, st, b);
         else hipLaunchKernelGGL((conv_igemm_glds_kernel<TBM, BN, NW, NBUF, MINW, false, LIN>), grid1, dim3(NW * 64), lds, st, b);
         return;
     }
     dim3 grid((unsigned)m_tiles, (unsigned)chunks);
+    g_conv_opt.last_variant = conv_variant_glds(TBM, BN, NW, NBUF, MINW, a.out_s3, LIN, false, false);
     if (a.out_s3) hipLaunchKernelGGL((conv_igemm_glds_kernel<TBM, BN, NW, NBUF, MINW, true, LIN>), grid, dim3(NW * 64), lds, st, a);
     else hipLaunchKernelGGL((conv_igemm_glds_kernel<TBM, BN, NW, NBUF, MINW, false, LIN>), grid, dim3(NW * 64), lds, st, a);
 }
@@ -669,6 +671,7 @@ static void launch_t(const ConvArgs& a, hipStream_t st) {
     if (out_tile > lds) lds = out_tile;
     const long M = (long)a.N * a.Ho * a.Wo;
     dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((a.Cout + BN - 1) / BN));
+    g_conv_opt.last_variant = conv_variant_igemm(BN, PRECISE, BK, !PRECISE && a.out_s3);
     if constexpr (!PRECISE) {
         if (a.out_s3) {
             const size_t s3_tile = (size_t)BM * (BN + 8) * 2 * 2;
@@ -888,12 +891,15 @@ hipError_t launch_dgrad_s2_fold(const void* gy, const unsigned short* w_hi, void
     const dim3 grid(tiles, (unsigned)((Cin + bn - 1) / bn));
     if (bn == 128 && 4 * (Cout / 64) <= g_conv_opt.short_k_single) {   // K loops of a few stages: epilogue-bound -- single buffer, four workgroups per CU
         const size_t lds = (size_t)128 * (128 + 8) * 2;       // (the output tile is the larger of the two uses)
+        g_conv_opt.last_variant = conv_variant_glds(128, 128, 4, 1, SHORTK_MINW, false, false, true, false);
         hipLaunchKernelGGL((conv_igemm_glds_kernel<128, 128, 4, 1, SHORTK_MINW, false, false, true>), grid, dim3(256), lds, st, a);
     } else if (bn == 128) {
         const size_t lds = (size_t)(128 + 128) * 64 * 2 * 2;
+        g_conv_opt.last_variant = conv_variant_glds(128, 128, 4, 2, 1, false, false, true, false);
         hipLaunchKernelGGL((conv_igemm_glds_kernel<128, 128, 4, 2, 1, false, false, true>), grid, dim3(256), lds, st, a);
     } else {
         const size_t lds = (size_t)(128 + 64) * 64 * 2 * 3;
+        g_conv_opt.last_variant = conv_variant_glds(128, 64, 4, 3, 1, false, false, true, false);
         hipLaunchKernelGGL((conv_igemm_glds_kernel<128, 64, 4, 3, 1, false, false, true>), grid, dim3(256), lds, st, a);
     }
     hipError_t e = hipGetLastError();

@@ -30,8 +30,35 @@ struct ConvOptions {
     int wgrad3x3_s2 = 1;                // stride-2 3x3 weight gradients on the nine-tap kernel (0: the per-tap kernel, r3)
     int stem_fused = 1;                 // the stem without its patch matrix (0: callers keep the patch-matrix path)
     int dgrad_s2_merge = 1;             // stride-2 3x3 data gradients: one launch, unpadded output (0: four launches + fold / crop)
+    int last_variant = 0;               // id of the instantiation the last convolution / weight-gradient launch took (conv_variant_*; tests read it to see the dispatch)
 };
 extern ConvOptions g_conv_opt;
+
+// Instantiation ids ("conv_last_variant"): one hexadecimal digit per template argument that selects different code, the kernel
+// family in the top digit, so that two instantiations never share an id and an id reads back as its arguments:
+//   0x1 T B W U M f   conv_igemm_glds_kernel<TBM, BN, NW, NBUF, MINW, S3, LIN, CLS>: T = TBM / 128, B = BN / 32, W = NW, U = NBUF, M = MINW,
+//                     f = S3 * 8 + LIN * 4 + CLS * 2 + (the 1-D XCD-pair grid ? 1 : 0)
+//   0x2 0 B 0 K P f   conv_igemm_kernel<BN, PRECISE, BK, S3>: B = BN / 32, K = BK / 32, P = PRECISE, f = S3 * 8
+//   0x3 T B W K U f   conv3x3_patch_kernel<BN, NBW, UNROLL_TAPS, CK, S3, TBM>: T = TBM / 256, B = BN / 32, W = NBW, K = CK / 32, U = UNROLL_TAPS,
+//                     f = S3 * 8 + (the 1-D XCD-pair grid ? 1 : 0)
+//   0x4 0 O I S 0 f   conv_wgrad3x3_kernel<COT, CIT, S>: O = COT, I = CIT, S = stride, f = (the XCD-aware 1-D grid ? 1 : 0)
+//   0x5 0 O I 0 0 f   conv_wgrad1x1_kernel<COT, CIT>: the same digits
+//   0x6 0 M N 0 P 0   conv_wgrad_kernel<TM, TN, PRECISE> (per tap): M = TM, N = TN, P = PRECISE
+// e.g. 0x1248314: the eight-wave 256 x 128 tile, three buffers, linear-pixel prologue, 2-D grid.
+enum ConvFamily { CONV_FAM_GLDS = 1, CONV_FAM_IGEMM = 2, CONV_FAM_PATCH = 3, CONV_FAM_WGRAD3X3 = 4, CONV_FAM_WGRAD1X1 = 5, CONV_FAM_WGRAD_TAP = 6 };
+constexpr int conv_variant_id(int family, int d5, int d4, int d3, int d2, int d1, int flags) {
+    return family << 24 | d5 << 20 | d4 << 16 | d3 << 12 | d2 << 8 | d1 << 4 | flags;
+}
+constexpr int conv_variant_glds(int tbm, int bn, int nw, int nbuf, int minw, bool s3, bool lin, bool cls, bool pair) {
+    return conv_variant_id(CONV_FAM_GLDS, tbm / 128, bn / 32, nw, nbuf, minw, s3 * 8 + lin * 4 + cls * 2 + pair);
+}
+constexpr int conv_variant_igemm(int bn, bool precise, int bk, bool s3) { return conv_variant_id(CONV_FAM_IGEMM, 0, bn / 32, 0, bk / 32, precise, s3 * 8); }
+constexpr int conv_variant_patch(int bn, int nbw, bool unroll, int ck, bool s3, int tbm, bool pair) {
+    return conv_variant_id(CONV_FAM_PATCH, tbm / 256, bn / 32, nbw, ck / 32, unroll, s3 * 8 + pair);
+}
+constexpr int conv_variant_wgrad3x3(int cot, int cit, int stride, bool xcd) { return conv_variant_id(CONV_FAM_WGRAD3X3, 0, cot, cit, stride, 0, xcd); }
+constexpr int conv_variant_wgrad1x1(int cot, int cit, bool xcd) { return conv_variant_id(CONV_FAM_WGRAD1X1, 0, cot, cit, 0, 0, xcd); }
+constexpr int conv_variant_wgrad_tap(int tm, int tn, bool precise) { return conv_variant_id(CONV_FAM_WGRAD_TAP, 0, tm, tn, 0, precise, 0); }
 
 // One record of the convolution profile (bench.py's roofline_conv leg) around the launches of the enclosing block: when
 // recording is on and a slot is free it files flops / kind / shape[4] and records the start event on `st`; the end event

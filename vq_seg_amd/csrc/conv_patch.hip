@@ -298,11 +298,13 @@ static void launch_patch_t(const ConvArgs& a, hipStream_t st) {
         b.pair_chunks = chunks;
         b.pair_tiles = (int)tiles;
         const dim3 grid1((unsigned)((tiles + 7) / 8 * 8 * chunks));
+        g_conv_opt.last_variant = conv_variant_patch(BN, NBW, UNROLL_TAPS, CK, a.out_s3, TBM, true);
         if (a.out_s3) hipLaunchKernelGGL((conv3x3_patch_kernel<BN, NBW, UNROLL_TAPS, CK, true, TBM>), grid1, dim3(512), lds, st, b);
         else hipLaunchKernelGGL((conv3x3_patch_kernel<BN, NBW, UNROLL_TAPS, CK, false, TBM>), grid1, dim3(512), lds, st, b);
         return;
     }
     dim3 grid((unsigned)tiles, (unsigned)chunks);
+    g_conv_opt.last_variant = conv_variant_patch(BN, NBW, UNROLL_TAPS, CK, a.out_s3, TBM, false);
     if (a.out_s3) hipLaunchKernelGGL((conv3x3_patch_kernel<BN, NBW, UNROLL_TAPS, CK, true, TBM>), grid, dim3(512), lds, st, a);
     else hipLaunchKernelGGL((conv3x3_patch_kernel<BN, NBW, UNROLL_TAPS, CK, false, TBM>), grid, dim3(512), lds, st, a);
 }

@@ -787,11 +787,13 @@ static void wgrad1x1_launch_t(const WgradArgs& a, const Wg1Plan& pl, hipStream_t
     if (g_conv_opt.wgrad_xcd && tiles > 1 && pl.slabs >= 8) {
         WgradArgs b = a;
         b.xcd_slabs = pl.slabs;
+        g_conv_opt.last_variant = conv_variant_wgrad1x1(COT, CIT, true);
         hipLaunchKernelGGL((conv_wgrad1x1_kernel<COT, CIT>), dim3(8u * tiles * (unsigned)((pl.slabs + 7) / 8)), dim3(C::NW * 64), (size_t)C::NBUF * C::STAGE, st,
                            b, pl.stages_per_slab);
         return;
     }
     dim3 grid((unsigned)(a.Cin / (32 * CIT)), (unsigned)(a.Cout / (32 * COT)), (unsigned)pl.slabs);
+    g_conv_opt.last_variant = conv_variant_wgrad1x1(COT, CIT, false);
     hipLaunchKernelGGL((conv_wgrad1x1_kernel<COT, CIT>), grid, dim3(C::NW * 64), (size_t)C::NBUF * C::STAGE, st, a, pl.stages_per_slab);
 }
 
@@ -859,11 +861,13 @@ static void wgrad3x3_launch_t(const WgradArgs& a, const Wg3Plan& pl, hipStream_t
     if (g_conv_opt.wgrad_xcd && tiles > 1 && pl.slabs >= 8) {
         WgradArgs b = a;
         b.xcd_slabs = pl.slabs;
+        g_conv_opt.last_variant = conv_variant_wgrad3x3(COT, CIT, S, true);
         hipLaunchKernelGGL((conv_wgrad3x3_kernel<COT, CIT, S>), dim3(8u * tiles * (unsigned)((pl.slabs + 7) / 8)), dim3(C::NW * 64), (size_t)C::NBUF * C::STAGE,
                            st, b, pl.blocks_per_slab);
         return;
     }
     dim3 grid((unsigned)(a.Cin / (32 * CIT)), (unsigned)(a.Cout / (32 * COT)), (unsigned)pl.slabs);
+    g_conv_opt.last_variant = conv_variant_wgrad3x3(COT, CIT, S, false);
     hipLaunchKernelGGL((conv_wgrad3x3_kernel<COT, CIT, S>), grid, dim3(C::NW * 64), (size_t)C::NBUF * C::STAGE, st, a, pl.blocks_per_slab);
 }
 
@@ -873,6 +877,7 @@ static void wgrad_launch_t(const WgradArgs& a, int slabs, hipStream_t st) {
     const size_t lds = (size_t)32 * (GS + AS) * 2 * (PRECISE ? 2 : 1);
     dim3 grid((unsigned)(a.KH * a.KW * ((a.Cin + TN * 32 - 1) / (TN * 32))), (unsigned)((a.Cout + TM * 32 - 1) / (TM * 32)),
               (unsigned)slabs);
+    g_conv_opt.last_variant = conv_variant_wgrad_tap(TM, TN, PRECISE);
     hipLaunchKernelGGL((conv_wgrad_kernel<TM, TN, PRECISE>), grid, dim3(256), lds, st, a);
 }
 

@@ -76,6 +76,13 @@ size_t vqseg_vq_filter_counter_offset(int64_t n, int c, int k) {
     return p.off_amb == p.off_summary ? 0 : p.off_amb;          // 0: the shape does not take the candidate filter
 }
 
+int vqseg_vq_tiles_per_wave(int n_levels, const int64_t* n_rows_host, const int* n_codes_host) {
+    if (n_levels < 1 || n_levels > vqseg::VQ_MAX_LEVELS || !n_rows_host || !n_codes_host) return fail(VQSEG_EINVAL, "tiles_per_wave: bad argument");
+    for (int i = 0; i < n_levels; ++i)
+        if (n_rows_host[i] <= 0 || n_codes_host[i] <= 0) return fail(VQSEG_EINVAL, "tiles_per_wave: non-positive size");
+    return vqseg::vq_group_tiles(n_levels, n_rows_host, n_codes_host);
+}
+
 size_t vqseg_vq_prepared_bytes(int c, int k) {
     if (c <= 0 || k <= 0) return 0;
     return vqseg::prepared_bytes(c, k);

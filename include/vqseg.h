@@ -192,7 +192,8 @@ int vqseg_vq_backward_f32(const float* grad_quant, const float* grad_loss, const
  * exact float and all arithmetic (distances, argmin, straight-through value, commitment) is the fp32 arithmetic of the
  * f32 entry points, so the indices are identical to those of the up-cast rows; quant is rounded to bf16 on store.
  * Backward re-reads e = codebook[idx] in fp32 (the bf16 quant would cost the commitment gradient its accuracy):
- *   grad_x = grad_quant + (2 w grad_loss / (n c)) (x - e). */
+ *   grad_x = grad_quant + (2 w grad_loss / (n c)) (x - e).
+ * Precondition: every idx[i] lies in [0, n_codes) -- what a forward returns; it addresses the codebook unchecked. */
 int vqseg_vq_forward_bf16(const void* x, const float* codebook, const void* prepared, int64_t n_rows, int channels,
                           int n_codes, int training, float commitment_weight, void* quant, int64_t* idx, float* loss,
                           float* dead_pct, float* dmin, void* workspace, size_t workspace_bytes, void* stream);
@@ -236,6 +237,7 @@ int vqseg_kmeans_finalize_f32(const float* sums, const int64_t* counts, float* m
  *                            forward returned (no second distance pass); rows f32 or bf16; deterministic (the k-means
  *                            member-list reduction).  workspace: vqseg_kmeans_workspace_bytes(n_rows, channels, n_codes).
  *                            Data-parallel use: all-reduce sums and counts (RCCL) before the update.
+ *                            Precondition: every idx[i] lies in [0, n_codes); it addresses the histograms unchecked.
  *   vqseg_vq_ema_update_f32: cluster_size <- d cluster_size + (1-d) counts;  embed_avg <- d embed_avg + (1-d) sums;
  *                            codebook <- embed_avg / ((cluster_size + eps) / (S + K eps) * S),  S = sum cluster_size.
  *                            scratch: 1 float on the device.

@@ -241,12 +241,40 @@ int vqseg_kmeans_finalize_f32(const float* sums, const int64_t* counts, float* m
  *   vqseg_vq_ema_update_f32: cluster_size <- d cluster_size + (1-d) counts;  embed_avg <- d embed_avg + (1-d) sums;
  *                            codebook <- embed_avg / ((cluster_size + eps) / (S + K eps) * S),  S = sum cluster_size.
  *                            scratch: 1 float on the device.
+ *
+ * Dead-code revival (opt-in on top of the EMA rule; that library never ships the EMA rule without it: its
+ * `threshold_ema_dead_code`.  No copy of it exists to compare with, so the rule below IS the specification; parity unpinned,
+ * like the EMA rule itself).  After the update above, on the state it has just written, with tau = threshold:
+ *     expired[k] = cluster_size[k] < tau                      (the UPDATED moving count, before any reset)
+ *     for expired k whose candidate row s_k is entirely finite:
+ *         codebook[k] = s_k;   embed_avg[k] = s_k * tau (one fp32 multiply);   cluster_size[k] = tau
+ *     every other code keeps exactly what vqseg_vq_ema_update_f32 writes; S sums the updated counts BEFORE any reset.
+ *   The candidate is a pure function of (seed, t, k), t = the number of EMA updates of this codebook so far -- no generator, no state.
+ *   With M = 2^64:
+ *     x = (seed + 0x9E3779B97F4A7C15 * (t * 2^32 + k + 1)) mod M              (splitmix64 at counter t * 2^32 + k + 1)
+ *     x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) mod M;   x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) mod M;   h = x ^ (x >> 31)
+ *     g = h mod (world * n_rows);   owner = g / n_rows;   j = g mod n_rows;   s_k = float32(rows of rank `owner`[j])
+ *   (every rank holds n_rows rows; world = 1, rank = 0 without data parallelism).  Two ranks on two shards revive what one process
+ *   on the concatenated shards revives.
+ *   vqseg_vq_revive_candidates:     cand[k][c] (f32) = the row if this rank is its owner, bit for bit (bf16 widened), else zeros;
+ *                                   ok[k] (f32) = 1 if this rank owns code k's candidate and the row is entirely finite, else 0.  One
+ *                                   launch; t is read from `counter` on the device.  Data-parallel use: all-reduce cand and ok together
+ *                                   with the code sums (one message).  rows f32 (channels % 4 == 0) or bf16 (channels % 8 == 0).
+ *   vqseg_vq_ema_update_revive_f32: vqseg_vq_ema_update_f32 (same operations in the same order, same reduction tree for S) with the
+ *                                   expiry fused in: two launches.  Writes the number of revived codes to `revived` and increments
+ *                                   *counter; both stay on the device.  scratch: 1 + n_codes floats on the device.
  * ---------------------------------------------------------------------------------- */
 int vqseg_vq_code_sums(int bf16, const void* x, const int64_t* idx, int64_t n_rows, int channels, int n_codes,
                        float* sums, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 int vqseg_vq_ema_update_f32(float* cluster_size, float* embed_avg, float* codebook, const float* sums,
                             const int64_t* counts, int channels, int n_codes, float decay, float eps, float* scratch,
                             void* stream);
+int vqseg_vq_revive_candidates(int bf16, const void* x, int64_t n_rows, int channels, int n_codes, uint64_t seed,
+                               const int64_t* counter, int rank, int world, float* cand, float* ok, void* stream);
+int vqseg_vq_ema_update_revive_f32(float* cluster_size, float* embed_avg, float* codebook, const float* sums,
+                                   const int64_t* counts, int channels, int n_codes, float decay, float eps, float* scratch,
+                                   const float* cand, const float* ok, float threshold, int64_t* counter, int64_t* revived,
+                                   void* stream);
 
 /* ================================================================================== *
  * Encoder / decoder blocks.  Tensors are NHWC rows; `precise` = 1: activations fp32, bf16x3

@@ -57,6 +57,10 @@ SYMBOLS = {
     "vqseg_vq_code_sums": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vqseg_vq_ema_update_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p,
                                         c_void_p]),
+    "vqseg_vq_revive_candidates": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, ctypes.c_uint64, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                           c_void_p]),
+    "vqseg_vq_ema_update_revive_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p,
+                                               c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "vqseg_conv_packed_elems": (c_size_t, [c_int] * 5),
     "vqseg_conv_pack_weights_f32": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p]),
     "vqseg_conv_stat_slots": (c_int64, [c_int64, c_int]),
@@ -467,33 +471,62 @@ def kmeans_finalize(sums: torch.Tensor, counts: torch.Tensor, means: torch.Tenso
     return means
 
 
-def vq_code_sums(rows: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Per-code sums (K, C) f32 and counts (K,) i64 of rows (N, C) f32 / bf16 under the assignment idx (N,) i64."""
+def vq_code_sums(rows: torch.Tensor, idx: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-code sums (K, C) f32 and counts (K,) i64 of rows (N, C) f32 / bf16 under the assignment idx (N,) i64.  `out`: the tensor the
+    sums are written to (a dense (K, C) f32 view of a larger buffer, say)."""
     L = lib()
     n, c = rows.shape
     if rows.dtype not in (torch.float32, torch.bfloat16):
         raise HipLibraryError(f"rows: expected torch.float32 or torch.bfloat16, got {rows.dtype}")
     ip = _dev(idx, torch.int64, "idx", n)
-    sums = torch.empty(k, c, dtype=torch.float32, device=rows.device)
+    sums = torch.empty(k, c, dtype=torch.float32, device=rows.device) if out is None else out
     counts = torch.empty(k, dtype=torch.int64, device=rows.device)
     nbytes = L.vqseg_kmeans_workspace_bytes(n, c, k)
     ws = _workspace(nbytes, rows.device)
     bf = int(rows.dtype == torch.bfloat16)
-    launch("vqseg_vq_code_sums", rows.device, bf, tptr(rows, "rows", bf=bf, numel=n * c), ip, n, c, k, sums.data_ptr(), counts.data_ptr(),
-           ws.data_ptr(), nbytes)
+    launch("vqseg_vq_code_sums", rows.device, bf, tptr(rows, "rows", bf=bf, numel=n * c), ip, n, c, k,
+           sums.data_ptr() if out is None else _dev(out, torch.float32, "out", k * c), counts.data_ptr(), ws.data_ptr(), nbytes)
     return sums, counts
 
 
+def vq_revive_candidates(rows: torch.Tensor, seed: int, counter: torch.Tensor, k: int, rank: int, world: int, out=None):
+    """The rows of this rank that expired codes would take (include/vqseg.h: vqseg_vq_revive_candidates): -> cand (K, C) f32, ok (K,) f32.
+    `counter`: the device int64 count of EMA updates so far (read on the device); `out`: a (cand, ok) pair to write into."""
+    n, c = rows.shape
+    if rows.dtype not in (torch.float32, torch.bfloat16):
+        raise HipLibraryError(f"rows: expected torch.float32 or torch.bfloat16, got {rows.dtype}")
+    bf = int(rows.dtype == torch.bfloat16)
+    xp, tp = tptr(rows, "rows", bf=bf, numel=n * c), _dev(counter, torch.int64, "counter", 1)
+    if out is None:
+        out = (torch.empty(k, c, dtype=torch.float32, device=rows.device), torch.empty(k, dtype=torch.float32, device=rows.device))
+    cand, ok = out
+    launch("vqseg_vq_revive_candidates", rows.device, bf, xp, n, c, k, int(seed) & 0xFFFFFFFFFFFFFFFF, tp, int(rank), int(world),
+           _dev(cand, torch.float32, "candidates", k * c), _dev(ok, torch.float32, "ok", k))
+    return cand, ok
+
+
 def vq_ema_update(cluster_size: torch.Tensor, embed_avg: torch.Tensor, codebook: torch.Tensor, sums: torch.Tensor,
-                  counts: torch.Tensor, decay: float, eps: float) -> None:
-    """In place: moving counts / sums and the codebook they imply (include/vqseg.h: vqseg_vq_ema_update_f32)."""
+                  counts: torch.Tensor, decay: float, eps: float, candidates: Optional[torch.Tensor] = None,
+                  ok: Optional[torch.Tensor] = None, threshold: float = 0.0, counter: Optional[torch.Tensor] = None,
+                  revived: Optional[torch.Tensor] = None) -> None:
+    """In place: moving counts / sums and the codebook they imply (include/vqseg.h: vqseg_vq_ema_update_f32).  With `threshold` > 0 the
+    dead-code revival is fused in (vqseg_vq_ema_update_revive_f32): codes whose updated count lies below it take their row of
+    `candidates` where `ok` is set, `revived` (device int64) receives their number and `counter` (device int64) advances by one."""
     k, c = codebook.shape
     if cluster_size.shape != (k,) or embed_avg.shape != (k, c) or sums.shape != (k, c) or counts.shape != (k,):
         raise ValueError("vq_ema_update: shapes must be (K,), (K, C), (K, C), (K, C), (K,)")
-    scratch = torch.empty(1, dtype=torch.float32, device=codebook.device)
-    launch("vqseg_vq_ema_update_f32", codebook.device, _dev(cluster_size, torch.float32, "cluster_size"),
+    if threshold == 0:
+        scratch = torch.empty(1, dtype=torch.float32, device=codebook.device)
+        launch("vqseg_vq_ema_update_f32", codebook.device, _dev(cluster_size, torch.float32, "cluster_size"),
+               _dev(embed_avg, torch.float32, "embed_avg"), _dev(codebook, torch.float32, "codebook"), _dev(sums, torch.float32, "sums"),
+               _dev(counts, torch.int64, "counts"), c, k, float(decay), float(eps), scratch.data_ptr())
+        return
+    scratch = torch.empty(1 + k, dtype=torch.float32, device=codebook.device)
+    launch("vqseg_vq_ema_update_revive_f32", codebook.device, _dev(cluster_size, torch.float32, "cluster_size"),
            _dev(embed_avg, torch.float32, "embed_avg"), _dev(codebook, torch.float32, "codebook"), _dev(sums, torch.float32, "sums"),
-           _dev(counts, torch.int64, "counts"), c, k, float(decay), float(eps), scratch.data_ptr())
+           _dev(counts, torch.int64, "counts"), c, k, float(decay), float(eps), scratch.data_ptr(),
+           _dev(candidates, torch.float32, "candidates", k * c), _dev(ok, torch.float32, "ok", k), float(threshold),
+           _dev(counter, torch.int64, "counter", 1), _dev(revived, torch.int64, "revived", 1))
 
 
 def batch_u8(img_cache: torch.Tensor, img_offsets, hw: Tuple[int, int], f32_lut: torch.Tensor, img_out: torch.Tensor,

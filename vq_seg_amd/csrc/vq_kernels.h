@@ -129,6 +129,13 @@ hipError_t launch_code_sums(const void* x, int x_bf16, const int64_t* idx, int64
                             float* sums, int64_t* counts64, hipStream_t st);
 hipError_t launch_ema_update(float* cluster_size, float* embed_avg, float* codebook, const float* sums, const int64_t* counts64,
                              int K, int C, float decay, float eps, float* total, hipStream_t st);
+// dead-code revival (include/vqseg.h, EMA EXTENSION): the candidate rows of this rank, and the EMA update with the expiry fused in
+// (scratch: 1 + K floats)
+hipError_t launch_revive_candidates(const void* x, int x_bf16, int64_t N, int C, int K, uint64_t seed, const int64_t* t, int rank,
+                                    int world, float* cand, float* ok, hipStream_t st);
+hipError_t launch_ema_update_revive(float* cluster_size, float* embed_avg, float* codebook, const float* sums, const int64_t* counts64,
+                                    int K, int C, float decay, float eps, float* scratch, const float* cand, const float* ok,
+                                    float threshold, int64_t* t, int64_t* revived, hipStream_t st);
 hipError_t launch_km_finalize(const float* sums, const int64_t* counts64, float* means, int C, int K, hipStream_t st);
 
 }  // namespace vqseg

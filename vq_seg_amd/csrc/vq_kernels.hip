@@ -1324,6 +1324,119 @@ __global__ __launch_bounds__(256) void ema_embed_kernel(float* __restrict__ embe
     codebook[o] = avg / smoothed;
 }
 
+// ---- dead-code revival, the companion of the EMA rule in the same library (EXTENSION, include/vqseg.h): a code whose UPDATED
+// moving count lies below the threshold takes a row of the current batch.  Which row is a pure function of (seed, t, k):
+// splitmix64 at counter t * 2^32 + k + 1, reduced modulo world * N; nothing is drawn from a generator and nothing is kept.
+__device__ __forceinline__ unsigned long long revive_hash(unsigned long long seed, unsigned long long t, unsigned k) {
+    unsigned long long x = seed + 0x9E3779B97F4A7C15ull * ((t << 32) + (unsigned long long)k + 1ull);
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ bool finite_bits(unsigned u) { return (u & 0x7F800000u) != 0x7F800000u; }
+
+template <typename TS>
+__global__ __launch_bounds__(256) void revive_candidates_kernel(const TS* __restrict__ rows, long N, int C, unsigned long long seed,
+                                                                const long long* __restrict__ t, int rank, int world,
+                                                                float* __restrict__ cand, float* __restrict__ ok) {
+    // block = code k: its candidate row (16-byte loads, float4 stores) if this rank holds it, zeros if another rank does -- the sum over
+    // ranks (the all-reduce the code sums travel in) is then the row itself
+    const int k = blockIdx.x;
+    const unsigned long long g = revive_hash(seed, (unsigned long long)*t, (unsigned)k) % ((unsigned long long)world * (unsigned long long)N);
+    const unsigned long long NN = (unsigned long long)N;
+    const bool mine = g / NN == (unsigned long long)rank;
+    const size_t j = (size_t)(g % NN);
+    float4* __restrict__ out = reinterpret_cast<float4*>(cand + (size_t)k * C);
+    __shared__ int bad;
+    if (threadIdx.x == 0) bad = 0;
+    __syncthreads();
+    if (!mine) {
+        for (int q = threadIdx.x; q < C / 4; q += 256) out[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (threadIdx.x == 0) ok[k] = 0.0f;
+        return;
+    }
+    bool nonfinite = false;
+    if constexpr (sizeof(TS) == 4) {
+        const uint4* __restrict__ in = reinterpret_cast<const uint4*>(rows + j * C);
+        for (int q = threadIdx.x; q < C / 4; q += 256) {
+            const uint4 v = in[q];
+            nonfinite |= !(finite_bits(v.x) && finite_bits(v.y) && finite_bits(v.z) && finite_bits(v.w));
+            out[q] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        }
+    } else {
+        const uint4* __restrict__ in = reinterpret_cast<const uint4*>(rows + j * C);      // 8 bf16: float32 = the bits << 16, exactly
+        for (int q = threadIdx.x; q < C / 8; q += 256) {
+            const uint4 v = in[q];
+            const unsigned w[8] = {v.x << 16, v.x & 0xFFFF0000u, v.y << 16, v.y & 0xFFFF0000u,
+                                   v.z << 16, v.z & 0xFFFF0000u, v.w << 16, v.w & 0xFFFF0000u};
+            for (int i = 0; i < 8; ++i) nonfinite |= !finite_bits(w[i]);
+            out[2 * q] = make_float4(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3]));
+            out[2 * q + 1] = make_float4(__uint_as_float(w[4]), __uint_as_float(w[5]), __uint_as_float(w[6]), __uint_as_float(w[7]));
+        }
+    }
+    if (nonfinite) bad = 1;                                  // every writer stores the same value
+    __syncthreads();
+    if (threadIdx.x == 0) ok[k] = bad ? 0.0f : 1.0f;
+}
+
+__global__ __launch_bounds__(256) void ema_counts_revive_kernel(float* __restrict__ cluster_size, const long long* __restrict__ counts,
+                                                                int K, float decay, float* __restrict__ total,
+                                                                const float* __restrict__ ok, float threshold, float* __restrict__ revive,
+                                                                long long* __restrict__ t, long long* __restrict__ revived) {
+    // ema_counts_kernel (same operations, same tree: *total sums the updated counts BEFORE any reset) + the expiry: revive[k] = 1 and
+    // cluster_size[k] = threshold where the updated count is below the threshold and the candidate is usable; one more update counted
+    __shared__ float sh[256];
+    __shared__ int shn[256];
+    float s = 0.0f;
+    int n = 0;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const float v = __builtin_fmaf(cluster_size[k], decay, (1.0f - decay) * (float)counts[k]);
+        const bool r = v < threshold && ok[k] > 0.0f;
+        cluster_size[k] = r ? threshold : v;
+        revive[k] = r ? 1.0f : 0.0f;
+        n += r ? 1 : 0;
+        s += v;
+    }
+    sh[threadIdx.x] = s;
+    shn[threadIdx.x] = n;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            sh[threadIdx.x] += sh[threadIdx.x + w];
+            shn[threadIdx.x] += shn[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        *total = sh[0];
+        *revived = shn[0];
+        *t = *t + 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void ema_embed_revive_kernel(float* __restrict__ embed_avg, const float* __restrict__ sums,
+                                                               const float* __restrict__ cluster_size, const float* __restrict__ total,
+                                                               float* __restrict__ codebook, int K, int C, float decay, float eps,
+                                                               const float* __restrict__ cand, const float* __restrict__ revive,
+                                                               float threshold) {
+    const int k = blockIdx.x;
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= C) return;
+    const size_t o = (size_t)k * C + c;
+    if (revive[k] > 0.0f) {                                  // uniform over the block
+        const float s = cand[o];
+        embed_avg[o] = s * threshold;
+        codebook[o] = s;
+        return;
+    }
+    const float n = *total;                                  // ema_embed_kernel from here on
+    const float smoothed = (cluster_size[k] + eps) / (n + (float)K * eps) * n;
+    const float avg = __builtin_fmaf(embed_avg[o], decay, (1.0f - decay) * sums[o]);
+    embed_avg[o] = avg;
+    codebook[o] = avg / smoothed;
+}
+
 // ------------------------------------------------------------------------------------
 // host-side launch helpers (called by the C ABI in vqseg_abi.cpp)
 // ------------------------------------------------------------------------------------
@@ -1754,6 +1867,30 @@ hipError_t launch_ema_update(float* cluster_size, float* embed_avg, float* codeb
                        decay, total);
     hipLaunchKernelGGL(ema_embed_kernel, dim3(K, (C + 255) / 256), dim3(256), 0, st, embed_avg, sums, cluster_size, total, codebook,
                        K, C, decay, eps);
+    return hipGetLastError();
+}
+
+hipError_t launch_revive_candidates(const void* x, int x_bf16, int64_t N, int C, int K, uint64_t seed, const int64_t* t, int rank,
+                                    int world, float* cand, float* ok, hipStream_t st) {
+    const long long* tp = reinterpret_cast<const long long*>(t);
+    if (x_bf16)
+        hipLaunchKernelGGL(revive_candidates_kernel<__bf16>, dim3(K), dim3(256), 0, st, static_cast<const __bf16*>(x), (long)N, C,
+                           (unsigned long long)seed, tp, rank, world, cand, ok);
+    else
+        hipLaunchKernelGGL(revive_candidates_kernel<float>, dim3(K), dim3(256), 0, st, static_cast<const float*>(x), (long)N, C,
+                           (unsigned long long)seed, tp, rank, world, cand, ok);
+    return hipGetLastError();
+}
+
+hipError_t launch_ema_update_revive(float* cluster_size, float* embed_avg, float* codebook, const float* sums, const int64_t* counts64,
+                                    int K, int C, float decay, float eps, float* scratch, const float* cand, const float* ok,
+                                    float threshold, int64_t* t, int64_t* revived, hipStream_t st) {
+    float* total = scratch;                                  // scratch: [total | revive flags K]
+    float* revive = scratch + 1;
+    hipLaunchKernelGGL(ema_counts_revive_kernel, dim3(1), dim3(256), 0, st, cluster_size, reinterpret_cast<const long long*>(counts64), K,
+                       decay, total, ok, threshold, revive, reinterpret_cast<long long*>(t), reinterpret_cast<long long*>(revived));
+    hipLaunchKernelGGL(ema_embed_revive_kernel, dim3(K, (C + 255) / 256), dim3(256), 0, st, embed_avg, sums, cluster_size, total,
+                       codebook, K, C, decay, eps, cand, revive, threshold);
     return hipGetLastError();
 }
 

@@ -257,6 +257,36 @@ int vqseg_vq_ema_update_f32(float* cluster_size, float* embed_avg, float* codebo
     return 0;
 }
 
+int vqseg_vq_revive_candidates(int bf16, const void* x, int64_t n, int c, int k, uint64_t seed, const int64_t* counter, int rank,
+                               int world, float* cand, float* ok, void* stream) {
+    if (!x || !counter || !cand || !ok) return fail(VQSEG_EINVAL, "revive candidates: null pointer argument");
+    if (n < 1 || k < 1) return fail(VQSEG_EINVAL, "revive candidates: n_rows and n_codes must be positive (got %lld, %d)", (long long)n, k);
+    if (n > (int64_t)1 << 31) return fail(VQSEG_EINVAL, "n_rows too large (%lld)", (long long)n);
+    if (world < 1) return fail(VQSEG_EINVAL, "revive candidates: world must be >= 1 (got %d)", world);
+    if (rank < 0 || rank >= world) return fail(VQSEG_EINVAL, "revive candidates: rank %d outside [0, %d)", rank, world);
+    if (c <= 0 || c % 4) return fail(VQSEG_EINVAL, "channels must be a multiple of 4 (got %d)", c);
+    if (bf16 && c % 8) return fail(VQSEG_EINVAL, "bf16 rows need channels %% 8 == 0");
+    if (!aligned16(x) || !aligned16(cand)) return fail(VQSEG_EINVAL, "rows and cand must be 16-byte aligned");
+    hipError_t e = vqseg::launch_revive_candidates(x, bf16 != 0, n, c, k, seed, counter, rank, world, cand, ok,
+                                                   static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "revive_candidates_kernel");
+    return 0;
+}
+
+int vqseg_vq_ema_update_revive_f32(float* cluster_size, float* embed_avg, float* codebook, const float* sums, const int64_t* counts,
+                                   int c, int k, float decay, float eps, float* scratch, const float* cand, const float* ok,
+                                   float threshold, int64_t* counter, int64_t* revived, void* stream) {
+    if (c <= 0 || k <= 0 || !cluster_size || !embed_avg || !codebook || !sums || !counts || !scratch)
+        return fail(VQSEG_EINVAL, "bad argument");
+    if (!cand || !ok || !counter || !revived) return fail(VQSEG_EINVAL, "ema update with revival: null pointer argument");
+    if (!(decay >= 0.0f && decay <= 1.0f) || !(eps >= 0.0f)) return fail(VQSEG_EINVAL, "need 0 <= decay <= 1, eps >= 0");
+    if (!(threshold >= 0.0f) || threshold > 3.0e38f) return fail(VQSEG_EINVAL, "need a finite threshold >= 0");
+    hipError_t e = vqseg::launch_ema_update_revive(cluster_size, embed_avg, codebook, sums, counts, k, c, decay, eps, scratch, cand, ok,
+                                                   threshold, counter, revived, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "ema_embed_revive_kernel");
+    return 0;
+}
+
 int vqseg_kmeans_finalize_f32(const float* sums, const int64_t* counts, float* means, int c, int k, void* stream) {
     if (c <= 0 || k <= 0 || !sums || !counts || !means) return fail(VQSEG_EINVAL, "bad argument");
     hipError_t e = vqseg::launch_km_finalize(sums, counts, means, c, k, static_cast<hipStream_t>(stream));

@@ -12,6 +12,9 @@ Extension (opt-in, `ema_update=True`; default False = the reference's frozen cod
 codebook update BASELINE.json's north_star names.  The reference stores `decay` / `eps` and never uses them (SURVEY 0.1);
 with the flag set they drive the published EMA rule (see include/vqseg.h, vqseg_vq_ema_update_f32) after every training
 forward, with the per-code sums / counts all-reduced over RCCL when torch.distributed runs more than one rank.
+`threshold_ema_dead_code` > 0 adds that rule's companion: a code whose moving count falls below the threshold takes a row of
+the current batch, chosen by a hash of (revive_seed, number of updates so far, code) -- on the device, identically on every rank,
+inside the same all-reduce (include/vqseg.h, vqseg_vq_revive_candidates / vqseg_vq_ema_update_revive_f32).
 """
 from __future__ import annotations
 
@@ -21,7 +24,8 @@ from torch import nn
 from .. import _hip
 from .. import nnf
 from .._wcache import cache_of as _cache_of, invalidate as _invalidate
-from ..dist import collectives_on as _collectives_on, broadcast0 as _broadcast0, all_reduce_sum as _all_reduce_sum
+from ..dist import collectives_on as _collectives_on, broadcast0 as _broadcast0, all_reduce_sum as _all_reduce_sum, rank as _rank, \
+    world_size as _world_size
 
 
 class _VQFunction(torch.autograd.Function):
@@ -184,8 +188,13 @@ def kmeans(rows: torch.Tensor, num_clusters: int, num_iters: int, init_means: to
 
 
 class EuclideanCodebook(nn.Module):
-    def __init__(self, embedding_dim, num_embeddings, kmeans_init, kmeans_iters, decay, eps, num_codebook, ema_update=False):
+    def __init__(self, embedding_dim, num_embeddings, kmeans_init, kmeans_iters, decay, eps, num_codebook, ema_update=False,
+                 threshold_ema_dead_code: float = 0.0, revive_seed: int = 0):
         super().__init__()
+        if threshold_ema_dead_code < 0:
+            raise ValueError(f"threshold_ema_dead_code must be >= 0, got {threshold_ema_dead_code}")
+        if threshold_ema_dead_code > 0 and not ema_update:
+            raise ValueError("threshold_ema_dead_code > 0 revives codes of the EMA update: it needs ema_update=True")
         self.kmeans_init = kmeans_init
         self.kmeans_iters = kmeans_iters
         self.initted = False
@@ -202,6 +211,11 @@ class EuclideanCodebook(nn.Module):
         if self.ema_update:                                  # extension state; absent from state_dict() otherwise
             self.register_buffer("cluster_size", torch.zeros(num_embeddings))
             self.register_buffer("embed_avg", self.embedding.weight.detach().clone())
+        self.threshold_ema_dead_code = float(threshold_ema_dead_code)
+        self.revive_seed = int(revive_seed)
+        self.revived = None                                  # device int64 scalar: codes the last update revived (never read on the step path)
+        if self.threshold_ema_dead_code > 0:                 # the `t` of the candidate hash; travels with the state, absent otherwise
+            self.register_buffer("ema_updates", torch.zeros((), dtype=torch.int64))
 
     def prepared(self) -> torch.Tensor:
         """Kernel-side image of the codebook (include/vqseg.h: vqseg_vq_prepare_f32), rebuilt only when the weight may have
@@ -227,11 +241,30 @@ class EuclideanCodebook(nn.Module):
     @torch.no_grad()
     def ema_step(self, rows: torch.Tensor, idx: torch.Tensor):
         """Extension: one EMA update from the rows (N, C) of this forward and their code indices."""
+        if self.threshold_ema_dead_code > 0:
+            return self._ema_revive_step(rows, idx)
         sums, counts = _hip.vq_code_sums(rows, idx.reshape(-1), self.num_embeddings)
         if _collectives_on():                                # every rank applies the same update to the same state
             _all_reduce_sum(sums)
             _all_reduce_sum(counts)
         _hip.vq_ema_update(self.cluster_size, self.embed_avg, self.embedding.weight.detach(), sums, counts, self.decay, self.eps)
+        _invalidate(self.embedding.weight)                   # the kernel wrote the weight behind autograd's back
+
+    def _ema_revive_step(self, rows: torch.Tensor, idx: torch.Tensor):
+        """ema_step with the dead-code revival: the code sums, the candidate rows and their flags share ONE flat buffer
+        [sums K*C | cand K*C | ok K], so data parallelism all-reduces one message where it all-reduced the sums."""
+        k, c = self.num_embeddings, self.embedding_dim
+        flat = torch.empty(2 * k * c + k, dtype=torch.float32, device=rows.device)
+        sums, cand, ok = flat[:k * c].view(k, c), flat[k * c:2 * k * c].view(k, c), flat[2 * k * c:]
+        _, counts = _hip.vq_code_sums(rows, idx.reshape(-1), k, out=sums)
+        _hip.vq_revive_candidates(rows, self.revive_seed, self.ema_updates, k, _rank(), _world_size(), out=(cand, ok))
+        if _collectives_on():
+            _all_reduce_sum(flat)
+            _all_reduce_sum(counts)
+        if self.revived is None or self.revived.device != rows.device:
+            self.revived = torch.zeros((), dtype=torch.int64, device=rows.device)
+        _hip.vq_ema_update(self.cluster_size, self.embed_avg, self.embedding.weight.detach(), sums, counts, self.decay, self.eps,
+                           candidates=cand, ok=ok, threshold=self.threshold_ema_dead_code, counter=self.ema_updates, revived=self.revived)
         _invalidate(self.embedding.weight)                   # the kernel wrote the weight behind autograd's back
 
     def forward(self, x: torch.Tensor):
@@ -247,7 +280,8 @@ class EuclideanCodebook(nn.Module):
 
 class VectorQuantizer(nn.Module):
     def __init__(self, dim, num_embeddings, embedding_dim=None, decay=0.8, eps=1e-5, kmeans_init=False,
-                 kmeans_iters=10, distance="euclidean", commitment_weight=1, num_codebook=1, ema_update=False):
+                 kmeans_iters=10, distance="euclidean", commitment_weight=1, num_codebook=1, ema_update=False,
+                 threshold_ema_dead_code: float = 0.0, revive_seed: int = 0):
         super().__init__()
         embedding_dim = embedding_dim if embedding_dim is not None else dim
         self.num_embeddings = num_embeddings
@@ -259,7 +293,8 @@ class VectorQuantizer(nn.Module):
                 "cosine codebook is unused by the target configs)")
         self.codebook = EuclideanCodebook(embedding_dim=embedding_dim, num_embeddings=num_embeddings,
                                           kmeans_init=kmeans_init, kmeans_iters=kmeans_iters, decay=decay, eps=eps,
-                                          num_codebook=num_codebook, ema_update=ema_update)
+                                          num_codebook=num_codebook, ema_update=ema_update,
+                                          threshold_ema_dead_code=threshold_ema_dead_code, revive_seed=revive_seed)
 
     def forward(self, x: torch.Tensor):
         """x (B, C, H, W) -> (quantize (B, C, H, W) f32 -- bf16 for bf16 input --, embed_index (B, H, W) i64, loss (1,), code_usage ())."""

@@ -609,6 +609,12 @@ int vqseg_order_stats_f(const float* x, int64_t n, int64_t k, void* workspace, s
  *   k = 1 / 3: nn.Conv2d weight [cout][cin][k][k], tiles of 32 output x 128 / 32 input channels; fwd / tr / s3 (each nullable):
  *   the images [cout][k][k][cin^32], [cin][k][k flipped][cout^32], [cout][k][k][3 cin] ([w_hi | w_hi | w_lo] per concat segment
  *   split at c1; needs cin % 32 == 0 and c1 % 32 == 0) -- bit-identical to vqseg_conv_pack_all_f32 of the updated weight.
+ * Preconditions the entry point cannot check (the tables live in device memory): p / g / m / v hold numel floats each and do not
+ * overlap (4-byte alignment is enough; a parameter whose four pointers are all 16-byte aligned takes 16-byte accesses, with
+ * bit-identical results); for k = 1 / 3 numel == cout * cin * k * k; every non-NULL image is 16-byte aligned and holds
+ * cout k k cin^32 / cin k k cout^32 / cout k k 3 cin 16-bit elements; 0 < c1 <= cin; every (parameter, tile) pair appears exactly once
+ * (a parameter with numel == 0 has no tile).  Arithmetic is IEEE float32 with subnormals (no flush to zero): NaN / Inf gradients
+ * propagate into m, v and p of their own element only.  The image outputs of the pack entry points above must be 16-byte aligned too.
  * ---------------------------------------------------------------------------------- */
 #define VQSEG_ADAM_CHUNK 4096
 typedef struct VqsegAdamParam {

@@ -47,15 +47,23 @@ def _grads(step, device):
 
 
 def test_hip_adam_matches_torch_adam_on_the_cpu_and_rewrites_the_weight_images():
+    for first in (1, 0):
+        _hip_adam_against_torch_adam(first)
+
+
+def _hip_adam_against_torch_adam(first):
     from vq_seg_amd import nnf
     from vq_seg_amd.optim import HipAdam
     cpu_p, gpu_p = _params("cpu", False), _params(dev(), True)
-    # gradient storage as the trainer's buckets hand it out: views into ONE flat buffer at offsets that are not 16-byte multiples
-    flat = torch.zeros(sum(p.numel() for p in gpu_p) + 1, device=dev())
-    off = 1
+    # gradient storage as the trainer's buckets hand it out: views into ONE flat buffer.  first = 1: at offsets that are not 16-byte
+    # multiples (the scalar body of adam_flat_chunk); first = 0: every offset rounded up to 4 floats (its 16-byte vector body)
+    flat = torch.zeros(sum((p.numel() + 3) // 4 * 4 for p in gpu_p) + 1, device=dev())
+    off = first
     for p in gpu_p:
         p.grad = flat[off:off + p.numel()].view_as(p)
-        off += p.numel()
+        off += p.numel() if first else (p.numel() + 3) // 4 * 4
+    aligned = [p.grad.data_ptr() % 16 == 0 for p in gpu_p]
+    assert all(aligned) if first == 0 else not all(aligned)
     ref = torch.optim.Adam(cpu_p, lr=3e-3, betas=(0.9, 0.999), foreach=False, fused=False)
     opt = HipAdam(gpu_p, lr=3e-3, betas=(0.9, 0.999))
     for step in range(6):
@@ -74,6 +82,8 @@ def test_hip_adam_matches_torch_adam_on_the_cpu_and_rewrites_the_weight_images()
                 # moments: the same fma chain -> 1e-7 of scale; parameters: 2.5e-7 (<= 3 ulp at the tensor's scale) -- ATen's vectorised
                 # CPU sqrt is not correctly rounded (its own scalar path differs from it by an ulp), the kernel's IEEE sqrt / div are
                 assert rel(a, b) <= (2.5e-7 if what == "param" else 1e-7), (step, ADAM_SHAPES[i], what, rel(a, b))
+                if what != "param":                                     # "the moments exactly" (optim_kernels.hip): bit for bit
+                    assert torch.equal(a.detach().cpu(), b.detach()), (step, ADAM_SHAPES[i], what)
             assert float(opt.state[q]["step"]) == float(ref.state[p]["step"]) == step + 1
     # the images installed by the step == a fresh pack of the updated weight, bit for bit; no pack launch is needed afterwards
     for q in gpu_p:

@@ -9,8 +9,10 @@
 //     den = sqrt(v) / sqrt(1 - b2^t) + eps                 (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
 //     p   = p + (-(lr / (1 - b1^t)) * m) / den             param.addcdiv_(exp_avg, denom, value=-step_size)
 // with the step-dependent scalars evaluated by the host in double, as torch does.  Divisions and the square root are the
-// correctly rounded IEEE ones; ATen's vectorised CPU sqrt is not (its scalar and vector paths differ from each other by an ulp), so
-// parameters agree with a CPU torch.optim.Adam to 1-2 ulp, the moments exactly (tests/test_optim_gpu.py).
+// correctly rounded IEEE ones, subnormals included: every output is reproduced bit for bit by a float32 emulation of this chain on the
+// CPU (tests/optim_cases.py::adam_emulate, tests/test_optim_parity_gpu.py).  ATen's vectorised CPU sqrt and div are not correctly
+// rounded (its scalar and vector paths differ from each other), so against a CPU torch.optim.Adam the moments agree exactly and the
+// parameters to 3 units of max(ulp(p), ulp(update)) measured over 1.2 M elements (profiles/optim_parity.md; the tests assert 6).
 //
 // What the launch adds to a plain optimiser: the convolution kernels do not read nn.Conv2d.weight, they read bf16 images of it
 // (conv_kernels.hip: forward [Cout][k][k][Cin^32], data-gradient [Cin][k][k flipped][Cout^32], split-3 [Cout][k][k][3 Cin]),
@@ -49,7 +51,9 @@ struct AdamScalars {
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamScalars& s) {
     m = __fmaf_rn(s.w1, __fsub_rn(g, m), m);
     v = __fmaf_rn(__fmul_rn(s.a2, g), g, __fmul_rn(v, s.b2));
-    const float den = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), s.bc2_sqrt), s.eps);
+    // __builtin_sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS hipcc's __fsqrt_rn is the native v_sqrt_f32 (1 ulp, not
+    // correctly rounded); the builtin is the IEEE square root (the Makefile passes no fast-math flag), as `/` is the IEEE division
+    const float den = __fadd_rn(__fdiv_rn(__builtin_sqrtf(v), s.bc2_sqrt), s.eps);
     p = __fadd_rn(p, __fdiv_rn(__fmul_rn(s.neg_step, m), den));
 }
 

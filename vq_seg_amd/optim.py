@@ -127,8 +127,9 @@ class HipAdam(torch.optim.Adam):
             beta1, beta2 = group["betas"]
             lr = group["lr"]
             lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
-            for step, idx in by_step.items():
-                sub = (gi, step) if len(by_step) > 1 else gi
+            for j, (step, idx) in enumerate(by_step.items()):
+                # keyed by position, not by step count: the count changes every step, and a key that held it built a new table each step
+                sub = (gi, j) if len(by_step) > 1 else gi
                 ps = plist if len(by_step) == 1 else [plist[i] for i in idx]
                 ms = exp_avgs if len(by_step) == 1 else [exp_avgs[i] for i in idx]
                 vs = exp_avg_sqs if len(by_step) == 1 else [exp_avg_sqs[i] for i in idx]

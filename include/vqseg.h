@@ -632,6 +632,30 @@ int64_t vqseg_adam_work_items(int64_t numel, int k, int cout, int cin);
 int vqseg_adam_step_f32(const VqsegAdamParam* params_dev, const int32_t* items_dev, int n_items, double lr, double beta1,
                         double beta2, double eps, int64_t step, void* stream);
 
+/* The same launch with an exponential moving average ("teacher") of the network kept in the same pass: ema_dev holds one
+ * VqsegEmaParam per VqsegAdamParam record, same index.  With p' the float32 parameter value this launch has just stored and
+ * w = (float)(1.0 - ema_decay) (formed in double, cast once):
+ *     average:  e' = fmaf(w, p' - e, e)      (the difference rounded once, the fma rounded once; IEEE float32 with subnormals)
+ *     copy:     e' = the stored bits of p'   (a record whose `copy` is non-zero, or every record when copy_all != 0; e is not read)
+ * and the teacher's images fwd / tr / s3 (each nullable) are written from e' in the layouts, sizes and alignment rules of the
+ * student's (k, cout, cin, c1 of the VqsegAdamParam record).  A record with e == NULL behaves exactly as under vqseg_adam_step_f32.
+ * Average-only records: under THIS entry point a record with g == NULL skips the Adam rule -- p is read only, m and v may be NULL,
+ * only e and its images are produced (BatchNorm running statistics).  Under vqseg_adam_step_f32 g == NULL stays a precondition
+ * violation.  Tiles, chunk size, item table and the other preconditions are those of vqseg_adam_step_f32; e holds numel floats and
+ * overlaps none of p / g / m / v (a flat record takes 16-byte accesses when e and the record's other pointers are all 16-byte
+ * aligned, with bit-identical results).  ema_decay must lie in [0, 1). */
+typedef struct VqsegEmaParam {
+    float* e;            /* averaged values  [numel] f32, updated in place; NULL: this record keeps no average */
+    int32_t copy;        /* non-zero: e takes the NEW p bit for bit instead of the average */
+    int32_t reserved;    /* 0 */
+    void* fwd;           /* images of e, each nullable */
+    void* tr;
+    void* s3;
+} VqsegEmaParam;
+int vqseg_adam_ema_step_f32(const VqsegAdamParam* params_dev, const VqsegEmaParam* ema_dev, const int32_t* items_dev, int n_items,
+                            double lr, double beta1, double beta2, double eps, int64_t step, double ema_decay, int copy_all,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------------- *
  * Batch assembly of the device-resident data loader (vq_seg_amd.data.DeviceLoader): the per-sample work of BaseDataset.__getitem__
  * after its decode / resize (data/dataset.py:47-57: uint8 HWC -> float32 / 255, the raw uint8 mask) and of the loop's

@@ -137,6 +137,8 @@ SYMBOLS = {
     "vqseg_s3_bilinear_f": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p]),
     "vqseg_adam_work_items": (c_int64, [c_int64, c_int, c_int, c_int]),
     "vqseg_adam_step_f32": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double, c_int64, c_void_p]),
+    "vqseg_adam_ema_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double, c_int64, c_double, c_int,
+                                        c_void_p]),
     "vqseg_batch_u8_f": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 6),
     "vqseg_box_mix_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 3 + [c_void_p, ctypes.c_uint64, c_void_p]),
 }

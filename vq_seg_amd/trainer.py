@@ -26,6 +26,8 @@ from .loss.dice_loss import DiceLoss, ce_dice_loss, dice_loss
 from .loss.focal_loss import FocalLoss
 from .measurement import confusion_matrix_device, miou_device
 from . import nnf
+from .averaging import AveragedNetwork
+from .evaluate import test_loop
 from .models import init_weight
 from .models.networks import make_model
 from .optim import HipAdam
@@ -221,9 +223,17 @@ class CPSConfig:
                                               # supervised and both CPS terms (deprecated/train_vq_pt_unet_balncedweightedloss.py:135-141); made and kept on
                                               # the device, per rank under data parallelism; nothing of it is checkpointed.  A sequence: fixed weights
                                               # (train_vq_pt_unet_withtest.py:283).  None = today's step
+    ema_decay: Optional[float] = None         # exponential moving average ("teacher") of each network, kept inside its Adam launch
+                                              # (averaging.AveragedNetwork, optim.HipAdam.attach_average; no reference counterpart): e' = e + (1 - decay)(p' - e)
+                                              # after every step, the first update a copy.  None = no teacher, nothing of it is entered
+    teacher_pseudo_labels: bool = False       # the two no-grad eval forwards that open the step run the teachers instead of the students
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
+        if self.ema_decay is not None and not 0.0 <= float(self.ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be None or lie in [0, 1), got {self.ema_decay!r}")
+        if self.teacher_pseudo_labels and self.ema_decay is None:
+            raise ValueError("teacher_pseudo_labels needs a teacher: set ema_decay")
         if self.recipe != "v1" and (self.criterion != "dice_loss" or self.class_weight is not None):
             raise ValueError("criterion / class_weight apply to recipe 'v1', the single-criterion recipe; the reference has no weighted or "
                              "focal form of recipe 'v2' (CE + Dice)")
@@ -283,10 +293,16 @@ def score_mask(pred: torch.Tensor, pseudo: torch.Tensor, th: float = 0.7) -> tor
 
 
 class CPSTrainer:
+    averages: Sequence[AveragedNetwork] = ()              # cfg.ema_decay: one per network (and `teachers`, their modules); empty = no teacher
+    teachers: Sequence[nn.Module] = ()
+
     def __init__(self, cfg: CPSConfig, device, models: Optional[List[nn.Module]] = None):
         """`models`: an already built (model_1, model_2) pair on `device` (fixtures with given weights); else the pair is built
         from cfg.model as the reference trainer does (train_vqreptunet1x1v2.py:70-80)."""
         self.cfg, self.device = cfg, device
+        if cfg.ema_decay is not None and not (torch.device(device).type == "cuda" and nnf.py_opt("py_hip_adam", 1)):
+            raise ValueError("ema_decay: the averaged networks are kept inside optim.HipAdam's launch, which needs a 'cuda' (ROCm) device and "
+                             "py_hip_adam = 1. There is no CPU path.")
         self.aux: Dict[str, torch.Tensor] = {}
         torch.manual_seed(cfg.seed)                      # same initial weights on every rank
         self.models = list(models) if models is not None else [make_model(cfg.model).to(device), make_model(cfg.model).to(device)]
@@ -323,6 +339,17 @@ class CPSTrainer:
         self.opts = [HipAdam(m.parameters(), lr=cfg.learning_rate, betas=(0.9, 0.999)) if self.device.type == "cuda" and nnf.py_opt("py_hip_adam", 1)
                      else torch.optim.Adam(m.parameters(), lr=cfg.learning_rate, betas=(0.9, 0.999), fused=self.device.type == "cuda")
                      for m in self.models]
+        # the teachers (cfg.ema_decay): built after the init and the rank-0 broadcast, so every rank's teacher starts from the same bits;
+        # network k's teacher is written by network k's Adam launch on network k's stream (the end-of-step _join() shows it to the caller)
+        if cfg.ema_decay is not None:
+            self.averages = []
+            with torch.random.fork_rng(devices=[device]):    # building the teachers draws nothing from the run's generators
+                for m, o in zip(self.models, self.opts):
+                    avg = AveragedNetwork(m, lambda: make_model(cfg.model), cfg.ema_decay)
+                    avg.module.async_code_usage = True
+                    o.attach_average(avg)
+                    self.averages.append(avg)
+            self.teachers = [a.module for a in self.averages]
         self.sched = CosineAnnealingLR(cfg.learning_rate, cfg.min_lr, cfg.total_iters, cfg.warmup_steps)
         self.ce = nn.CrossEntropyLoss(ignore_index=255)
         fixed = None
@@ -349,12 +376,13 @@ class CPSTrainer:
         self._pending_sides.add(side)
         return out
 
-    def _fwd_pair(self, a1, a2, use_amp=True, **kw):
+    def _fwd_pair(self, a1, a2, use_amp=True, models=None, **kw):
         """model 1 on a1 = (x[, gt]) and model 2 on a2, phase by phase: encoders overlap on the two streams, the VQ phases
         run one after the other with the other stream idle (the distance kernels fill the GPU on their own, and their
         in-stream timing -- bench.py's roofline -- then measures the kernel, not the sharing), decoders overlap again.
-        `use_amp=False`: this pair runs outside autocast whatever cfg.amp_dtype says (the pseudo-label passes)."""
-        m1, m2 = self.models
+        `use_amp=False`: this pair runs outside autocast whatever cfg.amp_dtype says (the pseudo-label passes).
+        `models`: the pair of modules to run (the teachers, for their pseudo labels), on the same streams; default the students."""
+        m1, m2 = models or self.models
         amp = self.cfg.amp_dtype if use_amp else None
 
         def on(stream, fn, *args, **kws):
@@ -479,7 +507,7 @@ class CPSTrainer:
 
         with torch.no_grad():                                           # pseudo labels from eval passes
             m1.eval(); m2.eval()
-            o1, o2 = self._fwd_pair((ul_input,), (ul_input,), use_amp=cfg.eval_amp)
+            o1, o2 = self._fwd_pair((ul_input,), (ul_input,), use_amp=cfg.eval_amp, models=self.teachers if cfg.teacher_pseudo_labels else None)
             score_1, score_2 = o1[0], o2[0]
             if not split:
                 self._join()
@@ -664,6 +692,10 @@ class CPSTrainer:
         moments are identical on all ranks; the BatchNorm running statistics in the file are rank 0's); no collective, no rank's
         state is touched -- writing a checkpoint cannot alter the run."""
         extra = {"iter": self.iter}
+        if self.averages and vdist.rank() == 0:              # the teachers, beside the reference's keys
+            for i, a in enumerate(self.averages):
+                extra[f"ema_model_{i + 1}"] = a.state_dict()["module"]
+            extra["ema_updates"] = [int(a.updates) for a in self.averages]
         if vdist.collectives_on() and vdist.world_size() > 1:
             # BatchNorm running statistics are per-rank: COPIES of every rank's buffers are gathered to rank 0 (no rank's state is
             # touched) and stored beside the reference's keys, so that a data-parallel resume restores each rank's own statistics
@@ -703,8 +735,23 @@ class CPSTrainer:
                         if name in bufs:
                             bufs[name].copy_(flat[off:off + n].view(shape).to(bufs[name].dtype))
                         off += n
+        for i, a in enumerate(self.averages):
+            # a file without teachers (a reference checkpoint, or one written with the feature off): each a copy of the loaded student
+            a.reset_from_student()
+            if f"ema_model_{i + 1}" in state:
+                a.load_state_dict({"module": state[f"ema_model_{i + 1}"], "updates": state["ema_updates"][i]})
         self.iter = int(state.get("iter", self.iter))
         return state.get("epoch", 0), state.get("batch_idx", 0)
+
+    def evaluate(self, batches, which: str = "student", index: int = 0):
+        """evaluate.test_loop on network `index` of the pair: which="student" scores the trained weights, which="teacher" their
+        exponential moving average (cfg.ema_decay), under cfg.amp_dtype.  `batches` yields (images, labels)."""
+        if which not in ("student", "teacher"):
+            raise ValueError(f"which must be 'student' or 'teacher', got {which!r}")
+        if which == "teacher" and not self.teachers:
+            raise ValueError("which='teacher' needs a teacher: set CPSConfig.ema_decay")
+        model = (self.teachers if which == "teacher" else self.models)[index]
+        return test_loop(model, batches, self.cfg.num_classes, device=self.device, amp_dtype=self.cfg.amp_dtype)
 
     def _weighted(self, pred, target, weight):
         """the configured criterion with this step's class weights: the module's own parameters (ignore index 255, the focal

@@ -407,7 +407,8 @@ int vqseg_maxpool3x3s2_backward_add_f(int bf16, const void* g, const unsigned ch
                                       int c, void* gx, void* stream);
 
 /* Stem support: patch matrix of the 7x7/2 convolution (resnet.py:122-125; zero or reflect padding),
- * columns (kh, kw, ci) padded with zeros to kp; gradient fold of reflect padding 1; f32 <-> bf16 cast. */
+ * columns (kh, kw, ci) padded with zeros to kp; gradient fold of reflect padding 1; f32 <-> bf16 cast.
+ * Reflect padding needs pad < h and pad < w (one reflection, as F.pad), else VQSEG_EINVAL. */
 int vqseg_im2col_f(int out_bf16, const float* x, int n, int h, int w, int cin, int kh, int kw, int stride,
                    int pad, int reflect, int ho, int wo, int kp, void* out, void* stream);
 int vqseg_reflect_fold_f(int bf16, const void* gp, int n, int h, int w, int c, void* gx, void* stream);

@@ -121,10 +121,13 @@ def _assert_within_bound(case, y, what):
 
 
 def _assert_batchnorm_statistics(case, stat):
-    """the partials through vqseg_bn_finalize_f (training form, as nnf._bn_finalize): mean within 1e-5 of max |ref|, biased variance
-    within 1e-4 of the largest variance -- the bars of test_nn_gpu._patch_case"""
+    _assert_batchnorm_statistics_of(dc.reference(case)[0], stat)
+
+
+def _assert_batchnorm_statistics_of(ref, stat):
+    """the partials through vqseg_bn_finalize_f (training form, as nnf._bn_finalize) against the fp64 output ref [M, C]: mean within
+    1e-5 of max |ref|, biased variance within 1e-4 of the largest variance -- the bars of test_nn_gpu._patch_case"""
     L = _lib()
-    ref, _S = dc.reference(case)
     m, c = ref.shape
     eps, d = 1e-5, dev()
     part = stat.clone()                                         # finalize merges in place

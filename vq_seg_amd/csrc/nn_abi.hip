@@ -302,6 +302,7 @@ int vqseg_maxpool3x3s2_backward_add_f(int bf16, const void* g, const unsigned ch
 int vqseg_im2col_f(int out_bf16, const float* x, int n, int h, int w, int cin, int kh, int kw, int stride, int pad, int reflect,
                    int ho, int wo, int kp, void* out, void* stream) {
     if (!x || !out || kp < kh * kw * cin) return bad("im2col: bad argument");
+    if (reflect && (pad >= h || pad >= w)) return bad("im2col: reflect padding needs pad < size");   // one reflection only, as F.pad
     hipError_t e = vqseg::launch_im2col_stem(out_bf16, x, n, h, w, cin, kh, kw, stride, pad, reflect, ho, wo, kp, out,
                                              static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "im2col_stem_kernel");

@@ -693,6 +693,30 @@ int vqseg_batch_u8_f(int n, const uint8_t* img_cache, const uint8_t* mask_cache,
 int vqseg_box_mix_f(int mode, int elem_bytes, const void* src, void* out, int n, int planes, int h, int w, int64_t stride_s,
                     int64_t stride_p, int64_t stride_px, const int32_t* boxes_host, uint64_t fill_bits, void* stream);
 
+/* Affine warp: a whole batch resampled out of place in one pass, one 2 x 2 matrix per sample (vq_seg_amd.data.augmentations:
+ * similarity_transform / inverse_similarity_transform / warp_batch; the reference's flips and TF.rotate, data/augmentations.py:108-148,
+ * TF.rotate on tensors being grid_sample with align_corners=False and zero padding).  For output pixel (x, y) of an h x w image, with
+ * cx = (w - 1) / 2, cy = (h - 1) / 2, dx = x - cx, dy = y - cy:
+ *     xs = (M00 * dx + M01 * dy) + cx        ys = (M10 * dx + M11 * dy) + cy          (f32, this order, no FMA contraction)
+ * so for M with entries in {0, +-1} every (xs, ys) is an exact integer.
+ *   mode 0 BILINEAR     elem_bytes 4 (f32) or 2 (bf16): four taps, weights from xs - floor(xs), ys - floor(ys), f32 accumulation, bf16 rounded
+ *                       once (nearest even); a tap outside the image contributes nothing (zero padding); a tap of weight exactly zero is not
+ *                       read, and an integer (xs, ys) is copied by bits: identity, flips and quarter turns pass every bit pattern through
+ *   mode 1 NEAREST      elem_bytes 1, 2, 4, 8 (uint8 ... int64 label maps, anything by bits): source pixel (rintf(xs), rintf(ys)), round half
+ *                       to even; a source outside the image gives fill_bits (its low elem_bytes bytes)
+ *   src, out            out of place; the same layout, each with its own sample stride (ELEMENTS, >= planes * h * w when n > 1)
+ *   stride_p/_px        plane and pixel strides in ELEMENTS, rows dense, as vqseg_box_mix_f takes them: planar (pixel stride 1, plane stride
+ *                       h * w) or interleaved (plane stride 1, pixel stride planes); anything else is VQSEG_EINVAL
+ *   matrices_host [n][6] HOST rows (M00, M01, 0, M10, M11, 0): the layout of a 2 x 3 affine matrix whose translation slots are reserved and
+ *                       must be 0; every entry finite.  The matrices travel as kernel arguments (64 samples per launch): no device
+ *                       allocation, no host-to-device copy, no synchronisation
+ * A gather bound by HBM / L2: a 256-thread workgroup takes a 2-D tile of output pixels, so that the rotated source footprint's cache lines
+ * are reused inside the tile and the stores stay coalesced; coordinates and weights once per pixel for all its planes.  h, w <= 2^24.
+ * Grid capped by option "nn_grid_cap". */
+int vqseg_affine_warp_f(int mode, int elem_bytes, const void* src, void* out, int n, int planes, int h, int w, int64_t src_stride_s,
+                        int64_t out_stride_s, int64_t stride_p, int64_t stride_px, const float* matrices_host, uint64_t fill_bits,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,7 @@ SYMBOLS = {
                                         c_void_p]),
     "vqseg_batch_u8_f": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 6),
     "vqseg_box_mix_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 3 + [c_void_p, ctypes.c_uint64, c_void_p]),
+    "vqseg_affine_warp_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 4 + [c_void_p, ctypes.c_uint64, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -591,6 +592,66 @@ def box_mix(src: torch.Tensor, boxes, mode: str = "mix", fill=0, out: Optional[t
     bits = int.from_bytes(torch.tensor([fill], dtype=src.dtype).view(torch.uint8).numpy().tobytes(), "little") if mode == "fill" else 0
     launch("vqseg_box_mix_f", src.device, int(mode == "fill"), src.element_size(), sp, op, n, planes, h, w, *strides, bx.ctypes.data, bits)
     BOX_MIX_CALLS += 1
+    return out
+
+
+AFFINE_WARP_BILINEAR_DTYPES = (torch.float32, torch.bfloat16)
+AFFINE_WARP_NEAREST_DTYPES = (torch.uint8, torch.int8, torch.bool, torch.int16, torch.bfloat16, torch.float16, torch.int32, torch.float32, torch.int64,
+                              torch.float64)             # element widths 1, 2, 4, 8: nearest selects by bits
+AFFINE_WARP_CALLS = 0         # calls of affine_warp that reached the library (as BOX_MIX_CALLS: for tests, never read by the product)
+
+
+def affine_warp(src: torch.Tensor, matrices, mode: str = "bilinear", fill=0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A batch resampled through one 2 x 2 matrix per sample (include/vqseg.h: vqseg_affine_warp_f): src (n, P, h, w) -- NCHW-contiguous
+    or channels_last -- or (n, h, w); `matrices`: n host rows (M00, M01, 0, M10, M11, 0) mapping an output pixel's offset from the image
+    centre to its source's.  `mode` "bilinear" (float32 / bfloat16, zero padding) or "nearest" (any 1 / 2 / 4 / 8-byte dtype, by bits;
+    a source outside the image gives `fill`).  Out of place: returns `out` (default: a new tensor of src's layout; a given `out` has
+    src's shape and per-sample layout and may have a larger sample stride); src is not written."""
+    global AFFINE_WARP_CALLS
+    if mode not in ("bilinear", "nearest"):
+        raise HipLibraryError(f"affine_warp: mode must be 'bilinear' or 'nearest', got {mode!r}")
+    if not isinstance(src, torch.Tensor) or src.dim() not in (3, 4):
+        raise HipLibraryError("affine_warp: src must be a (n, P, h, w) or (n, h, w) tensor")
+    n, (h, w) = src.shape[0], src.shape[-2:]
+    planes = src.shape[1] if src.dim() == 4 else 1
+    try:
+        mats = np.ascontiguousarray(matrices, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise HipLibraryError("affine_warp: matrices must be n rows of six numbers") from None
+    if mats.shape != (n, 6):
+        raise HipLibraryError(f"affine_warp: one (M00, M01, 0, M10, M11, 0) row per sample required: {n} samples, matrices of shape {mats.shape}")
+    if not np.isfinite(mats).all():
+        raise HipLibraryError("affine_warp: a matrix entry is not finite")
+    if mats[:, (2, 5)].any():
+        raise HipLibraryError("affine_warp: the translation slots (entries 2 and 5 of a row) are reserved and must be 0")
+    dtypes = AFFINE_WARP_BILINEAR_DTYPES if mode == "bilinear" else AFFINE_WARP_NEAREST_DTYPES
+    numel = n * planes * h * w
+    sp = tptr(src, "src", dtype=dtypes, numel=numel)
+    if numel == 0:
+        raise HipLibraryError("affine_warp: empty tensor")
+    # tptr admits two dense layouts; the strides are stated from the layout (a size-1 dimension's own stride is arbitrary)
+    planar = src.is_contiguous()
+    inner = (h * w, 1) if planar else (1, planes)
+    out_stride = planes * h * w
+    if out is None:
+        out = torch.empty_like(src)                          # dense src: the same strides
+        op = tptr(out, "out", dtype=src.dtype, numel=numel)
+    else:
+        if not isinstance(out, torch.Tensor) or out.shape != src.shape:
+            raise HipLibraryError("affine_warp: out must have src's shape and layout")
+        one = out[:1]                                        # a sample of out: dense in src's layout; samples at least a sample apart
+        if (one.is_contiguous() if planar else (one.dim() == 4 and one.is_contiguous(memory_format=torch.channels_last))) and \
+                (n == 1 or out.stride(0) >= out_stride):
+            out_stride = out.stride(0) if n > 1 else out_stride
+        else:
+            raise HipLibraryError("affine_warp: out must have src's shape and layout")
+        op = tptr(out, "out", dtype=src.dtype, numel=numel, dense=False)
+        if type(sp) is int and type(op) is int and sp == op:
+            raise HipLibraryError("affine_warp: out of place only")
+    bits = int.from_bytes(torch.tensor([fill], dtype=src.dtype).view(torch.uint8).numpy().tobytes(), "little") if mode == "nearest" else 0
+    launch("vqseg_affine_warp_f", src.device, int(mode == "nearest"), src.element_size(), sp, op, n, planes, h, w, planes * h * w, out_stride,
+           *inner, mats.ctypes.data, bits)
+    AFFINE_WARP_CALLS += 1
     return out
 
 

@@ -215,6 +215,121 @@ static hipError_t launch_box_mix(const BoxArgs& box, int s0, int nb, int n, int 
     return hipGetLastError();
 }
 
+// ---- affine warp (vq_seg_amd/data/augmentations.py: similarity_transform / inverse_similarity_transform / warp_batch; the CPS step's
+// easy augmentation) -------------------------------------------------------------------------------------------------------------------
+//
+// Reference: similarity_transform / inverse_similarity_transform (data/augmentations.py:108-148) flip and TF.rotate a batch; on tensors
+// TF.rotate is F.grid_sample on an affine grid (align_corners=False, zero padding).  In pixel space that is, for output pixel (x, y) of an
+// h x w image with cx = (w - 1) / 2, cy = (h - 1) / 2, dx = x - cx, dy = y - cy and the sample's 2 x 2 matrix M:
+//     xs = (M00 * dx + M01 * dy) + cx        ys = (M10 * dx + M11 * dy) + cy          (f32, this order, no FMA contraction)
+// cx, cy, dx, dy are exact in f32, so for M with entries in {0, +-1} (identity, flips, quarter turns) xs and ys are exact integers.
+//   BILINEAR (f32, bf16): taps (x0, y0) = floor(xs, ys) and its right / lower neighbours, weights from fx = xs - x0, fy = ys - y0,
+//     accumulated in f32 in the order 00, 01, 10, 11; bf16 rounded once (nearest even).  A tap outside the image contributes nothing
+//     (zero padding) and a tap whose weight is exactly zero is not read; with fx == fy == 0 the one tap is copied by BITS, so identity,
+//     flips and quarter turns pass NaN payloads, infinities and -0.0 through as the box mix does.
+//   NEAREST (1 / 2 / 4 / 8-byte elements, by bits): the source pixel is (rintf(xs), rintf(ys)) -- round half to even, as grid_sample --
+//     and a source outside the image gives `fill`.
+// A gather bound by HBM / L2: one read and one write per element when the source footprint stays in cache.  A 256-thread workgroup
+// takes a 2-D tile of OUTPUT pixels (16 x 16, or 32 x 8 / 64 x 4 for pixels of <= 4 / <= 2 bytes, so a tile row stays >= 64 bytes of
+// coalesced stores): under a rotation the tile's source footprint is a rotated rectangle whose cache lines are reused by the tile's
+// rows, where 256 pixels of one output row would touch a new line per pixel.  Coordinates and weights are computed once per pixel and
+// applied to all its planes.  The matrices travel as kernel arguments, BATCH_ARG_SAMPLES per launch.
+constexpr int WARP_BILINEAR = 0, WARP_NEAREST = 1;
+
+struct WarpArgs {                                           // 1 KiB of kernel arguments: BATCH_ARG_SAMPLES 2 x 2 matrices
+    float m00[BATCH_ARG_SAMPLES], m01[BATCH_ARG_SAMPLES], m10[BATCH_ARG_SAMPLES], m11[BATCH_ARG_SAMPLES];
+};
+
+__device__ inline float warp_value(uint32_t bits) { return __uint_as_float(bits); }
+__device__ inline float warp_value(uint16_t bits) { return __uint_as_float((uint32_t)bits << 16); }     // bf16
+
+template <typename T>
+__device__ inline T warp_bits(float v) {
+    uint32_t u = __float_as_uint(v);
+    if constexpr (sizeof(T) == 4) {
+        return u;
+    } else {                                                // bf16, round to nearest even; a NaN stays a (quiet) NaN
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (T)((u >> 16) | 0x40u);
+        return (T)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+    }
+}
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void affine_warp_kernel(WarpArgs mat, int nb, const T* __restrict__ src, T* __restrict__ out,
+                                                          long src_stride_s, long out_stride_s, int planes, int h, int w, long stride_p,
+                                                          long stride_px, int tw_log2, T fill) {
+#pragma clang fp contract(off)
+    const int tw = 1 << tw_log2, th = 256 >> tw_log2;
+    const int tiles_x = (w + tw - 1) >> tw_log2, tiles_y = (h + th - 1) / th;
+    const long per = (long)tiles_x * tiles_y;               // tiles per sample
+    const int lx = threadIdx.x & (tw - 1), ly = threadIdx.x >> tw_log2;
+    const float cx = (float)(w - 1) * 0.5f, cy = (float)(h - 1) * 0.5f;
+    for (long tile = blockIdx.x; tile < per * nb; tile += gridDim.x) {
+        const int i = (int)(tile / per);                    // uniform across the workgroup: the matrix is read from scalar registers
+        const long r = tile - i * per;
+        const int ty = (int)(r / tiles_x), tx = (int)(r - (long)ty * tiles_x);
+        const int x = (tx << tw_log2) + lx, y = ty * th + ly;
+        if (x >= w || y >= h) continue;
+        const float dx = (float)x - cx, dy = (float)y - cy;
+        const float xs = (mat.m00[i] * dx + mat.m01[i] * dy) + cx;
+        const float ys = (mat.m10[i] * dx + mat.m11[i] * dy) + cy;
+        const T* a = src + i * src_stride_s;
+        T* o = out + i * out_stride_s + ((long)y * w + x) * stride_px;
+        if constexpr (MODE == WARP_NEAREST) {
+            bool in = xs > -1.0f && xs < (float)w + 1.0f && ys > -1.0f && ys < (float)h + 1.0f;     // (false for a NaN: inf - inf)
+            long at = 0;
+            if (in) {
+                const int xi = (int)rintf(xs), yi = (int)rintf(ys);
+                in = xi >= 0 && xi < w && yi >= 0 && yi < h;
+                at = ((long)yi * w + xi) * stride_px;
+            }
+            for (int p = 0; p < planes; ++p) o[p * stride_p] = in ? a[at + p * stride_p] : fill;
+        } else {
+            if (!(xs > -1.0f && xs < (float)w && ys > -1.0f && ys < (float)h)) {      // all four taps outside (or a NaN coordinate)
+                for (int p = 0; p < planes; ++p) o[p * stride_p] = (T)0;
+                continue;
+            }
+            const float xf = floorf(xs), yf = floorf(ys);
+            const float fx = xs - xf, fy = ys - yf;
+            const int x0 = (int)xf, y0 = (int)yf;           // in [-1, w - 1] x [-1, h - 1]
+            const long at = ((long)y0 * w + x0) * stride_px;
+            if (fx == 0.0f && fy == 0.0f) {                 // an integer source pixel (inside: xs > -1 and whole): by bits
+                for (int p = 0; p < planes; ++p) o[p * stride_p] = a[at + p * stride_p];
+                continue;
+            }
+            const float wx0 = 1.0f - fx, wy0 = 1.0f - fy;
+            const float w00 = wy0 * wx0, w01 = wy0 * fx, w10 = fy * wx0, w11 = fy * fx;
+            const bool r00 = w00 != 0.0f && x0 >= 0 && y0 >= 0, r01 = w01 != 0.0f && x0 + 1 < w && y0 >= 0;
+            const bool r10 = w10 != 0.0f && x0 >= 0 && y0 + 1 < h, r11 = w11 != 0.0f && x0 + 1 < w && y0 + 1 < h;
+            const long right = stride_px, down = (long)w * stride_px;
+            for (int p = 0; p < planes; ++p) {
+                const T* t = a + at + p * stride_p;
+                const float v00 = r00 ? warp_value(t[0]) : 0.0f, v01 = r01 ? warp_value(t[right]) : 0.0f;
+                const float v10 = r10 ? warp_value(t[down]) : 0.0f, v11 = r11 ? warp_value(t[down + right]) : 0.0f;
+                float acc = r00 ? w00 * v00 : 0.0f;
+                if (r01) acc += w01 * v01;
+                if (r10) acc += w10 * v10;
+                if (r11) acc += w11 * v11;
+                o[p * stride_p] = warp_bits<T>(acc);
+            }
+        }
+    }
+}
+
+template <typename T, int MODE>
+static hipError_t launch_affine_warp(const WarpArgs& mat, int nb, const void* src, void* out, long src_stride_s, long out_stride_s, int planes,
+                                     int h, int w, long stride_p, long stride_px, unsigned long long fill_bits, hipStream_t st) {
+    const long pixel_bytes = (long)sizeof(T) * (stride_px > 1 ? planes : 1);
+    const int tw_log2 = pixel_bytes <= 2 ? 6 : pixel_bytes <= 4 ? 5 : 4;
+    const int tw = 1 << tw_log2, th = 256 >> tw_log2;
+    long blocks = (long)((w + tw - 1) / tw) * ((h + th - 1) / th) * nb;
+    const long cap = nn_grid_cap();
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL((affine_warp_kernel<T, MODE>), dim3((unsigned)blocks), dim3(256), 0, st, mat, nb, static_cast<const T*>(src),
+                       static_cast<T*>(out), src_stride_s, out_stride_s, planes, h, w, stride_p, stride_px, tw_log2, (T)fill_bits);
+    return hipGetLastError();
+}
+
 }  // namespace vqseg
 
 extern "C" {
@@ -315,6 +430,66 @@ int vqseg_box_mix_f(int mode, int elem_bytes, const void* src, void* out, int n,
         if (e != hipSuccess) {
             char buf[160];
             snprintf(buf, sizeof(buf), "box_mix_kernel: %s", hipGetErrorString(e));
+            return vqseg_set_error((int)e, buf);
+        }
+    }
+    return 0;
+}
+
+int vqseg_affine_warp_f(int mode, int elem_bytes, const void* src, void* out, int n, int planes, int h, int w, int64_t src_stride_s,
+                        int64_t out_stride_s, int64_t stride_p, int64_t stride_px, const float* matrices_host, uint64_t fill_bits,
+                        void* stream) {
+    using namespace vqseg;
+    if (mode != WARP_BILINEAR && mode != WARP_NEAREST)
+        return vqseg_set_error(VQSEG_EINVAL, "affine_warp: mode must be 0 (bilinear) or 1 (nearest)");
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8)
+        return vqseg_set_error(VQSEG_EINVAL, "affine_warp: element width must be 1, 2, 4 or 8 bytes");
+    if (mode == WARP_BILINEAR && elem_bytes != 2 && elem_bytes != 4)
+        return vqseg_set_error(VQSEG_EINVAL, "affine_warp: bilinear takes element width 4 (f32) or 2 (bf16) only; other widths are nearest");
+    if (n <= 0 || planes <= 0 || h <= 0 || w <= 0) return vqseg_set_error(VQSEG_EINVAL, "affine_warp: n, planes, h and w must be positive");
+    if (h > (1 << 24) || w > (1 << 24) || (long)planes * h * w > (1L << 40))
+        return vqseg_set_error(VQSEG_EINVAL, "affine_warp: h or w above 2^24 (the image centre must be exact in f32) or sample larger than 2^40 elements");
+    if (!src || !out || !matrices_host) return vqseg_set_error(VQSEG_EINVAL, "affine_warp: null src, out or matrices_host");
+    if (src == out) return vqseg_set_error(VQSEG_EINVAL, "affine_warp: out of place only (a pixel's source is read after other pixels are written)");
+    const long elems = (long)planes * h * w;
+    const bool planar = stride_px == 1 && (planes == 1 || stride_p == (int64_t)h * w);
+    const bool interleaved = planes > 1 && stride_p == 1 && stride_px == planes;
+    if (!planar && !interleaved)
+        return vqseg_set_error(VQSEG_EINVAL, "affine_warp: layout must be planar (NCHW, 3-D labels) or interleaved (channels_last) with dense rows");
+    if (n > 1 && (src_stride_s < elems || out_stride_s < elems))
+        return vqseg_set_error(VQSEG_EINVAL, "affine_warp: sample stride smaller than a sample");
+    for (long i = 0; i < 6L * n; ++i)
+        if (!(matrices_host[i] - matrices_host[i] == 0.0f))
+            return vqseg_set_error(VQSEG_EINVAL, "affine_warp: a matrix entry is not finite");
+    for (long i = 0; i < n; ++i)
+        if (matrices_host[6 * i + 2] != 0.0f || matrices_host[6 * i + 5] != 0.0f)
+            return vqseg_set_error(VQSEG_EINVAL, "affine_warp: the translation slots (entries 2 and 5 of a row) are reserved and must be 0");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (int s0 = 0; s0 < n; s0 += BATCH_ARG_SAMPLES) {
+        const int nb = n - s0 < BATCH_ARG_SAMPLES ? n - s0 : BATCH_ARG_SAMPLES;
+        WarpArgs mat = {};
+        for (int i = 0; i < nb; ++i) {
+            const float* m = matrices_host + 6 * (long)(s0 + i);
+            mat.m00[i] = m[0], mat.m01[i] = m[1], mat.m10[i] = m[3], mat.m11[i] = m[4];
+        }
+        const char* a = static_cast<const char*>(src) + (long)s0 * src_stride_s * elem_bytes;
+        char* o = static_cast<char*>(out) + (long)s0 * out_stride_s * elem_bytes;
+        hipError_t e;
+#define VQSEG_WARP(T, MODE) launch_affine_warp<T, MODE>(mat, nb, a, o, src_stride_s, out_stride_s, planes, h, w, stride_p, stride_px, fill_bits, st)
+        if (mode == WARP_BILINEAR) {
+            e = elem_bytes == 4 ? VQSEG_WARP(uint32_t, WARP_BILINEAR) : VQSEG_WARP(uint16_t, WARP_BILINEAR);
+        } else {
+            switch (elem_bytes) {
+                case 1: e = VQSEG_WARP(uint8_t, WARP_NEAREST); break;
+                case 2: e = VQSEG_WARP(uint16_t, WARP_NEAREST); break;
+                case 4: e = VQSEG_WARP(uint32_t, WARP_NEAREST); break;
+                default: e = VQSEG_WARP(uint64_t, WARP_NEAREST); break;
+            }
+        }
+#undef VQSEG_WARP
+        if (e != hipSuccess) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "affine_warp_kernel: %s", hipGetErrorString(e));
             return vqseg_set_error((int)e, buf);
         }
     }

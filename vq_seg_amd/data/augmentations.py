@@ -8,7 +8,21 @@ the GPU take ONE HIP pass per tensor (`_hip.box_mix`, vqseg_box_mix_f) that sele
 (0 / 1 masks make the arithmetic a selection); they differ only where arithmetic is not a selection: the reference turns -0.0 into
 +0.0 and spreads a NaN / inf of the partner over the whole image (x * 1 + nan * 0), the kernel passes every bit pattern through.
 
-Not built: similarity_transform / inverse_similarity_transform (data/augmentations.py:108-148; their rotations discard their result).
+Similarity transforms (reference: data/augmentations.py:108-148; driven by deprecated/train_vqpt_easyhard_aug.py:90-123 as the EASY
+augmentation: the pseudo-label forwards see a flipped / rotated batch, and inverse_similarity_transform brings their outputs back into
+the clean frame).  What is the reference's: the two names and signatures, the ten codes, and the draws in their order -- one
+random.randint(0, 9), then, for every code but 1 and 2, one uniform angle of [0, 90) from torch's global generator
+(RandomRotation.get_params, restated from torchvision's source: torchvision is not a dependency).  What is evident intent: the
+reference's forward rotations call TF.rotate and DROP the result (codes 3-8 return their input, or nothing but the flip), codes 4 / 6 / 8
+negate the angle and then pass its negation again, and codes 0 and 9 return a drawn angle that the inverse would then rotate by.  Built
+here: code 1 / 2 = horizontal / vertical flip; 3 / 4 = rotation by +a / -a; 5 / 6 = horizontal flip, then rotation by +a / -a; 7 / 8 =
+vertical flip, then rotation; 0 and 9 = identity.  The angle returned is signed (negative for 4 / 6 / 8) and 0.0 for codes 0, 1, 2 and 9,
+so inverse_similarity_transform(similarity_transform(x)) is the exact matrix inverse for every code.  A rotation is TF.rotate's on
+tensors -- grid_sample, align_corners=False, zero fill, positive = counter-clockwise as displayed -- restated in pixel space
+(`similarity_matrices`, `warp_batch`; vqseg_affine_warp_f on the GPU).  Where the two differ on purpose: the reference's inverse
+interpolates integer class maps bilinearly, which invents classes between two labels; integer and bool tensors here take the NEAREST
+source pixel (and `fill` outside the image).  Flips, quarter turns on square images and the identity pass every bit pattern through,
+on either device.
 """
 from __future__ import annotations
 
@@ -106,6 +120,168 @@ def mix_boxes(t: torch.Tensor, boxes: Sequence[Box], mode: str = "mix", fill=0) 
         inside = inside[:, None]
     other = torch.roll(t, -1, 0) if mode == "mix" else torch.full_like(t, fill)
     return torch.where(inside, other, t)
+
+
+# ---- similarity transforms (flip / rotation): the easy augmentation ---------------------------------------------------------------
+
+_FLIP = {1: (-1.0, 1.0), 2: (1.0, -1.0), 5: (-1.0, 1.0), 6: (-1.0, 1.0), 7: (1.0, -1.0), 8: (1.0, -1.0)}     # code -> diag(sx, sy) of its flip
+_QUARTER = {0.0: (1.0, 0.0), 90.0: (0.0, 1.0), 180.0: (-1.0, 0.0), 270.0: (0.0, -1.0)}                          # angle mod 360 -> exact (cos, sin)
+
+
+def similarity_matrices(codes, angles, inverse: bool = False) -> np.ndarray:
+    """float32 (n, 6) rows (M00, M01, 0, M10, M11, 0) for `warp_batch` / _hip.affine_warp: the matrix that maps an OUTPUT pixel's
+    offset from the image centre to its SOURCE pixel's.  `codes`: the reference's transform codes 0-9; `angles`: SIGNED degrees, as
+    similarity_transform returns them (negative for codes 4 / 6 / 8; ignored for 0, 1, 2 and 9).  A rotation by a (positive =
+    counter-clockwise as displayed, TF.rotate) samples xs = cos a dx - sin a dy, ys = sin a dx + cos a dy; "flip, then rotate" is
+    F R(a), its inverse -- rotate by -a, then the same flip -- R(-a) F.  Computed in float64; multiples of 90 degrees get exact
+    0 / +-1 entries, so flips and quarter turns are exact permutations of the pixels."""
+    codes = np.atleast_1d(np.asarray(codes)).astype(np.int64)
+    angles = np.atleast_1d(np.asarray(angles, dtype=np.float64))
+    if codes.ndim != 1 or codes.shape != angles.shape:
+        raise ValueError(f"similarity_matrices: one code and one angle per sample required, got shapes {codes.shape} and {angles.shape}")
+    if codes.size and (codes.min() < 0 or codes.max() > 9):
+        raise ValueError("similarity_matrices: codes must lie in 0..9")
+    if not np.isfinite(angles).all():
+        raise ValueError("similarity_matrices: an angle is not finite")
+    out = np.zeros((codes.size, 6), dtype=np.float64)
+    for i, (c, a) in enumerate(zip(codes.tolist(), angles.tolist())):
+        a = 0.0 if c in (0, 1, 2, 9) else (-a if inverse else a)
+        cs = _QUARTER.get(a % 360.0)
+        co, si = cs if cs is not None else (float(np.cos(np.deg2rad(a))), float(np.sin(np.deg2rad(a))))
+        rot = np.array([[co, -si], [si, co]])
+        flip = np.diag(_FLIP.get(c, (1.0, 1.0)))
+        m = rot @ flip if inverse else flip @ rot
+        out[i, 0:2], out[i, 3:5] = m[0], m[1]
+    return (out + 0.0).astype(np.float32)                   # (+ 0.0: no negative zeros among the entries)
+
+
+def _warp_torch(t: torch.Tensor, mats: np.ndarray, mode: str, fill) -> torch.Tensor:
+    """the kernel's arithmetic with torch ops (CPU tensors, and whatever the kernel does not take): the same float32 source
+    coordinates in the same order, the same tap order, zero-weight and outside taps left out, whole source pixels taken by value"""
+    n, (h, w) = t.shape[0], t.shape[-2:]
+    dev = t.device
+    m = torch.as_tensor(mats, dtype=torch.float32, device=dev)
+    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+    dx = (torch.arange(w, dtype=torch.float32, device=dev) - cx)[None, None, :]
+    dy = (torch.arange(h, dtype=torch.float32, device=dev) - cy)[None, :, None]
+    col = [m[:, k, None, None] for k in range(6)]
+    xs = (col[0] * dx + col[1] * dy) + cx                  # separate ops: no fused multiply-add
+    ys = (col[3] * dx + col[4] * dy) + cy
+    xs = torch.nan_to_num(xs, nan=-2.0).clamp(-2.0, w + 1.0)           # far outside is outside (and stays convertible to an index)
+    ys = torch.nan_to_num(ys, nan=-2.0).clamp(-2.0, h + 1.0)
+    flat = t.reshape(n, -1, h * w)                          # (n, P, h w); P = 1 for 3-D maps
+    planes = flat.shape[1]
+    # whole pixels are moved as BITS (an integer view of the same width): torch's selections may pass a bfloat16 through float32 and
+    # lose a NaN's payload on the way
+    as_bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]
+    bits = flat.view(as_bits) if (t.is_floating_point() or t.dtype == torch.bool) else flat
+
+    def tap(of, xi, yi):
+        inside = (xi >= 0) & (xi < w) & (yi >= 0) & (yi < h)
+        at = (yi.clamp(0, h - 1) * w + xi.clamp(0, w - 1)).reshape(n, 1, h * w).expand(n, planes, h * w)
+        return torch.gather(of, 2, at), inside.reshape(n, 1, h * w)
+
+    if mode == "nearest":
+        v, inside = tap(bits, torch.round(xs).long(), torch.round(ys).long())    # round half to even
+        fill_bits = torch.tensor([fill], dtype=t.dtype).view(bits.dtype).to(dev)
+        return torch.where(inside, v, fill_bits).view(t.dtype).reshape(t.shape)
+    xf, yf = torch.floor(xs), torch.floor(ys)
+    fx, fy = xs - xf, ys - yf
+    x0, y0 = xf.long(), yf.long()
+    acc = torch.zeros(flat.shape, dtype=torch.float32, device=dev)
+    for wgt, xi, yi in (((1.0 - fy) * (1.0 - fx), x0, y0), ((1.0 - fy) * fx, x0 + 1, y0), (fy * (1.0 - fx), x0, y0 + 1), (fy * fx, x0 + 1, y0 + 1)):
+        v, inside = tap(flat, xi, yi)
+        wgt = wgt.reshape(n, 1, h * w)
+        acc = acc + torch.where(inside & (wgt != 0), wgt * v.float(), torch.zeros((), dtype=torch.float32, device=dev))
+    v00, in00 = tap(bits, x0, y0)
+    whole = ((fx == 0) & (fy == 0)).reshape(n, 1, h * w)
+    return torch.where(whole, torch.where(in00, v00, torch.zeros_like(v00)), acc.to(t.dtype).view(as_bits)).view(t.dtype).reshape(t.shape)
+
+
+def warp_batch(t: torch.Tensor, matrices, mode: str = "bilinear", fill=0) -> torch.Tensor:
+    """out[s] = t[s] resampled through matrices[s] (rows of `similarity_matrices`); t: (n, P, H, W) or (n, H, W); a new tensor.
+    `mode` "bilinear" (floating tensors; zero padding) or "nearest" (any dtype; `fill` outside the image).  On the GPU: one launch of the
+    affine-warp kernel for the dtypes it takes; CPU tensors and the rest: the same arithmetic with torch ops."""
+    if mode not in ("bilinear", "nearest"):
+        raise ValueError(f"warp_batch: mode must be 'bilinear' or 'nearest', got {mode!r}")
+    if t.dim() not in (3, 4):
+        raise ValueError("warp_batch: a (n, P, H, W) or (n, H, W) tensor required")
+    mats = np.ascontiguousarray(matrices, dtype=np.float32)
+    if mats.shape != (t.shape[0], 6):
+        raise ValueError(f"one matrix row per sample required: {t.shape[0]} samples, matrices of shape {mats.shape}")
+    if mode == "bilinear" and not t.is_floating_point():
+        raise ValueError(f"warp_batch: bilinear needs a floating tensor, got {t.dtype} (integer maps take mode='nearest')")
+    if t.is_cuda and t.dtype in (_hip.AFFINE_WARP_BILINEAR_DTYPES if mode == "bilinear" else _hip.AFFINE_WARP_NEAREST_DTYPES):
+        return _hip.affine_warp(_dense(t), mats, mode=mode, fill=fill)
+    if not np.isfinite(mats).all() or mats[:, (2, 5)].any():
+        raise ValueError("warp_batch: matrix entries must be finite and the translation slots 0")
+    return _warp_torch(t, mats, mode, fill)
+
+
+def _similarity(input: torch.Tensor, aug: int, angle: float, inverse: bool, fill=0) -> torch.Tensor:
+    """one transform for the whole of `input` (..., H, W): a (n, P, H, W) or (n, H, W) batch as it is, a single (H, W) map as a batch of one"""
+    if input.dim() < 2:
+        raise ValueError("similarity transforms need a (..., H, W) tensor")
+    batched = input if input.dim() in (3, 4) else input[None] if input.dim() == 2 else input.flatten(0, -4)
+    n = batched.shape[0]
+    mats = similarity_matrices([int(aug)] * n, [float(angle)] * n, inverse=inverse)
+    mode = "bilinear" if input.is_floating_point() else "nearest"
+    return warp_batch(batched, mats, mode=mode, fill=fill).reshape(input.shape)
+
+
+def similarity_transform(input: torch.Tensor, aug: Optional[int] = None):
+    """data/augmentations.py:108-134 as it is meant (module docstring): -> (output, aug, angle).  `aug` None draws
+    random.randint(0, 9) from Python's global generator; every code but 1 and 2 then draws one angle of [0, 90) from torch's global
+    generator -- also codes 0 and 9, which do not use it (the reference's order of draws).  The angle returned is signed (negative
+    for 4 / 6 / 8), and 0.0 for codes 0, 1, 2, 9.  `input`: (..., H, W); floating tensors are resampled bilinearly with zero fill,
+    integer and bool tensors take the nearest source pixel."""
+    if aug is None:
+        aug = random.randint(0, 9)
+    aug = int(aug)
+    if not 0 <= aug <= 9:
+        raise ValueError(f"similarity_transform: aug must lie in 0..9, got {aug}")
+    angle = 0.0
+    if aug not in (1, 2):
+        drawn = float(torch.empty(1).uniform_(0.0, 90.0).item())        # RandomRotation.get_params([0., 90.])
+        if aug in (3, 5, 7):
+            angle = drawn
+        elif aug in (4, 6, 8):
+            angle = -drawn
+    return _similarity(input, aug, angle, inverse=False), aug, angle
+
+
+def inverse_similarity_transform(input: torch.Tensor, aug: int, angle: float, fill=0) -> torch.Tensor:
+    """data/augmentations.py:136-148: the transform that undoes similarity_transform(., aug) -> (., aug, angle): rotate by -angle,
+    then the code's flip.  Floating tensors: bilinear, zero fill.  Integer and bool tensors (pseudo labels): NEAREST, `fill` outside
+    the image (255 = the ignore index) -- a deviation on purpose, see the module docstring."""
+    aug = int(aug)
+    if not 0 <= aug <= 9:
+        raise ValueError(f"inverse_similarity_transform: aug must lie in 0..9, got {aug}")
+    return _similarity(input, aug, angle, inverse=True, fill=fill)
+
+
+def step_transforms(n: int, seed: int, rank: int, it: int, per: str = "batch", codes: Sequence[int] = tuple(range(10)),
+                    max_angle: float = 90.0) -> Tuple[List[int], List[float]]:
+    """the n (code, signed angle) pairs of one training step as a pure function of (seed, rank, iteration): `per` "batch" = one
+    transform for all samples (the reference draws once per batch), "sample" = one per sample in sample order.  Per transform: the
+    code uniformly from `codes`, then -- for every code but 1 and 2, as similarity_transform draws -- an angle uniformly of
+    [0, max_angle), signed as similarity_transform signs it.  The generator is np.random.default_rng([seed, rank, it, 1]): a key
+    `step_generators` never uses, so a step's CutMix boxes do not depend on this option, and nothing is taken from the global
+    generators."""
+    if per not in ("batch", "sample"):
+        raise ValueError(f"easy_aug_per must be 'batch' or 'sample', got {per!r}")
+    codes = [int(c) for c in codes]
+    if not codes or min(codes) < 0 or max(codes) > 9:
+        raise ValueError(f"step_transforms: codes must be a non-empty selection of 0..9, got {codes!r}")
+    rng = np.random.default_rng([int(seed), int(rank), int(it), 1])
+
+    def draw():
+        c = codes[int(rng.integers(0, len(codes)))]
+        a = 0.0 if c in (1, 2) else float(rng.uniform(0.0, float(max_angle)))
+        return c, (a if c in (3, 5, 7) else -a if c in (4, 6, 8) else 0.0)
+
+    pairs = [draw()] * int(n) if per == "batch" else [draw() for _ in range(int(n))]
+    return [c for c, _a in pairs], [a for _c, a in pairs]
 
 
 class _BoxAug:

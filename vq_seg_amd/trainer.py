@@ -227,6 +227,13 @@ class CPSConfig:
                                               # (averaging.AveragedNetwork, optim.HipAdam.attach_average; no reference counterpart): e' = e + (1 - decay)(p' - e)
                                               # after every step, the first update a copy.  None = no teacher, nothing of it is entered
     teacher_pseudo_labels: bool = False       # the two no-grad eval forwards that open the step run the teachers instead of the students
+    easy_aug: Optional[str] = None            # "similarity": the easy augmentation of deprecated/train_vqpt_easyhard_aug.py:118-123 -- the two no-grad
+                                              # pseudo-label forwards see a flipped / rotated unlabelled batch (data.augmentations.similarity_transform, one
+                                              # affine-warp launch), and each score map is warped back into the clean frame before anything derives a pseudo
+                                              # label from it (corners a rotation leaves uncovered: all-zero logits).  None = the plain step, nothing is entered
+    easy_aug_per: str = "batch"               # "batch": one transform per step for all samples (the reference); "sample": one per image
+    easy_aug_max_angle: float = 90.0          # rotation angles are drawn of [0, max) degrees (the reference: 90)
+    easy_aug_codes: Sequence[int] = tuple(range(10))      # the transform codes drawn from (0 / 9 identity, 1 / 2 flips, 3-8 rotations without / with a flip)
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -234,6 +241,15 @@ class CPSConfig:
             raise ValueError(f"ema_decay must be None or lie in [0, 1), got {self.ema_decay!r}")
         if self.teacher_pseudo_labels and self.ema_decay is None:
             raise ValueError("teacher_pseudo_labels needs a teacher: set ema_decay")
+        if self.easy_aug not in (None, "similarity"):
+            raise ValueError(f"easy_aug must be None or 'similarity', got {self.easy_aug!r}")
+        if self.easy_aug_per not in ("batch", "sample"):
+            raise ValueError(f"easy_aug_per must be 'batch' or 'sample', got {self.easy_aug_per!r}")
+        self.easy_aug_codes = tuple(int(c) for c in self.easy_aug_codes)
+        if not self.easy_aug_codes or min(self.easy_aug_codes) < 0 or max(self.easy_aug_codes) > 9:
+            raise ValueError(f"easy_aug_codes must be a non-empty selection of 0..9, got {self.easy_aug_codes!r}")
+        if not 0.0 <= float(self.easy_aug_max_angle) <= 180.0:
+            raise ValueError(f"easy_aug_max_angle must lie in [0, 180], got {self.easy_aug_max_angle!r}")
         if self.recipe != "v1" and (self.criterion != "dice_loss" or self.class_weight is not None):
             raise ValueError("criterion / class_weight apply to recipe 'v1', the single-criterion recipe; the reference has no weighted or "
                              "focal form of recipe 'v2' (CE + Dice)")
@@ -507,7 +523,17 @@ class CPSTrainer:
 
         with torch.no_grad():                                           # pseudo labels from eval passes
             m1.eval(); m2.eval()
-            o1, o2 = self._fwd_pair((ul_input,), (ul_input,), use_amp=cfg.eval_amp, models=self.teachers if cfg.teacher_pseudo_labels else None)
+            ul_easy = ul_input
+            if cfg.easy_aug is not None:
+                # easy augmentation: the step's transforms on the host, a pure function of (seed, rank, iteration[, sample]) under a key of
+                # their own (the CutMix boxes of the step do not move).  The images are warped ONCE on the caller's stream, for both networks
+                easy_codes, easy_angles = augmentations.step_transforms(ul_input.shape[0], cfg.seed, vdist.rank(), self.iter, cfg.easy_aug_per,
+                                                                        cfg.easy_aug_codes, cfg.easy_aug_max_angle)
+                ul_easy = augmentations.warp_batch(ul_input, augmentations.similarity_matrices(easy_codes, easy_angles))
+                if self._two_streams and ul_easy.is_cuda:
+                    for s_ in self._streams:
+                        ul_easy.record_stream(s_)                       # made on the caller's stream, read by both networks' streams
+            o1, o2 = self._fwd_pair((ul_easy,), (ul_easy,), use_amp=cfg.eval_amp, models=self.teachers if cfg.teacher_pseudo_labels else None)
             score_1, score_2 = o1[0], o2[0]
             if not split:
                 self._join()
@@ -515,6 +541,14 @@ class CPSTrainer:
                 score_1 = score_1.float()
             with on(1):
                 score_2 = score_2.float()
+            if cfg.easy_aug is not None:
+                # back into the clean frame, each score map on the stream that made it; from here on the step is the existing one
+                back = augmentations.similarity_matrices(easy_codes, easy_angles, inverse=True)
+                easy_1, easy_2 = score_1, score_2
+                with on(0):
+                    score_1 = augmentations.warp_batch(easy_1, back)
+                with on(1):
+                    score_2 = augmentations.warp_batch(easy_2, back)
             m1.train(); m2.train()
             ul_train = ul_input
             if cfg.cutmix_ratio is not None:
@@ -610,6 +644,10 @@ class CPSTrainer:
                 if split:
                     clean_1.record_stream(main), clean_2.record_stream(main)
                 self.aux.update(score_1=clean_1, score_2=clean_2, ul_mixed=ul_train, score_1_mixed=score_1, score_2_mixed=score_2, boxes=list(boxes))
+            if cfg.easy_aug is not None:                                # score_1 / score_2 are the maps in the clean frame; the forwards' own beside them
+                if split:
+                    easy_1.record_stream(main), easy_2.record_stream(main)
+                self.aux.update(ul_easy=ul_easy, easy_codes=list(easy_codes), easy_angles=list(easy_angles), score_1_easy=easy_1, score_2_easy=easy_2)
         lr = self.sched.get_lr(self.iter)
         for o in self.opts:
             o.param_groups[0]["lr"] = lr

@@ -5,6 +5,7 @@
   * distributed k-means init: rank 0's initial means are broadcast and per-iteration sums/counts are
     all-reduced, so two ranks holding half the rows each reproduce single-process Lloyd on all rows.
     (The per-rank accumulate kernel is replaced by the CPU oracle here: no GPU in this test.)
+  * the trainer's stream helper with the lanes off (its CPU path), and the old import home of what moved out of trainer.py.
 """
 import os
 import socket
@@ -170,3 +171,31 @@ def test_initial_broadcast_is_flat_and_dp_resume_keeps_per_rank_bn_statistics():
     out = spawn(_flat_broadcast_and_resume_job)
     assert torch.equal(out[0][0], out[1][0])                 # every rank starts from rank 0's parameters and buffers
     assert out[0][1] and out[1][1]                           # ranks > 0 get THEIR OWN running statistics back on resume
+
+
+def test_stream_lanes_off_do_nothing_and_moved_names_keep_their_old_home():
+    """lanes.Lanes with the lanes off (the CPU path of the trainer): on(k) is a null context, every dependency call returns
+    without touching a stream; and what left trainer.py is the same object under its old name."""
+    import contextlib
+    import vq_seg_amd.data
+    from vq_seg_amd import grad_buckets, lanes, trainer
+    from vq_seg_amd.data import synthetic
+    for L in (lanes.Lanes(torch.device("cpu")), lanes.OFF):
+        assert not L.enabled and L.streams == [] and L.sides == [] and L.producers(0) == []
+        a, b = torch.ones(3), torch.zeros(3)
+        with L.on(0) as got:
+            ran = torch.is_grad_enabled()
+        assert got is None and ran
+        with L.on(1), contextlib.nullcontext():                  # nests like any context manager
+            pass
+        with pytest.raises(KeyError):                            # and does not swallow what is raised inside
+            with L.on(0):
+                raise KeyError("x")
+        assert L.fork() is None and L.fork(0, sides=True) is None
+        assert L.share(a) is None and L.mark() is None
+        assert L.exchange(a, b) is None and L.exchange(a, b, marks=L.mark()) is None
+        assert L.hold(0) is None and L.to_caller(a, (a, b), None) is None
+        assert L.join() is None and L.join(0, 1, sides=True) is None and L.wgrad_sides(True) is None and L.wgrad_sides(False) is None
+        assert torch.equal(a, torch.ones(3)) and torch.equal(b, torch.zeros(3))
+    assert trainer.GradBuckets is grad_buckets.GradBuckets and trainer.broadcast_module_state is grad_buckets.broadcast_module_state
+    assert trainer.SyntheticCropWeed is synthetic.SyntheticCropWeed is vq_seg_amd.data.SyntheticCropWeed

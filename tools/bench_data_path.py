@@ -2,7 +2,7 @@
 32 labelled + 32 unlabelled images, CPSTrainer) driven by the reference's loop (train_vqreptunet1x1v2.py:89-90,118,130-139:
 zip(cycle(sup_loader), unsup_loader), img_to_label, .to(device)) over a synthetic folder of CWFID-sized 1296 x 966 PNGs, fed by
 
-    synthetic   tensors already in HBM (trainer.SyntheticCropWeed, what bench.py times)
+    synthetic   tensors already in HBM (data.synthetic.SyntheticCropWeed, what bench.py times)
     device      vq_seg_amd.data.DeviceLoader (cache built once; one assembly kernel per batch)
     workers     DataLoader(BaseDataset, num_workers=...): min(16, CPUs of this process) workers in all, half per loader
                 (spawned processes; persistent across epochs)

@@ -69,7 +69,7 @@ class BaseDataset(Dataset):
 def write_synthetic_dataset(data_dir: str, n_labelled: int, n_unlabelled: int, size: int = 64, seed: int = 0, cell: int = 8,
                             pixel_values=(0, 128, 255)):
     """A CWFID-shaped folder of synthetic crop / weed blobs: class k's mask pixels carry pixel_values[k] (the reference configs'
-    `pixel_to_label` {"0": 0, "128": 1, "255": 2}), images are the class colours + noise (same recipe as trainer.SyntheticCropWeed).
+    `pixel_to_label` {"0": 0, "128": 1, "255": 2}), images are the class colours + noise (same recipe as data.synthetic.SyntheticCropWeed).
     `size`: an int for square files, or (w, h) -- PIL's order, as `resize` -- for non-square ones (e.g. CWFID's 1296 x 966)."""
     rng = np.random.default_rng(seed)
     palette = np.array([[0.25, 0.20, 0.15], [0.20, 0.55, 0.25], [0.55, 0.60, 0.20]])

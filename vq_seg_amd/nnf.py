@@ -391,7 +391,7 @@ def _out_size(h, k, s, p):
 
 
 # ------------------------------------------------------------------------------------------------
-# Gradient sinks.  A trainer that owns the parameters' .grad storage (trainer.GradBuckets: flat fp32 buckets) marks a
+# Gradient sinks.  A trainer that owns the parameters' .grad storage (grad_buckets.GradBuckets: flat fp32 buckets) marks a
 # parameter with `p._vq_grad_sink = callback-or-None`; the weight-gradient kernels then ADD into p.grad themselves
 # (`accumulate` flag of the C entry points) and autograd gets None for that parameter -- one tiny add kernel per
 # parameter and backward pass less.  The callback (if any) is told, as a post-accumulate-grad hook would be.

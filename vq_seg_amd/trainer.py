@@ -10,17 +10,19 @@ wandb / image dumps of the reference trainer are out of scope.
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Union
 
-import contextlib
 import torch
 import torch.distributed as dist
-import torch.nn.functional as F
 from torch import nn
 
 from . import dist as vdist
 from .data import augmentations
+from .data.synthetic import SyntheticCropWeed  # noqa: F401  (its home; imported from here by the benchmark, tools and tests)
+from .grad_buckets import GradBuckets, broadcast_module_state
+from .lanes import OFF, Lanes
 from .loss import compute_class_weight, cross_entropy, make_loss
 from .loss.dice_loss import DiceLoss, ce_dice_loss, dice_loss
 from .loss.focal_loss import FocalLoss
@@ -31,160 +33,10 @@ from .evaluate import test_loop
 from .models import init_weight
 from .models.networks import make_model
 from .optim import HipAdam
-from .utils.ckpoints import load_training_state, restore_initted, save_ckpoints
+from .utils.ckpoints import gather_rank_buffers, load_training_state, restore_initted, restore_rank_buffers, save_ckpoints
 from .utils.lr_schedulers import CosineAnnealingLR
 
 
-# ----------------------------------------------------------------------------------------------
-# gradient all-reduce: flat fp32 buckets, launched from post-accumulate hooks while backward runs
-# ----------------------------------------------------------------------------------------------
-class GradBuckets:
-    """Owns the .grad storage of `params` as views into a few flat buffers ("buckets", filled in
-    reverse parameter order = the order backward produces them).  With world_size > 1 each bucket is
-    all-reduced (sum, then scaled by 1/world) as soon as all its gradients have been accumulated."""
-
-    def __init__(self, params: List[nn.Parameter], bucket_mb: float = 64.0):
-        self.params = [p for p in params if p.requires_grad]
-        self.world = vdist.world_size()
-        self.on = vdist.collectives_on()                   # world > 1, or the single-rank RCCL drive (VQSEG_DIST_SINGLE)
-        cap = int(bucket_mb * (1 << 20) / 4)
-        self.buckets: List[torch.Tensor] = []
-        self.owner: Dict[int, int] = {}
-        groups, cur, cur_n = [], [], 0
-        for p in reversed(self.params):
-            if cur and cur_n + p.numel() > cap:
-                groups.append(cur)
-                cur, cur_n = [], 0
-            cur.append(p)
-            cur_n += p.numel()
-        if cur:
-            groups.append(cur)
-        for bi, g in enumerate(groups):
-            flat = torch.zeros(sum(p.numel() for p in g), dtype=torch.float32, device=g[0].device)
-            off = 0
-            for p in g:
-                p.grad = flat[off:off + p.numel()].view_as(p)
-                off += p.numel()
-                self.owner[id(p)] = bi
-            self.buckets.append(flat)
-        self._sizes = [len(g) for g in groups]
-        self._pending = list(self._sizes)
-        self._launched = [False] * len(groups)
-        self._handles = []
-        self._reported = set()
-        # parameters that never report a gradient (the frozen codebooks -- vq_img.py:236-239 -- and, in the v1 model, the prototypes
-        # that enter through `.data`, prototype.py:556) would keep their buckets from ever completing inside backward: they are
-        # learnt on the first step (whoever has not reported by finish()) and left out of the count from then on
-        self._silent = None
-        self._names = {}
-        self.launched_in_backward = []                     # per step: which buckets were reduced from inside backward (tests, DESIGN 6)
-        self.launch_sequence: List[int] = []               # the order this step's bucket all-reduces were issued in (must be the same on
-                                                           # every rank: bench.py / tests compare it across ranks)
-        # RCCL has an averaging reduction; gloo (CPU tests, rehearsal) does not: sum, then scale
-        self._avg = dist.ReduceOp.AVG if (self.on and dist.get_backend() == "nccl") else None
-        self.producer_streams = []          # set by CPSTrainer: the side stream(s) the gradient kernels of these params run on
-        for p in self.params:
-            # the HIP weight-gradient kernels add straight into the bucket views (nnf grad sinks) and report here;
-            # parameters whose gradient still comes from autograd (VQ-free torch ops) report through the hook
-            p._vq_grad_sink = self._on_grad if self.on else None
-            if self.on:
-                p.register_post_accumulate_grad_hook(self._on_grad)
-
-    def zero(self):
-        for b in self.buckets:
-            b.zero_()
-        for p in self.params:
-            p._vq_uses = 0
-        self._pending = list(self._sizes)
-        if self._silent:
-            for pid in self._silent:
-                self._pending[self.owner[pid]] -= 1
-        self._launched = [False] * len(self.buckets)
-        self._handles = []
-        self._reported = set()
-        self.launch_sequence = []
-
-    def _launch(self, bi):
-        self._launched[bi] = True
-        self.launch_sequence.append(bi)
-        # The collective orders itself after the CURRENT stream only.  The last gradient of a bucket may report from an
-        # autograd hook running on another stream than the one the HIP weight-gradient kernels wrote the rest of the bucket
-        # on, so order the current stream after everything those streams hold so far (all of this bucket's gradients).
-        if self.producer_streams and self.buckets[bi].is_cuda:
-            cur = torch.cuda.current_stream(self.buckets[bi].device)
-            for s in self.producer_streams:
-                if s != cur:
-                    cur.wait_stream(s)
-        self._handles.append(dist.all_reduce(self.buckets[bi], op=self._avg or dist.ReduceOp.SUM, async_op=True))
-
-    def _on_grad(self, p):
-        # A sunk parameter reports through its sink (last contribution) AND, later, through the post-accumulate hook
-        # (autograd runs AccumulateGrad for it with an undefined gradient): count every parameter once per step.
-        if id(p) in self._reported:
-            return
-        self._reported.add(id(p))
-        bi = self.owner[id(p)]
-        if self._silent and id(p) in self._silent:
-            if self._launched[bi]:
-                raise RuntimeError("a parameter classified as gradient-free on the first step produced a gradient after its bucket had "
-                                   "been reduced; call GradBuckets.relearn() when the set of trained parameters changes")
-            self._silent.discard(id(p))                    # it does report after all: count it again from the next step on
-            return
-        self._pending[bi] -= 1
-        if self._pending[bi] == 0 and not self._launched[bi]:
-            self._launch(bi)
-
-    def finish(self):
-        """Call after backward: reduce what is left (parameters without a gradient this step keep
-        their bucket from completing), wait, average."""
-        if not self.on:
-            return
-        self.launched_in_backward = list(self._launched)
-        if self._silent is None:
-            self._silent = {id(p) for p in self.params if id(p) not in self._reported}
-        for bi in range(len(self.buckets)):
-            if not self._launched[bi]:
-                self._launch(bi)
-        for h in self._handles:
-            h.wait()
-        if self._avg is None:                              # gloo: no averaging reduction
-            for b in self.buckets:
-                b.mul_(1.0 / self.world)
-
-    def relearn(self):
-        """forget which parameters are gradient-free (after freezing / unfreezing parts of the model)"""
-        self._silent = None
-
-
-# ----------------------------------------------------------------------------------------------
-# synthetic data (no dataset is available offline; shapes and value ranges of data/dataset.py:41-62)
-# ----------------------------------------------------------------------------------------------
-class SyntheticCropWeed:
-    """Images: learnable colour-coded blobs + noise in [0,1] (TF.to_tensor range, no mean/std
-    normalisation, q14); labels: class ids 0/1/2 (post `img_to_label`).  Deterministic per (seed, rank)."""
-
-    def __init__(self, size: int, batch: int, device, seed: int = 42, cell: int = 32, num_classes: int = 3):
-        self.size, self.batch, self.device, self.cell, self.nc = size, batch, device, cell, num_classes
-        self.gen = torch.Generator(device="cpu")
-        self.gen.manual_seed(seed * 1000 + vdist.rank())
-        self.palette = torch.tensor([[0.25, 0.20, 0.15], [0.20, 0.55, 0.25], [0.55, 0.60, 0.20]])
-
-    def _one(self):
-        low = max(self.size // self.cell, 1)
-        lab = torch.randint(0, self.nc, (self.batch, 1, low, low), generator=self.gen).float()
-        lab = F.interpolate(lab, size=(self.size, self.size), mode="nearest")[:, 0].long()
-        img = self.palette[lab].permute(0, 3, 1, 2) + 0.15 * torch.rand(self.batch, 3, self.size, self.size, generator=self.gen)
-        return img.clamp_(0, 1), lab
-
-    def labelled(self):
-        img, lab = self._one()
-        return img.to(self.device, non_blocking=True), lab.to(self.device, non_blocking=True)
-
-    def unlabelled(self):
-        return self._one()[0].to(self.device, non_blocking=True)
-
-
-# ----------------------------------------------------------------------------------------------
 @dataclass
 class CPSConfig:
     model: dict
@@ -260,21 +112,6 @@ class CPSConfig:
             raise ValueError(f"class_weight: one weight per class required ({self.num_classes}), got {len(self.class_weight)}")
 
 
-def broadcast_module_state(m: nn.Module, src: int = 0) -> None:
-    """rank `src`'s parameters and buffers to every rank: ONE broadcast per dtype over a flat copy (r3 issued ~750 per-tensor
-    broadcasts per network)."""
-    by_dtype: Dict[torch.dtype, List[torch.Tensor]] = {}
-    for t in list(m.parameters()) + list(m.buffers()):
-        by_dtype.setdefault(t.dtype, []).append(t.data)
-    for ts in by_dtype.values():
-        flat = torch.cat([t.reshape(-1) for t in ts])
-        dist.broadcast(flat, src=src)
-        off = 0
-        for t in ts:
-            t.copy_(flat[off:off + t.numel()].view_as(t))
-            off += t.numel()
-
-
 def regularized_pseudo_label(raw: torch.Tensor, percent: float) -> torch.Tensor:
     """make_regularized_pseudo_label (deprecated/train_with_test_pt_pseudo_entropy_reg.py:30-39) with
     the percentile taken on the device (np.percentile's linear interpolation between two order statistics)."""
@@ -333,23 +170,14 @@ class CPSTrainer:
         for m in self.models:
             m.async_code_usage = True                     # no host sync inside forward (usage is read after the step)
         self.buckets = [GradBuckets(list(m.parameters()), cfg.bucket_mb) for m in self.models]
-        # the two networks of a CPS pair are independent until the loss: each runs on its own HIP stream so that one
+        # the two networks of a CPS pair are independent until the loss: each runs on its own HIP stream (lanes.Lanes) so that one
         # model's small, latency-bound kernels (statistics merges, reductions, packs) hide under the other's large ones
-        import os as _os
-        self._two_streams = device.type == "cuda" and cfg.two_streams and _os.environ.get("VQSEG_TWO_STREAMS", "1") == "1"
+        two = device.type == "cuda" and cfg.two_streams and os.environ.get("VQSEG_TWO_STREAMS", "1") == "1"
         prio = nnf.py_opt("py_stream_prio", 0) if device.type == "cuda" else 0      # A/B: 1 = the networks' streams above the weight-gradient side streams
-        self._streams = [torch.cuda.Stream(device, priority=-1 if prio == 1 else 0) for _ in self.models] if self._two_streams else []
-        # weight-gradient kernels (+ their slab sums) run on a side stream per network (nnf.WGRAD_SIDE_STREAMS): nothing later in
-        # backward depends on them, so they fill the chip under the latency-bound links of the main chain.  They add into the
-        # buckets, so the side streams are producer streams of the buckets and are joined before the optimiser step.
-        self._wgrad_streams = []
-        if self._two_streams and cfg.wgrad_side_stream and nnf.py_opt("py_wgrad_side", 1):
-            self._wgrad_streams = [torch.cuda.Stream(device, priority=-1 if prio == 2 else 0) for _ in self.models]
-        for b, s_ in zip(self.buckets, self._streams):
-            b.producer_streams = [s_]
-        for b, s_, w_ in zip(self.buckets, self._streams, self._wgrad_streams):
-            b.producer_streams.append(w_)
-        self._pending_sides = set()
+        self.lanes = Lanes(device, len(self.models), two, bool(two and cfg.wgrad_side_stream and nnf.py_opt("py_wgrad_side", 1)), prio)
+        self._glue = OFF                                  # where the glue between the forwards runs this step: see step()
+        for k, b in enumerate(self.buckets):
+            b.producer_streams = self.lanes.producers(k)
         # the reference's optimiser (train_vqreptunet1x1v2.py:106-107) on the HIP step kernel: Adam + the convolution kernels' weight
         # images in one launch per network (optim.HipAdam IS a torch.optim.Adam: same state / state_dict layout)
         self.opts = [HipAdam(m.parameters(), lr=cfg.learning_rate, betas=(0.9, 0.999)) if self.device.type == "cuda" and nnf.py_opt("py_hip_adam", 1)
@@ -377,110 +205,62 @@ class CPSTrainer:
             self.criterion.alpha, self.criterion.gamma = cfg.focal_alpha, cfg.focal_gamma
         self.iter = 0
 
-    # -- one model forward under the configured precision
-    def _fwd(self, model, *a, **kw):
-        side = self._side_stream(model)
-        if side is None:
-            return self._fwd_here(model, *a, **kw)
-        main = torch.cuda.current_stream()
-        side.wait_stream(main)                                          # inputs / zeroed buckets come from the caller's stream
-        with torch.cuda.stream(side):
-            out = self._fwd_here(model, *a, **kw)
-        for t in out:
-            if torch.is_tensor(t) and t.is_cuda:
-                t.record_stream(main)                                   # consumed on the caller's stream
-        self._pending_sides.add(side)
-        return out
+    @property
+    def _two_streams(self) -> bool:
+        """whether the networks run on their own streams; assignable on a live trainer (tools run single-stream sections), read
+        at the start of every step and forward pair"""
+        return self.lanes.enabled
+
+    @_two_streams.setter
+    def _two_streams(self, on: bool):
+        self.lanes.enabled = on
 
     def _fwd_pair(self, a1, a2, use_amp=True, models=None, **kw):
         """model 1 on a1 = (x[, gt]) and model 2 on a2, phase by phase: encoders overlap on the two streams, the VQ phases
         run one after the other with the other stream idle (the distance kernels fill the GPU on their own, and their
         in-stream timing -- bench.py's roofline -- then measures the kernel, not the sharing), decoders overlap again.
+        One stream or two, the phases are enqueued in this order (also the order of the RNG draws of the k-means inits).
         `use_amp=False`: this pair runs outside autocast whatever cfg.amp_dtype says (the pseudo-label passes).
         `models`: the pair of modules to run (the teachers, for their pseudo labels), on the same streams; default the students."""
         m1, m2 = models or self.models
-        amp = self.cfg.amp_dtype if use_amp else None
+        L, amp = self.lanes, self.cfg.amp_dtype if use_amp else None
 
-        def on(stream, fn, *args, **kws):
-            if stream is None:
-                if amp is None:
-                    return fn(*args, **kws)
-                with torch.autocast("cuda", dtype=amp):
-                    return fn(*args, **kws)
-            with torch.cuda.stream(stream):
-                if amp is None:
-                    return fn(*args, **kws)
-                with torch.autocast("cuda", dtype=amp):
-                    return fn(*args, **kws)
+        def run(k, fn, *args, **kws):
+            with L.on(k, amp):
+                return fn(*args, **kws)
 
-        if not self._two_streams:                                       # same phase order (also the order of the RNG draws
-            f1, f2 = on(None, m1.encode, a1[0]), on(None, m2.encode, a2[0])   # of the k-means inits) on one stream
-            q1, q2 = on(None, m1.quantize, f1), on(None, m2.quantize, f2)
-            return on(None, m1.finish, *q1, *a1[1:], **kw), on(None, m2.finish, *q2, *a2[1:], **kw)
-        main = torch.cuda.current_stream()
-        s1, s2 = self._streams
-        s1.wait_stream(main)
-        s2.wait_stream(main)
-        f1 = on(s1, m1.encode, a1[0])
-        f2 = on(s2, m2.encode, a2[0])
-        alone = nnf.py_opt("py_vq_alone", 1)                            # 0 (A/B runs): the VQ phases share the chip like everything else
+        L.fork()
+        f1, f2 = run(0, m1.encode, a1[0]), run(1, m2.encode, a2[0])
+        alone = L.enabled and nnf.py_opt("py_vq_alone", 1)              # 0 (A/B runs): the VQ phases share the chip like everything else
         if alone:
-            s1.wait_event(s2.record_event())                            # model 2's encoder done before model 1 quantises
-        q1 = on(s1, m1.quantize, f1)
+            L.hold(0)                                                   # model 2's encoder done before model 1 quantises
+        q1 = run(0, m1.quantize, f1)
         if alone:
-            s2.wait_event(s1.record_event())
-        q2 = on(s2, m2.quantize, f2)
+            L.hold(1)
+        q2 = run(1, m2.quantize, f2)
         if alone:
-            s1.wait_event(s2.record_event())                            # ... and model 1 stays idle meanwhile
-        o1 = on(s1, m1.finish, *q1, *a1[1:], **kw)
-        o2 = on(s2, m2.finish, *q2, *a2[1:], **kw)
-        for t in tuple(o1) + tuple(o2):
-            if torch.is_tensor(t) and t.is_cuda:
-                t.record_stream(main)
-        self._pending_sides.update((s1, s2))
+            L.hold(0)                                                   # ... and model 1 stays idle meanwhile
+        o1, o2 = run(0, m1.finish, *q1, *a1[1:], **kw), run(1, m2.finish, *q2, *a2[1:], **kw)
+        L.to_caller(*o1, *o2)
         return o1, o2
 
     def _join(self):
         """the caller's stream waits for everything queued on the per-model streams"""
-        main = torch.cuda.current_stream()
-        for s_ in self._pending_sides:
-            main.wait_stream(s_)
-        self._pending_sides.clear()
-
-    def _wgrad_sides(self, on: bool):
-        """register / unregister the weight-gradient side streams with nnf for the duration of a backward pass"""
-        for s_, w_ in zip(self._streams, self._wgrad_streams):
-            if on and self._two_streams:
-                nnf.WGRAD_SIDE_STREAMS[s_.cuda_stream] = w_
-            else:
-                nnf.WGRAD_SIDE_STREAMS.pop(s_.cuda_stream, None)
-
-    def _side_stream(self, model):
-        if not self._two_streams:
-            return None
-        return self._streams[self.models.index(model)]
-
-    def _fwd_here(self, model, *a, **kw):
-        if self.cfg.amp_dtype is None:
-            return model(*a, **kw)
-        with torch.autocast("cuda", dtype=self.cfg.amp_dtype):
-            return model(*a, **kw)
+        self.lanes.join()
 
     def step(self, l_input, l_target, ul_input, epoch_frac: float = 0.0) -> Dict[str, torch.Tensor]:
         """One CPS iteration on B labelled + B unlabelled images (6 forwards, 4 backwards per pair of
         models).  Returns device scalars (no host sync)."""
-        cfg = self.cfg
-        m1, m2 = self.models
-        if self._two_streams and l_input.is_cuda and nnf.py_opt("py_loss_streams", 1) == 1:
-            # each network's buckets are written by ITS stream's backward: zeroed there too, under the first forward's kernels
-            main = torch.cuda.current_stream()
-            for b, s_ in zip(self.buckets, self._streams):
-                s_.wait_stream(main)
-                with torch.cuda.stream(s_):
-                    b.zero()
-                self._pending_sides.add(s_)
-        else:
-            for b in self.buckets:
+        # r4: the glue between the forwards -- bucket zeroing, pseudo-label targets, the loss block -- runs on the two networks' OWN
+        # streams (what network k's stream produced is consumed there; the one exchange is the other network's mask / target, an event
+        # each way) instead of joining both streams into the caller's and running ~150 small kernels there with the chip idle (measured
+        # on a kernel trace: 3.2 ms of a 152 ms step).  Same operations, same operands, same order per network.  Decided here, once
+        # per step; py_loss_streams=0 (A/B) leaves the forwards on the lanes and runs the glue on the caller's stream after a join.
+        on_lanes = self.lanes.enabled and l_input.is_cuda and nnf.py_opt("py_loss_streams", 1) == 1
+        self._glue = g = self.lanes if on_lanes else OFF
+        g.fork()
+        for k, b in enumerate(self.buckets):                            # each network's buckets are written by ITS stream's backward:
+            with g.on(k):                                               # zeroed there too, under the first forward's kernels
                 b.zero()
         nnf.drop_pending_wgrads()
         if l_input.is_cuda:
@@ -499,211 +279,212 @@ class CPSTrainer:
             nnf.stem_share_end()
 
     def _step(self, l_input, l_target, ul_input, epoch_frac):
+        """the phases of a step, in order; each adds what it has in scope to `self.aux` (cfg.keep_aux)"""
         cfg = self.cfg
+        if cfg.keep_aux:
+            self.aux = {}
+        score_1, score_2 = self._pseudo_scores(ul_input)
+        ul_train, score_1, score_2 = self._cutmix(ul_input, score_1, score_2)
+        gt_ul_1, gt_ul_2, kw = self._targets(score_1, score_2, epoch_frac)
+        sup, unsup = self._train_forwards(l_input, l_target, ul_train, gt_ul_1, gt_ul_2, kw)
+        fused, ps1, sup_terms, cps_terms = self._terms(l_target, sup, unsup, score_1, score_2, kw)
+        lr = self.sched.get_lr(self.iter)
+        for o in self.opts:
+            o.param_groups[0]["lr"] = lr
+        loss, terms = self._total_loss(fused, sup_terms, cps_terms, [o[1] for o in sup + unsup], [o[3] for o in sup + unsup])
+        self._backward_and_step(loss)
+        self.iter += 1
+        with torch.no_grad():
+            miou, _ = miou_device(confusion_matrix_device(ps1, l_target, cfg.num_classes))
+        self._join()
+        return {"loss": loss.detach(), **{k: v.detach() for k, v in terms.items()}, "miou": miou, "lr": torch.tensor(lr)}
+
+    @torch.no_grad()
+    def _pseudo_scores(self, ul_input):
+        """The two eval forwards (students, or teachers) over the unlabelled batch -> score_1, score_2 in fp32, each on its
+        network's stream.  With the easy augmentation the forwards see the warped batch and the scores are warped back, so
+        what is returned is always in the clean frame."""
+        cfg, g = self.cfg, self._glue
         m1, m2 = self.models
-        # r4: the glue between the forwards -- pseudo-label targets, the loss block -- runs on the two networks' OWN streams (what
-        # network k's stream produced is consumed there; the one exchange is the other network's mask / target, an event each way)
-        # instead of joining both streams into the caller's and running ~150 small kernels there with the chip idle (measured on a
-        # kernel trace: 3.2 ms of a 152 ms step).  Same operations, same operands, same order per network.
-        split = self._two_streams and nnf.py_opt("py_loss_streams", 1) == 1
-        streams = self._streams if split else (None, None)
-        main = torch.cuda.current_stream() if l_input.is_cuda else None
-
-        def on(k):
-            return torch.cuda.stream(streams[k]) if split else contextlib.nullcontext()
-
-        def exchange(t_from_1, t_from_2):
-            """network 1's stream may read t_from_2 (made on network 2's stream) and vice versa"""
-            if split:
-                e1, e2 = streams[0].record_event(), streams[1].record_event()
-                streams[0].wait_event(e2)
-                streams[1].wait_event(e1)
-                t_from_2.record_stream(streams[0])
-                t_from_1.record_stream(streams[1])
-
-        with torch.no_grad():                                           # pseudo labels from eval passes
-            m1.eval(); m2.eval()
-            ul_easy = ul_input
-            if cfg.easy_aug is not None:
-                # easy augmentation: the step's transforms on the host, a pure function of (seed, rank, iteration[, sample]) under a key of
-                # their own (the CutMix boxes of the step do not move).  The images are warped ONCE on the caller's stream, for both networks
-                easy_codes, easy_angles = augmentations.step_transforms(ul_input.shape[0], cfg.seed, vdist.rank(), self.iter, cfg.easy_aug_per,
-                                                                        cfg.easy_aug_codes, cfg.easy_aug_max_angle)
-                ul_easy = augmentations.warp_batch(ul_input, augmentations.similarity_matrices(easy_codes, easy_angles))
-                if self._two_streams and ul_easy.is_cuda:
-                    for s_ in self._streams:
-                        ul_easy.record_stream(s_)                       # made on the caller's stream, read by both networks' streams
-            o1, o2 = self._fwd_pair((ul_easy,), (ul_easy,), use_amp=cfg.eval_amp, models=self.teachers if cfg.teacher_pseudo_labels else None)
-            score_1, score_2 = o1[0], o2[0]
-            if not split:
-                self._join()
-            with on(0):
-                score_1 = score_1.float()
-            with on(1):
-                score_2 = score_2.float()
-            if cfg.easy_aug is not None:
-                # back into the clean frame, each score map on the stream that made it; from here on the step is the existing one
-                back = augmentations.similarity_matrices(easy_codes, easy_angles, inverse=True)
-                easy_1, easy_2 = score_1, score_2
-                with on(0):
-                    score_1 = augmentations.warp_batch(easy_1, back)
-                with on(1):
-                    score_2 = augmentations.warp_batch(easy_2, back)
-            m1.train(); m2.train()
-            ul_train = ul_input
-            if cfg.cutmix_ratio is not None:
-                # CutMix: boxes on the host, a pure function of (seed, rank, iteration[, sample]) -- no generator state to checkpoint, nothing
-                # taken from the global generators.  The images are mixed ONCE (both networks get the same tensor object: one stem patch
-                # matrix), each score map on the stream that made it, before anything derives a pseudo label from it; from here on the
-                # step is the plain one on mixed scores and, for the two training forwards, mixed images.
-                boxes = augmentations.step_boxes(ul_input.shape[0], ul_input.shape[-2], ul_input.shape[-1], cfg.cutmix_ratio, cfg.seed,
-                                                 vdist.rank(), self.iter, cfg.cutmix_boxes)
-                clean_1, clean_2 = score_1, score_2
-                ul_train = augmentations.mix_boxes(ul_input, boxes)
-                if split:
-                    for s_ in streams:
-                        ul_train.record_stream(s_)                      # made on the caller's stream, read by both networks' streams
-                with on(0):
-                    score_1 = augmentations.mix_boxes(clean_1, boxes)
-                with on(1):
-                    score_2 = augmentations.mix_boxes(clean_2, boxes)
-        if cfg.recipe == "v1":
-            percent = 100 - cfg.unsup_loss_drop_percent * (1 - epoch_frac)
-            kw = dict(percent=percent)
-            with on(1):
-                gt_ul_1 = _argmax_classes(score_2)
-            with on(0):
-                gt_ul_2 = _argmax_classes(score_1)
-        else:
-            kw = dict(th=cfg.confidence_threshold)
-            gt_ul_1, gt_ul_2 = score_2, score_1
-        if split:                                                       # targets ready: the events the OTHER network's unlabelled forward waits for
-            e_gt = (streams[1].record_event(), streams[0].record_event())       # (gt_ul_1 on network 2's stream, gt_ul_2 on network 1's)
-        (ps1, c_l1, _u, p_l1), (ps2, c_l2, _u, p_l2) = self._fwd_pair((l_input, l_target), (l_input, l_target), **kw)
-        if split:
-            streams[0].wait_event(e_gt[0])
-            streams[1].wait_event(e_gt[1])
-            gt_ul_1.record_stream(streams[0])
-            gt_ul_2.record_stream(streams[1])
-        (pu1, c_u1, _u, p_u1), (pu2, c_u2, usage, p_u2) = self._fwd_pair((ul_train, gt_ul_1), (ul_train, gt_ul_2), **kw)
-        if not split:
+        m1.eval(); m2.eval()
+        ul_easy = ul_input
+        if cfg.easy_aug is not None:
+            # easy augmentation: the step's transforms on the host, a pure function of (seed, rank, iteration[, sample]) under a key of
+            # their own (the CutMix boxes of the step do not move).  The images are warped ONCE on the caller's stream, for both networks
+            codes, angles = augmentations.step_transforms(ul_input.shape[0], cfg.seed, vdist.rank(), self.iter, cfg.easy_aug_per,
+                                                          cfg.easy_aug_codes, cfg.easy_aug_max_angle)
+            ul_easy = augmentations.warp_batch(ul_input, augmentations.similarity_matrices(codes, angles))
+            self.lanes.share(ul_easy)
+        o1, o2 = self._fwd_pair((ul_easy,), (ul_easy,), use_amp=cfg.eval_amp, models=self.teachers if cfg.teacher_pseudo_labels else None)
+        if g is OFF:
             self._join()
-        crit = self.criterion if cfg.recipe == "v1" else self._ce_dice
+        with g.on(0):
+            score_1 = o1[0].float()
+        with g.on(1):
+            score_2 = o2[0].float()
+        if cfg.easy_aug is not None:
+            # back into the clean frame, each score map on the stream that made it; from here on the step is the plain one
+            back = augmentations.similarity_matrices(codes, angles, inverse=True)
+            easy_1, easy_2 = score_1, score_2
+            with g.on(0):
+                score_1 = augmentations.warp_batch(easy_1, back)
+            with g.on(1):
+                score_2 = augmentations.warp_batch(easy_2, back)
+            if cfg.keep_aux:                                            # the forwards' own maps beside the clean-frame ones
+                self.aux.update(ul_easy=ul_easy, easy_codes=list(codes), easy_angles=list(angles), score_1_easy=easy_1, score_2_easy=easy_2)
+                g.to_caller(easy_1, easy_2)
+        m1.train(); m2.train()
+        if cfg.keep_aux:                                                # the clean-frame maps, before any mixing
+            self.aux.update(score_1=score_1, score_2=score_2)
+            g.to_caller(score_1, score_2)
+        return score_1, score_2
+
+    @torch.no_grad()
+    def _cutmix(self, ul_input, score_1, score_2):
+        """-> the images of the two unlabelled training forwards and the score maps the pseudo labels come from: box-mixed with
+        the same boxes (cfg.cutmix_ratio), or as they came."""
+        cfg, g = self.cfg, self._glue
+        if cfg.cutmix_ratio is None:
+            return ul_input, score_1, score_2
+        # boxes on the host, a pure function of (seed, rank, iteration[, sample]) -- no generator state to checkpoint, nothing taken
+        # from the global generators.  The images are mixed ONCE (both networks get the same tensor object: one stem patch matrix),
+        # each score map on the stream that made it, before anything derives a pseudo label from it; from here on the step is the
+        # plain one on mixed scores and, for the two training forwards, mixed images.
+        boxes = augmentations.step_boxes(ul_input.shape[0], ul_input.shape[-2], ul_input.shape[-1], cfg.cutmix_ratio, cfg.seed,
+                                         vdist.rank(), self.iter, cfg.cutmix_boxes)
+        ul_train = augmentations.mix_boxes(ul_input, boxes)
+        g.share(ul_train)
+        with g.on(0):
+            mixed_1 = augmentations.mix_boxes(score_1, boxes)
+        with g.on(1):
+            mixed_2 = augmentations.mix_boxes(score_2, boxes)
+        if cfg.keep_aux:                                                # what the step used, beside the clean maps
+            self.aux.update(ul_mixed=ul_train, score_1_mixed=mixed_1, score_2_mixed=mixed_2, boxes=list(boxes))
+        return ul_train, mixed_1, mixed_2
+
+    def _targets(self, score_1, score_2, epoch_frac):
+        """-> gt_ul_1, gt_ul_2 (each network's unlabelled target comes from the OTHER network's scores, made on that network's
+        stream) and the recipe's keyword of the training forwards"""
+        cfg, g = self.cfg, self._glue
+        if cfg.recipe != "v1":
+            return score_2, score_1, dict(th=cfg.confidence_threshold)
+        with g.on(1):
+            gt_ul_1 = _argmax_classes(score_2)
+        with g.on(0):
+            gt_ul_2 = _argmax_classes(score_1)
+        return gt_ul_1, gt_ul_2, dict(percent=100 - cfg.unsup_loss_drop_percent * (1 - epoch_frac))
+
+    def _train_forwards(self, l_input, l_target, ul_train, gt_ul_1, gt_ul_2, kw):
+        """the labelled and the unlabelled training forward pair -> ((out_1, out_2), (out_1, out_2)), out = (pred, commitment,
+        usage, prototype).  The targets cross lanes: as of now (they are ready), waited for only before the unlabelled pair."""
+        g = self._glue
+        ready = g.mark()
+        sup = self._fwd_pair((l_input, l_target), (l_input, l_target), **kw)
+        g.exchange(gt_ul_2, gt_ul_1, marks=ready)
+        unsup = self._fwd_pair((ul_train, gt_ul_1), (ul_train, gt_ul_2), **kw)
+        if g is OFF:
+            self._join()
+        return sup, unsup
+
+    def _criterion(self, cls_weight, pred):
+        """-> (crit(pred, target), fused): what the four terms of a step are computed with.  fused: the terms stay as their
+        (inter, sets[, ce]) sums and _total_loss combines them in one launch."""
+        cfg, crt = self.cfg, self.criterion
+        if cls_weight is not None or not isinstance(crt, DiceLoss):    # recipe v1 only (cfg.__post_init__)
+            return (lambda p, t: self._weighted(p, t, cls_weight)), False
+        if (crt.weight is None and crt.ignore_index is not None and pred.is_cuda and nnf.dice_sums_supported(pred, crt.num_classes)
+                and nnf.py_opt("py_loss_combine", 1) == 1):
+            sums = nnf.dice_sums if cfg.recipe == "v1" else nnf.dice_ce_sums
+            return (lambda p, t: sums(p, t, crt.ignore_index)), True
+        return (crt if cfg.recipe == "v1" else self._ce_dice), False
+
+    def _own_mask(self, ps, pu, kw):
+        """a network's fp32 predictions (labelled, unlabelled, both) and the pseudo-label mask it hands to the other network"""
+        ps, pu = ps.float(), pu.float()
+        pred = torch.cat([ps, pu], dim=0)
+        if self.cfg.recipe == "v1":
+            return ps, pu, pred, regularized_pseudo_label(pred, kw["percent"])
+        return ps, pu, pred, score_mask(pred, _argmax_classes(pred), kw["th"])
+
+    def _terms(self, l_target, sup, unsup, score_1, score_2, kw):
+        """Each network's own mask and its two criterion terms (supervised; CPS against the other's mask) on its stream ->
+        fused, pred_sup_1, (sup_1, sup_2), (cps_1, cps_2).  Ends the glue: the caller's stream joins the lanes."""
+        cfg, g = self.cfg, self._glue
         cls_weight = self._fixed_weight
         if cfg.class_weight == "balanced":
             # this step's labelled targets weigh all four terms, as train_vq_pt_unet_balncedweightedloss.py:135-141 does; the counting
             # kernel leaves the weights on the device (no bincount, no host round trip).  One tensor for both networks' streams.
             cls_weight = compute_class_weight(cfg.num_classes, l_target)
-            if split:
-                for s_ in streams:
-                    s_.wait_stream(main)
-                    cls_weight.record_stream(s_)
-        if cls_weight is not None or not isinstance(self.criterion, DiceLoss):
-            def crit(pred, target):                                     # noqa: F811  (cfg.__post_init__: recipe v1 only)
-                return self._weighted(pred, target, cls_weight)
-
-        def own_mask(ps, pu):
-            ps, pu = ps.float(), pu.float()
-            pred = torch.cat([ps, pu], dim=0)
-            if cfg.recipe == "v1":
-                return ps, pu, pred, regularized_pseudo_label(pred, percent)
-            return ps, pu, pred, score_mask(pred, _argmax_classes(pred), cfg.confidence_threshold)
-
-        with on(0):
-            ps1, pu1, pred_1, mask_1 = own_mask(ps1, pu1)
-        with on(1):
-            ps2, pu2, pred_2, mask_2 = own_mask(ps2, pu2)
-        exchange(mask_1, mask_2)
-        # r4: with the Dice criterion (no class weights) the four terms stay as their (inter, sets[, ce]) sums and the whole combination
-        # -- terms, commitment, prototype, total, and its gradient -- is one launch (nnf.cps_loss_combine); else scalar torch ops
-        crt = self.criterion
-        fuse = (isinstance(crt, DiceLoss) and crt.weight is None and cls_weight is None and crt.ignore_index is not None and pred_1.is_cuda
-                and nnf.dice_sums_supported(pred_1, crt.num_classes) and nnf.py_opt("py_loss_combine", 1) == 1)
-        if fuse:
-            def crit(pred, target):                                     # noqa: F811  (the sums; combined below)
-                if cfg.recipe == "v1":
-                    return nnf.dice_sums(pred, target, crt.ignore_index)
-                return nnf.dice_ce_sums(pred, target, crt.ignore_index)
-        with on(0):
+            g.fork()
+            g.share(cls_weight)
+        with g.on(0):
+            ps1, pu1, pred_1, mask_1 = self._own_mask(sup[0][0], unsup[0][0], kw)
+        with g.on(1):
+            ps2, pu2, pred_2, mask_2 = self._own_mask(sup[1][0], unsup[1][0], kw)
+        g.exchange(mask_1, mask_2)
+        crit, fused = self._criterion(cls_weight, pred_1)
+        with g.on(0):
             cps_1, sup_1 = crit(pred_1, mask_2), crit(ps1, l_target)
-        with on(1):
+        with g.on(1):
             cps_2, sup_2 = crit(pred_2, mask_1), crit(ps2, l_target)
-        if split:
-            self._pending_sides.update(streams)
-            self._join()
-            for t in (cps_1, sup_1, cps_2, sup_2, ps1, pu2, mask_1, mask_2, score_1, score_2):
-                for x in (t if isinstance(t, tuple) else (t,)):
-                    x.record_stream(main)
+        g.join()
+        g.to_caller(cps_1, sup_1, cps_2, sup_2, ps1, pu2, mask_1, mask_2, score_1, score_2)
         if cfg.keep_aux:
-            self.aux = dict(mask_1=mask_1, mask_2=mask_2, score_1=score_1, score_2=score_2, pred_sup_1=ps1.detach(), pred_ul_2=pu2.detach())
-            if cls_weight is not None or not isinstance(crt, DiceLoss):    # what the criterion arms' terms are restated from
+            self.aux.update(mask_1=mask_1, mask_2=mask_2, pred_sup_1=ps1.detach(), pred_ul_2=pu2.detach())
+            if cls_weight is not None or not isinstance(self.criterion, DiceLoss):     # what the criterion arms' terms are restated from
                 self.aux.update(pred_1=pred_1.detach(), pred_2=pred_2.detach(), class_weight=cls_weight)
-                if split:
-                    pred_1.record_stream(main), pred_2.record_stream(main)
-            if cfg.cutmix_ratio is not None:                            # score_1 / score_2 stay the clean maps; what the step used comes beside them
-                if split:
-                    clean_1.record_stream(main), clean_2.record_stream(main)
-                self.aux.update(score_1=clean_1, score_2=clean_2, ul_mixed=ul_train, score_1_mixed=score_1, score_2_mixed=score_2, boxes=list(boxes))
-            if cfg.easy_aug is not None:                                # score_1 / score_2 are the maps in the clean frame; the forwards' own beside them
-                if split:
-                    easy_1.record_stream(main), easy_2.record_stream(main)
-                self.aux.update(ul_easy=ul_easy, easy_codes=list(easy_codes), easy_angles=list(easy_angles), score_1_easy=easy_1, score_2_easy=easy_2)
-        lr = self.sched.get_lr(self.iter)
-        for o in self.opts:
-            o.param_groups[0]["lr"] = lr
-        combined = None
-        if fuse:
-            combined = nnf.cps_loss_combine([sup_1, sup_2], [cps_1, cps_2], cfg.cps_loss_weight, 0.0 if cfg.recipe == "v1" else 0.5,
-                                            [c_l1, c_l2, c_u1, c_u2], cfg.total_commitment_loss_weight,
-                                            [p_l1, p_l2, p_u1, p_u2], cfg.total_prototype_loss_weight)
-            if combined is None:                                        # inputs the kernel does not take: the same terms with torch ops
-                def scalar(t):
-                    dice = 1 - (2 * t[0] / (t[1] + 1e-6)).mean(dim=0).mean()
-                    return dice if len(t) == 2 else 0.5 * (t[2][:, 0].sum() / t[2][:, 1].sum()) + dice
-                cps_1, sup_1, cps_2, sup_2 = scalar(cps_1), scalar(sup_1), scalar(cps_2), scalar(sup_2)
-        if combined is not None:
-            loss, stats = combined
-            com_sum, prototype, cps, sup_1, sup_2 = stats[1], stats[2], stats[3], stats[4], stats[5]
-        else:
-            cps = cps_1 + cps_2
-            commitment = (c_l1 + c_l2 + c_u1 + c_u2) * cfg.total_commitment_loss_weight
-            prototype = (p_l1 + p_l2 + p_u1 + p_u2) * cfg.total_prototype_loss_weight
-            com_sum = commitment.sum()
-            loss = sup_1 + sup_2 + cfg.cps_loss_weight * cps + com_sum + prototype.float()
-        self._wgrad_sides(True)
+                g.to_caller(pred_1, pred_2)
+        return fused, ps1, (sup_1, sup_2), (cps_1, cps_2)
+
+    def _total_loss(self, fused, sup, cps, commit, proto):
+        """-> loss and the reported terms.  fused: the whole combination -- terms from their sums, commitment, prototype, total, and
+        its gradient -- is one launch (nnf.cps_loss_combine); else scalar torch ops.  `commit` / `proto`: the four forwards' losses,
+        labelled pair first."""
+        cfg = self.cfg
+        if fused:
+            combined = nnf.cps_loss_combine(list(sup), list(cps), cfg.cps_loss_weight, 0.0 if cfg.recipe == "v1" else 0.5,
+                                            commit, cfg.total_commitment_loss_weight, proto, cfg.total_prototype_loss_weight)
+            if combined is not None:
+                loss, stats = combined
+                return loss, dict(sup_loss_1=stats[4], sup_loss_2=stats[5], cps_loss=stats[3], commitment_loss=stats[1], prototype_loss=stats[2])
+
+            def scalar(t):                                              # inputs the kernel does not take: the same terms with torch ops
+                dice = 1 - (2 * t[0] / (t[1] + 1e-6)).mean(dim=0).mean()
+                return dice if len(t) == 2 else 0.5 * (t[2][:, 0].sum() / t[2][:, 1].sum()) + dice
+            c1, s1, c2, s2 = scalar(cps[0]), scalar(sup[0]), scalar(cps[1]), scalar(sup[1])
+            cps, sup = (c1, c2), (s1, s2)
+        cps_sum = cps[0] + cps[1]
+        commitment = (commit[0] + commit[1] + commit[2] + commit[3]) * cfg.total_commitment_loss_weight
+        prototype = (proto[0] + proto[1] + proto[2] + proto[3]) * cfg.total_prototype_loss_weight
+        com_sum = commitment.sum()
+        loss = sup[0] + sup[1] + cfg.cps_loss_weight * cps_sum + com_sum + prototype.float()
+        return loss, dict(sup_loss_1=sup[0], sup_loss_2=sup[1], cps_loss=cps_sum, commitment_loss=com_sum, prototype_loss=prototype)
+
+    def _backward_and_step(self, loss):
+        """backward (weight gradients on their side streams, if configured), gradient reduction, optimiser step"""
+        L = self.lanes
+        L.wgrad_sides(True)
         try:
             loss.backward()
         finally:
-            self._wgrad_sides(False)
+            L.wgrad_sides(False)
         nnf.flush_pending_wgrads()                                      # two-use weight gradients whose second use never came (none, normally)
         nnf.check_fanin_consumed()
-        if self._two_streams and nnf.py_opt("py_opt_streams", 1):
+        if L.enabled and nnf.py_opt("py_opt_streams", 1):
             # each network's gradient reduction + optimiser step on ITS stream (the sinks wrote p.grad there): the two Adam launches
-            # overlap each other and the metric kernels below; the caller's stream joins both before the step returns
-            main = torch.cuda.current_stream()
-            for i, (b, o, s_) in enumerate(zip(self.buckets, self.opts, self._streams)):
-                s_.wait_stream(main)                                    # backward's leaf streams are joined into `main` by autograd
-                if self._wgrad_streams:
-                    s_.wait_stream(self._wgrad_streams[i])
-                with torch.cuda.stream(s_):
+            # overlap each other and the metric kernels of the caller; the caller's stream joins both before the step returns.
+            # (backward's leaf streams are joined into the caller's by autograd; the side streams are not)
+            L.fork(sides=True)
+            for k, (b, o) in enumerate(zip(self.buckets, self.opts)):
+                with L.on(k):
                     b.finish()
                     o.step()
-                self._pending_sides.add(s_)
         else:
-            if self._two_streams:                                       # the sinks wrote p.grad on the per-model (and side) streams
-                for s_ in self._streams + self._wgrad_streams:
-                    torch.cuda.current_stream().wait_stream(s_)
+            L.join(*range(len(self.models)), sides=True)               # the sinks wrote p.grad on the per-model (and side) streams
             for b in self.buckets:
                 b.finish()
             for o in self.opts:
                 o.step()
-        self.iter += 1
-        with torch.no_grad():
-            miou, _ = miou_device(confusion_matrix_device(ps1, l_target, cfg.num_classes))
-        self._join()
-        return {"loss": loss.detach(), "sup_loss_1": sup_1.detach(), "sup_loss_2": sup_2.detach(), "cps_loss": cps.detach(),
-                "commitment_loss": com_sum.detach(), "prototype_loss": prototype.detach(), "miou": miou,
-                "lr": torch.tensor(lr)}
 
     def sync_buffers(self):
         """Data parallel: BatchNorm running statistics are per-rank (each rank normalises with its own batch statistics -- the
@@ -734,18 +515,9 @@ class CPSTrainer:
             for i, a in enumerate(self.averages):
                 extra[f"ema_model_{i + 1}"] = a.state_dict()["module"]
             extra["ema_updates"] = [int(a.updates) for a in self.averages]
-        if vdist.collectives_on() and vdist.world_size() > 1:
-            # BatchNorm running statistics are per-rank: COPIES of every rank's buffers are gathered to rank 0 (no rank's state is
-            # touched) and stored beside the reference's keys, so that a data-parallel resume restores each rank's own statistics
+        if vdist.collectives_on() and vdist.world_size() > 1:    # every rank's own BatchNorm statistics (a collective; copies)
             for i, m in enumerate(self.models):
-                names = [k for k, _ in m.named_buffers()]
-                flat = torch.cat([b.detach().double().reshape(-1) for _, b in m.named_buffers()]) if names else torch.zeros(0, dtype=torch.float64, device=self.device)
-                if dist.get_backend() == "gloo":
-                    flat = flat.cpu()
-                gathered = [torch.zeros_like(flat) for _ in range(vdist.world_size())]
-                dist.all_gather(gathered, flat)
-                extra[f"bn_buffers_model_{i + 1}"] = {"names": names, "shapes": [tuple(b.shape) for _, b in m.named_buffers()],
-                                                       "per_rank": [g.cpu() for g in gathered]}
+                extra[f"bn_buffers_model_{i + 1}"] = gather_rank_buffers(m, self.device)
         if vdist.rank() == 0:
             m1, m2, o1, o2 = self.state_dicts()
             save_ckpoints(m1, m2, epoch, batch_idx, o1, o2, filepath, models=self.models, extra=extra)
@@ -761,18 +533,7 @@ class CPSTrainer:
         for m, flags in zip(self.models, state.get("initted") or (None, None)):
             restore_initted(m, flags)
         for i, m in enumerate(self.models):                # data-parallel resume: this rank's own BatchNorm statistics (see save_checkpoint)
-            rec = state.get(f"bn_buffers_model_{i + 1}")
-            if rec and vdist.rank() < len(rec["per_rank"]):
-                flat, off = rec["per_rank"][vdist.rank()], 0
-                bufs = dict(m.named_buffers())
-                with torch.no_grad():
-                    for name, shape in zip(rec["names"], rec["shapes"]):
-                        n = 1
-                        for d in shape:
-                            n *= d
-                        if name in bufs:
-                            bufs[name].copy_(flat[off:off + n].view(shape).to(bufs[name].dtype))
-                        off += n
+            restore_rank_buffers(m, state.get(f"bn_buffers_model_{i + 1}"), vdist.rank())
         for i, a in enumerate(self.averages):
             # a file without teachers (a reference checkpoint, or one written with the feature off): each a copy of the loaded student
             a.reset_from_student()
@@ -817,14 +578,18 @@ class CPSTrainer:
         self.buckets[0].zero()
         m.train()
         kw = dict(percent=80.0) if self.cfg.recipe == "v1" else dict(th=self.cfg.confidence_threshold)
-        pred, closs, _u, ploss = self._fwd(m, l_input, l_target, **kw)
+        L = self.lanes
+        L.fork(0)                                                       # inputs / zeroed buckets come from the caller's stream
+        with L.on(0, self.cfg.amp_dtype):
+            out = m(l_input, l_target, **kw)
+        L.to_caller(*out)                                               # consumed on the caller's stream
         self._join()
+        pred, closs, _u, ploss = out
         pred = pred.float()
         loss = self._ce_dice(pred, l_target) + closs.sum() + 0.01 * ploss.float()
         loss.backward()
         nnf.flush_pending_wgrads()
-        if self._two_streams:
-            torch.cuda.current_stream().wait_stream(self._streams[0])
+        L.join(0)                                                       # backward ran on network 1's stream
         self.buckets[0].finish()
         self.opts[0].step()
         return loss.detach()

@@ -11,11 +11,13 @@ Data parallel runs (trainer.CPSTrainer): parameters and codebooks are bit-identi
 statistics are per-rank (the reference's per-device BatchNorm semantics) -- `CPSTrainer.save_checkpoint()` writes rank 0's
 own state without a collective, so saving never changes any rank (`CPSTrainer.sync_buffers()` is the explicit broadcast).
 """
+import math
 import os
 import shutil
 import tarfile
 
 import torch
+import torch.distributed as dist
 
 
 def _initted_flags(model):
@@ -60,6 +62,44 @@ def restore_initted(model, flags):
     for name, v in flags.items():
         if name in mods:
             mods[name].initted = bool(v)
+
+
+def flat_copy(tensors, dtype=None):
+    """one flat tensor holding copies of `tensors` in order (converted to `dtype` if given)"""
+    return torch.cat([(t.detach() if dtype is None else t.detach().to(dtype)).reshape(-1) for t in tensors])
+
+
+def scatter_flat(flat, targets, shapes=None):
+    """flat_copy's inverse: consecutive pieces of `flat` are copied into `targets` (in each target's dtype).  `shapes` (default:
+    the targets' own) gives each piece's extent; a target of None skips its piece."""
+    off = 0
+    with torch.no_grad():
+        for i, t in enumerate(targets):
+            shape = tuple(t.shape if shapes is None else shapes[i])
+            n = math.prod(shape)
+            if t is not None:
+                t.copy_(flat[off:off + n].view(shape))
+            off += n
+
+
+def gather_rank_buffers(model, device):
+    """Data parallel: BatchNorm running statistics are per-rank.  COPIES of every rank's buffers of `model`, gathered to all ranks
+    (a collective; no rank's state is touched), as the record a checkpoint stores beside the reference's keys so that a
+    data-parallel resume restores each rank's own statistics: names, shapes, and one flat float64 tensor per rank."""
+    named = list(model.named_buffers())
+    flat = flat_copy([b for _, b in named], torch.float64) if named else torch.zeros(0, dtype=torch.float64, device=device)
+    if dist.get_backend() == "gloo":
+        flat = flat.cpu()
+    gathered = [torch.zeros_like(flat) for _ in range(dist.get_world_size())]
+    dist.all_gather(gathered, flat)
+    return {"names": [k for k, _ in named], "shapes": [tuple(b.shape) for _, b in named], "per_rank": [g.cpu() for g in gathered]}
+
+
+def restore_rank_buffers(model, rec, rank):
+    """this rank's own buffers from gather_rank_buffers' record; a file without one (or written by fewer ranks) leaves them alone"""
+    if rec and rank < len(rec["per_rank"]):
+        bufs = dict(model.named_buffers())
+        scatter_flat(rec["per_rank"][rank], [bufs.get(name) for name in rec["names"]], rec["shapes"])
 
 
 def save_tar(target_path):

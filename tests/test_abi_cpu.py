@@ -411,7 +411,7 @@ def test_option_table_of_the_integration_guide_lists_the_same_keys_and_defaults(
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# vqseg_vq_tiles_per_wave: the code tiles per wave T of the distance launch (vq_group_tiles, vq_kernels.hip).  The rule, with
+# vqseg_vq_tiles_per_wave: the code tiles per wave T of the distance launch (vq_group_tiles, vq_host.hip).  The rule, with
 # groups_i = ceil(N_i / 128) row groups and tiles_i = ceil(K_i / 32) code tiles per level, wgs(t) = sum_i groups_i * tiles_i / t, t
 # "divides" when tiles_i % t == 0 for every level:
 #   1. "vq_fine_split" on: the largest t in {cap, cap / 2, ...}, t >= 4, that divides with wgs(t) >= 4096;

@@ -1,4 +1,4 @@
-"""The bf16 candidate filter (csrc/vq_kernels.hip: vq_filter_bf16_kernel -> vq_resolve_kernel -> vq_rescore_kernel, the exact kernel's
+"""The bf16 candidate filter (csrc/vq_filter.hip: vq_filter_bf16_kernel -> vq_resolve_kernel -> vq_rescore_kernel, the exact kernel's
 fmaf chains for the few candidate codes of the rows the filter leaves open) against the exact fp32-MFMA kernel on every row and against the CPU chain oracle (oracle/vq_chain.c, order "mfma8"): the
 winning index AND the bits of the winning distance must be identical -- the filter is a speed path, not an approximation.
 Reference arithmetic replaced: torch.cdist -> argmin of EuclideanCodebook.forward (vector_quantizer/vq_img.py:167-168) on the bf16

@@ -1,4 +1,4 @@
-"""Non-finite and overflowing rows / codebooks through every VQ assign entry point (csrc/vq_kernels.hip: vq_assign_f32_kernel, and
+"""Non-finite and overflowing rows / codebooks through every VQ assign entry point (csrc/vq_assign.hip: vq_assign_f32_kernel, and csrc/vq_filter.hip:
 vq_filter_bf16_kernel -> vq_resolve_kernel -> vq_rescore_kernel for bf16 rows) and what consumes the indices (gather, backward,
 histogram, k-means lists).  A bf16 autocast step that diverges hands such rows to the layer; the reference computes through them
 (torch.cdist -> argmin, vector_quantizer/vq_img.py:167-168) and so must this path: every row gets the code and the distance bits of

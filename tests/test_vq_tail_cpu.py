@@ -11,7 +11,8 @@ import pytest
 from tests import vq_tail_cases as T
 
 F = np.float32
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vq_seg_amd", "csrc", "vq_kernels.hip")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vq_seg_amd", "csrc")
+SRC = [os.path.join(CSRC, name) for name in ("vq_internal.h", "vq_tail.hip")]        # the geometry constants; the launchers of the tail
 
 
 def fma32(a, b, c):
@@ -23,7 +24,7 @@ def fma32(a, b, c):
 # the geometry the cases are built around is the source's
 # ---------------------------------------------------------------------------------------------------------------------
 def test_launch_geometry_is_the_sources():
-    src = open(SRC).read()
+    src = "".join(open(path).read() for path in SRC)
     const = lambda name: int(re.search(rf"constexpr int {name} = (\d+);", src).group(1))
     assert (const("GATHER_BLOCKS_MAX"), const("GATHER_ROWS_PER_BLOCK"), const("KM_RB"), const("KM_SEG")) == \
         (T.GATHER_BLOCKS_MAX, T.GATHER_ROWS_PER_BLOCK, T.KM_RB, T.KM_SEG)

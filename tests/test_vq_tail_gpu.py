@@ -1,4 +1,4 @@
-"""Direct parity of the kernels that run after the argmin in csrc/vq_kernels.hip -- vq_gather_kernel<float | bf16> + vq_finalize_kernel,
+"""Direct parity of the kernels that run after the argmin in csrc/vq_tail.hip and csrc/vq_codebook.hip -- vq_gather_kernel<float | bf16> + vq_finalize_kernel,
 vq_backward_kernel, vq_backward_idx_kernel, the member-list code sums (km_hist / km_scan / km_lists / km_segsum / km_sums / km_counts64),
 km_finalize_kernel, ema_counts_kernel + ema_embed_kernel -- through the C ABI, against NumPy / torch computations on the CPU of the same
 inputs (tests/vq_tail_cases.py: cases, references, bars and the assertion functions; tests/test_vq_tail_cpu.py runs those functions on

@@ -1,4 +1,4 @@
-"""Cases, CPU references and assertion functions for the kernels that run after the argmin in csrc/vq_kernels.hip: gather + finalize,
+"""Cases, CPU references and assertion functions for the kernels that run after the argmin in csrc/vq_tail.hip and csrc/vq_codebook.hip: gather + finalize,
 the two backward kernels, the member-list code sums (km_hist / km_scan / km_lists / km_segsum / km_sums / km_counts64), km_finalize and
 the two EMA kernels.  Everything here is NumPy on the CPU: tests/test_vq_tail_gpu.py feeds the functions what the kernels returned,
 tests/test_vq_tail_cpu.py feeds them order-faithful emulations and emulations that carry one defect each.
@@ -18,7 +18,7 @@ import numpy as np
 U = 2.0 ** -24
 GUARD = 64                                        # elements behind every output buffer that must keep their fill
 
-# launch geometry of csrc/vq_kernels.hip (the tests name the paths these decide; test_vq_tail_cpu.py holds them to the source)
+# launch geometry of csrc/vq_tail.hip and csrc/vq_codebook.hip (constants: csrc/vq_internal.h) (the tests name the paths these decide; test_vq_tail_cpu.py holds them to the source)
 GATHER_BLOCKS_MAX, GATHER_ROWS_PER_BLOCK, GATHER_RG = 2048, 16, 4
 UNPACK_BLOCKS_MAX, UNPACK_ROWS_PER_BLOCK = 512, 1024
 BWD_BLOCKS_MAX, BWD_THREADS = 4096, 256

@@ -1,12 +1,12 @@
-// Internal launch-helper declarations shared by the kernels and the C ABI.
+// Launch-helper declarations of the vector quantiser that the C ABI files call (the VQ units themselves share vq_internal.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
-#include <vector>
-
 namespace vqseg {
+
+constexpr int VQ_MAX_LEVELS = 4;
 
 struct VqPlan {
     int Cp, Kp;                 // channels; codes padded to a multiple of 32
@@ -31,74 +31,6 @@ struct KmPlan {
     int row_blocks, max_segments;
 };
 
-struct ProfShape {
-    int64_t n;
-    int c, k;
-    int slot, group;            // first record of the launch this level ran in (its event pair), number of levels in that launch
-    int kind;                   // 0: exact fp32 MFMA kernel on f32 rows, 1: on bf16 rows, 2: bf16 candidate filter + exact re-score
-};
-
-constexpr int VQ_MAX_LEVELS = 4;
-constexpr int F_LISTS = 64;     // sub-lists of a level's candidate pair list (bf16 filter)
-struct VqLevel {
-    const void* x;              // pixel rows [N][C] (f32 or bf16: one type per launch)
-    const float* E4;            // prepared codebook
-    const float* enorm;
-    unsigned long long* keys;   // [N] (distance bits << 32 | code), pre-set to ~0
-    long N;
-    int C, Kp;
-    unsigned wg_end;            // exclusive end of this level's workgroup ids in the launch
-    // gated mode (the bf16 filter's overflow fallback): the level runs, in full, only if the filter's candidate list overflowed
-    // (*gate > gate_cap) -- degenerate codebooks; otherwise every workgroup exits at once
-    const int* gate = nullptr;
-    int gate_cap = 0;
-    int K = 0;                  // real codes: codes K .. Kp - 1 are padding and never win, whatever the row holds (set by the host)
-};
-// one level of the bf16 candidate filter launch (vq_filter_bf16_kernel)
-struct VqFilterLevel {
-    const void* x;              // bf16 pixel rows [N][C]
-    const unsigned short* Eb;   // [2][C / 8][Kp][8] bf16: hi / lo split of the codebook
-    const float* enorm;         // |e_k|^2 (the exact kernel's values)
-    const float* en_max;        // max_k |e_k|^2
-    unsigned long long* summary;// [N][Kp / 128]: (best code | candidate count << 16) << 32 | float bits of the sub-chunk's minimum score
-    float* brow;                // [N] band of the row (score space)
-    // candidate pairs (row << 32 | code) for the exact re-score: every code inside the band of its sub-chunk's minimum other than
-    // that minimum's own code (stage 1), the surviving minima of open rows (stage 2); pair_count[0] counts every append
-    // The list is cut into F_LISTS sub-lists (a workgroup appends to sub-list blockIdx % F_LISTS) with a counter each -- thousands of
-    // waves adding to ONE address serialise in the L2 atomic unit (measured: +50 us on the filter kernel); pair_count[F_LISTS] is
-    // the overflow flag (an append beyond a sub-list's capacity sets it: the gated exact launch then serves the level)
-    unsigned long long* pair_rc;
-    int* pair_count;
-    int pair_cap;               // capacity of ONE sub-list
-    unsigned long long* keys;   // [N] the exact kernel's keys (decided rows: written by stage 2; open rows: atomicMin of stage 3)
-    const float* W;             // fp32 codebook [K][C] (nullable: the re-score then reads the prepared image E4)
-    const float* E4;
-    long N;
-    int C, Kp;
-    unsigned wg_end;            // stage 1 launch: exclusive end of this level's workgroup ids
-    unsigned rblk_end;          // stage 2 launch: exclusive end of this level's 256-row blocks
-    unsigned sblk_end;          // stage 3 launch: exclusive end of this level's workgroups (a multiple of F_LISTS per level)
-};
-struct VqFilterGroup {
-    VqFilterLevel lv[VQ_MAX_LEVELS];
-    int n;
-};
-#ifndef VQ_TIMELINE
-#define VQ_TIMELINE 0             // debug build only (`make timeline` -> libvqseg_hip_tl.so; tools/vq_timeline.py): per-workgroup clock stamps
-#endif
-struct VqGroup {
-    VqLevel lv[VQ_MAX_LEVELS];
-    int n;
-#if VQ_TIMELINE
-    unsigned long long* tl;     // [workgroups][16]: (s_memrealtime, s_memtime) at 6 points of wave 0 + HW_ID + XCC_ID, or null
-#endif
-};
-struct Profile {
-    bool enabled = false;
-    int capacity = 0;
-    std::vector<hipEvent_t> ev;
-    std::vector<ProfShape> shape;
-};
 hipError_t profile_begin(int capacity);
 void profile_release();
 int profile_collect(int max_records, int64_t* n, int* c, int* k, float* ms, int* kind);

@@ -5,7 +5,7 @@ Mirrors vector_quantizer/vq_img.py of the reference: constructor keywords (:194-
 submodule path `.codebook.embedding.weight`, the `initted` flag, train/eval switching and
 the 4-tuple returned by forward (:228-244).  The arithmetic is NOT the reference's op
 sequence: distance + argmin + gather + straight-through + commitment + dead-code
-histogram run as fused kernels (vq_seg_amd/csrc/vq_kernels.hip), and backward is the
+histogram run as fused kernels (vq_seg_amd/csrc/vq_assign.hip, vq_filter.hip, vq_tail.hip), and backward is the
 analytic gradient instead of an autograd graph over cdist.
 
 Extension (opt-in, `ema_update=True`; default False = the reference's frozen codebook): the exponential-moving-average

@@ -1,6 +1,6 @@
-"""Direct parity of the BatchNorm, pooling, resize, head, cast and split-3 kernels (csrc/nn_kernels.hip) through the C ABI
-against plain float64 computations of the same operations on the CPU.  The reference always sees the values the kernel
-receives (inputs are rounded to the kernel's element type first).
+"""Direct parity of the BatchNorm, pooling, resize, head, cast and split-3 kernels (csrc/nn_bn.hip, nn_spatial.hip,
+nn_head.hip, nn_stem.hip) through the C ABI against plain float64 computations of the same operations on the CPU.  The
+reference always sees the values the kernel receives (inputs are rounded to the kernel's element type first).
 
 Metric.  Element-wise kernels are held to a per-element bound
     |got - ref| <= k * u * S  (+ half a bf16 ulp of ref when the kernel stores bf16)
@@ -770,3 +770,52 @@ def test_s3_bilinear(h, w, ho, wo, c, cap, align):
         outs.append(y)
     if cap:
         assert torch.equal(outs[0], outs[1])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 8. the split-3 pool and resize are the fp32 kernels on other rows:  s3_op(r) == s3_split(f32_op(s3_merge(r))), bit for bit
+# ------------------------------------------------------------------------------------------------------------------
+def _s3_through_f32(L, rows, n, h, w, c, ho, wo, f32_op):
+    """s3_split(f32_op(s3_merge(rows))) through the C ABI: the merge and the split are exact, so this is what the split-3 entry
+    point must return if it evaluates the fp32 kernel's expressions on the same values in the same order."""
+    merged = nan_like((n, h, w, c), F32)
+    ok(L.vqseg_s3_merge_f(rows.data_ptr(), n * h * w, c, merged.data_ptr(), stream()))
+    y32 = nan_like((n, ho, wo, c), F32)
+    f32_op(merged, y32)
+    want = nan_like((n, ho, wo, 2 * c), BF16)
+    ok(L.vqseg_s3_split_f(y32.data_ptr(), n * ho * wo, c, want.data_ptr(), stream()))
+    return want
+
+
+@pytest.mark.parametrize("n,h,w,c", [(2, 17, 13, 8), (1, 1, 5, 8), (2, 18, 22, 24)],
+                         ids=["odd-extents-one-vector", "single-row-clipped-windows", "cv3"])
+def test_s3_maxpool_is_f32_maxpool(n, h, w, c):
+    L = lib()
+    rows = _split3(synth.uniform(98, (n, h, w, c), -1, 1)).to(dev())
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    got = nan_like((n, ho, wo, 2 * c), BF16)
+    ok(L.vqseg_s3_maxpool3x3s2_f(rows.data_ptr(), n, h, w, c, got.data_ptr(), stream()))
+    want = _s3_through_f32(L, rows, n, h, w, c, ho, wo, lambda x, y: ok(
+        L.vqseg_maxpool3x3s2_f(0, 0, x.data_ptr(), None, n, h, w, c, y.data_ptr(), None, stream())))
+    torch.cuda.synchronize()
+    assert torch.equal(got.view(torch.int16), want.view(torch.int16))
+
+
+@pytest.mark.parametrize("align", [0, 1])
+@pytest.mark.parametrize("h,w,ho,wo,c", [(16, 32, 32, 64, 64), (16, 32, 32, 64, 24), (9, 11, 18, 22, 8), (7, 5, 30, 23, 8), (5, 7, 1, 1, 8)],
+                         ids=["exact2x", "generic-cv-not-pow2", "generic-2x-odd", "generic-up", "generic-to-1x1"])
+def test_s3_bilinear_is_f32_bilinear(h, w, ho, wo, c, align):
+    """16x32 -> 32x64 with C = 64 takes the exact-2x kernels on both sides for align = 0 (cv = 8 split-3, 16 fp32: powers of two);
+    it runs again with bilinear_up2 = 0 (the generic kernels).  C = 24: cv = 3 / 6, never the exact-2x kernels."""
+    L = lib()
+    n = 2
+    rows = _split3(synth.uniform(97, (n, h, w, c), -1, 1)).to(dev())
+    exact2x = ho == 2 * h and wo == 2 * w and c == 64
+    for up2 in ((None, 0) if exact2x else (None,)):
+        with option("bilinear_up2", up2) if up2 is not None else contextlib.nullcontext():
+            got = nan_like((n, ho, wo, 2 * c), BF16)
+            ok(L.vqseg_s3_bilinear_f(rows.data_ptr(), n, h, w, c, ho, wo, align, got.data_ptr(), stream()))
+            want = _s3_through_f32(L, rows, n, h, w, c, ho, wo, lambda x, y: ok(
+                L.vqseg_bilinear_f(0, 0, x.data_ptr(), n, h, w, c, ho, wo, align, y.data_ptr(), stream())))
+        torch.cuda.synchronize()
+        assert torch.equal(got.view(torch.int16), want.view(torch.int16)), f"bilinear_up2={up2}"

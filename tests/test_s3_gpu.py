@@ -162,7 +162,8 @@ def test_eval_forward_with_widths_the_split3_kernels_reject_falls_back_to_the_pr
 
 
 def test_split3_exact_2x_resize_is_bit_identical_to_the_generic_kernel():
-    """s3_bilinear_up2_kernel (2x, align_corners = False, power-of-two extents) against s3_bilinear_kernel (`bilinear_up2` = 0)."""
+    """bilinear_up2_fwd_kernel<S3Row, 8> (2x, align_corners = False, power-of-two extents) against bilinear_fwd_kernel<S3Row, 8>
+    (`bilinear_up2` = 0)."""
     from vq_seg_amd import _hip, nnf
     L = _hip.lib()
     for shape in ((2, 64, 16, 16), (1, 8, 1, 2), (2, 256, 4, 32)):

@@ -204,7 +204,7 @@ def test_stem_entry_point_refuses_what_the_kernel_does_not_cover():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# B. vqseg_im2col_f.  The kernels report no variant id: the branch of launch_im2col_stem (nn_kernels.hip) each case takes is
+# B. vqseg_im2col_f.  The kernels report no variant id: the branch of launch_im2col_stem (nn_stem.hip) each case takes is
 # read off its conditions and written next to the case.
 # ---------------------------------------------------------------------------------------------------------------------------
 STEM_GEOM = (3, 7, 2, 3)                                        # cin, k, stride, pad

@@ -1,4 +1,5 @@
-// Internal declarations of the HBM-bound NN kernels (nn_kernels.hip).
+// Internal declarations of the HBM-bound NN kernels (nn_bn / nn_spatial / nn_head / nn_stem / nn_host .hip): everything
+// nn_abi.hip and data_kernels.hip may call.  What the NN units share among themselves: nn_internal.h (host), nn_device.h (device).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

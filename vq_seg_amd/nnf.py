@@ -1,5 +1,5 @@
 """Functional building blocks of the encoder/decoder, executed by the gfx950 HIP kernels behind
-include/vqseg.h (conv_*.hip, nn_kernels.hip).  torch only owns memory and the autograd tape.
+include/vqseg.h (conv_*.hip, nn_*.hip).  torch only owns memory and the autograd tape.
 
 Layout: activations are NHWC in memory ("channels_last" views of logically NCHW tensors).
 Precision follows the activation dtype: float32 -> "precise" kernels (bf16x3 split MFMA, fp32 storage;

@@ -190,6 +190,14 @@ def test_wgrad_over_two_uses_in_one_launch(case):
     torch.cuda.synchronize()
     tol = 2e-4 if precise else 2e-5
     assert rel(gw, ref) < tol
+    if precise:                                                                          # ... and elementwise at the split kernels' derived bound
+        from tests import precise_cases as pc
+        S = 0
+        for x, gy in zip(xs, gys):
+            xp = F.pad(x.double().abs().permute(0, 3, 1, 2), (pad,) * 4, mode="reflect" if reflect else "constant")
+            S = S + torch.nn.grad.conv2d_weight(xp, (cout, cin, k, k), gy.double().abs().permute(0, 3, 1, 2), stride=stride)
+        m = (na + nb) * ho * wo
+        assert len(pc.violations(gw.cpu(), ref, S, m + (m + pc.STAGE - 1) // pc.STAGE)) == 0
     # == the two single-use launches accumulated (different slab partition: rounding-level agreement)
     gw2 = torch.zeros_like(gw)
     for i, n in enumerate((na, nb)):

@@ -717,6 +717,33 @@ int vqseg_affine_warp_f(int mode, int elem_bytes, const void* src, void* out, in
                         int64_t out_stride_s, int64_t stride_p, int64_t stride_px, const float* matrices_host, uint64_t fill_bits,
                         void* stream);
 
+/* Prediction: bilinear resize (align_corners = 0) of class logits to ho x wo, the mean over n_views logit tensors, arg-max, top
+ * probability and confusion counts in one pass, without the (b, c, ho, wo) tensor in between (vq_seg_amd.nnf.resize_argmax,
+ * vq_seg_amd.predict, evaluate.test_loop(fused=True)).  Per output pixel (y, x):
+ *     a_v   = bilinear interpolation of view v at (y, x), per class     (the arithmetic of vqseg_bilinear_f, bit for bit)
+ *     acc   = a_0 (+ a_1 (+ a_2 + a_3))   plain f32 adds in view order;  n_views > 1: acc *= 1 / n_views
+ *     label = first maximum of acc over the classes (a NaN never wins; all-NaN gives class 0)
+ *     top   = 1 / sum_c expf(acc_c - max)                               (the top probability of vqseg_softmax_stats_f)
+ *     counts[b][t][label] += 1  where t = target[b][y][x] lies in [0, c)   (others skipped, as vqseg_confusion_counts_f)
+ * With one view and no flip, label / top / counts equal what vqseg_softmax_stats_f and vqseg_confusion_counts_f give on the output of
+ * vqseg_bilinear_f, bit for bit.
+ *   views_host [n_views]  HOST array of device pointers: f32 logits of logical shape (b, c, h, w), all with the strides below
+ *   flips_host [n_views]  HOST array of flip codes 0..3: bit 0 flips the columns, bit 1 the rows of that view before it is resized -- an
+ *                         index map on the source grid (tap column i reads w - 1 - i), the weights do not change
+ *   n_views               1, 2 or 4 (1 / n_views exact); anything else is VQSEG_EINVAL
+ *   stride_b/_c/_px       batch, class and pixel strides in ELEMENTS (as vqseg_softmax_stats_f takes them), rows dense: planar (pixel
+ *                         stride 1, class stride h * w) or interleaved (class stride 1, pixel stride c); 2..4 classes
+ *   label  [b][ho][wo] u8 out, top [b][ho][wo] f32 out, counts [b][c][c] i64 out (overwritten; rows = ground truth): each may be NULL,
+ *                         not all three;  target [b][ho][wo] i64, non-NULL iff counts is
+ * Pointers and flip codes travel as kernel arguments: no device allocation, no host-to-device copy, no synchronisation.  A wave takes
+ * 256 consecutive output pixels, four per lane and 64 apart, so that its gathers, its top stores and its target loads each cover 64
+ * adjacent pixels; the u8 labels are packed across lanes into one 4-byte store per lane.  Counts go through wave ballots, a
+ * per-workgroup LDS histogram and integer atomics (order-independent).  Source images up to 2^27 pixels, outputs up to 2^30.  Grid
+ * capped by option "nn_grid_cap". */
+int vqseg_resize_argmax_f(const float* const* views_host, const int* flips_host, int n_views, int64_t stride_b, int64_t stride_c,
+                          int64_t stride_px, int b, int c, int h, int w, int ho, int wo, uint8_t* label, float* top,
+                          const int64_t* target, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

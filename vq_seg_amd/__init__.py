@@ -9,3 +9,5 @@ vq_seg_amd.models  <->  models/.  There is NO CPU or eager fallback: calling a f
 without the HIP library or on a CPU tensor raises.
 """
 __version__ = "0.1.0"
+
+from .predict import Prediction, Predictor, predict_batches  # noqa: E402,F401  (the package's front door: class maps from trained networks)

@@ -142,6 +142,7 @@ SYMBOLS = {
     "vqseg_batch_u8_f": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 6),
     "vqseg_box_mix_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 3 + [c_void_p, ctypes.c_uint64, c_void_p]),
     "vqseg_affine_warp_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 4 + [c_void_p, ctypes.c_uint64, c_void_p]),
+    "vqseg_resize_argmax_f": (c_int, [c_void_p, c_void_p, c_int] + [c_int64] * 3 + [c_int] * 6 + [c_void_p] * 5),
 }
 
 _lib: Optional[ctypes.CDLL] = None

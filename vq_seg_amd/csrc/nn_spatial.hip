@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bilinear_device.h"
 #include "nn_device.h"
 #include "nn_internal.h"
 
@@ -175,29 +176,9 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // bilinear resize (NHWC), both corner conventions (ATen upsample_bilinear2d semantics)
 //   align_corners: src = dst * (in-1)/(out-1);  else src = max((dst+0.5)*in/out - 0.5, 0)
+// bil_src (taps and weight of one output coordinate) and bil_mix (the three multiply-adds): bilinear_device.h, shared with the fused
+// resize + arg-max of predict_kernels.hip
 // ---------------------------------------------------------------------------------------------
-// (1 - lh) * ((1 - lw) * v00 + lw * v01) + lh * ((1 - lw) * v10 + lw * v11) with the multiply-adds spelled out: the generic and the
-// exact-2x kernels (and their split-3 instantiations) must round identically, and the compiler's own choice of which product of a sum to fuse
-// differs between kernels whose weights are run-time values and kernels whose weights are constants
-__device__ __forceinline__ float bil_mix(float v00, float v01, float v10, float v11, float lh, float lw) {
-    const float top = __builtin_fmaf(lw, v01, (1.0f - lw) * v00);
-    const float bot = __builtin_fmaf(lw, v11, (1.0f - lw) * v10);
-    return __builtin_fmaf(lh, bot, (1.0f - lh) * top);
-}
-
-__device__ __forceinline__ void bil_src(int d, int in, int out, int align, int& i0, int& i1, float& l1) {
-    float s;
-    if (align) s = out > 1 ? (float)d * ((float)(in - 1) / (float)(out - 1)) : 0.0f;
-    else {
-        s = ((float)d + 0.5f) * ((float)in / (float)out) - 0.5f;
-        if (s < 0.0f) s = 0.0f;
-    }
-    i0 = (int)s;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = s - (float)i0;
-}
-
 template <typename T, int VC>
 __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const T* __restrict__ x, int N, int H, int W, int C, int Ho, int Wo,
                                                            int align, T* __restrict__ y) {

@@ -4,6 +4,11 @@ Eval-mode model (on the HIP path BatchNorm + residual + ReLU ride in the convolu
 gathers), logits resized bilinearly to the native mask size, metrics per batch exactly as `Measurement.measure` defines
 them (`measurement.py:7-91`: per-image confusion matrices, IoU with the +1e-8 denominator, batch means) and averaged
 over the batches.  Only the (N, C, C) confusion counts and the per-image hit counts leave the device.
+
+`fused=True` (opt-in) takes resize, arg-max and confusion counts of a batch from one `nnf.resize_argmax` call, so the logits at
+mask size are never written; the per-image accuracy is then trace(counts) / (Hm * Wm) -- the same number as the mean of the
+0 / 1 hits (an out-of-range target never equals a class, and a mean of 0 / 1 doubles is a ratio of integers), and the returned
+dict equals the unfused one.  `tta` (with fused: "hflip", "vflip", "hvflip" beside "none") scores the mean over flipped views.
 """
 from typing import Dict, Iterable, Tuple
 
@@ -13,12 +18,33 @@ import torch.nn.functional as F
 
 from . import nnf
 from .measurement import Measurement, confusion_matrix_device
+from .predict import Predictor
+
+
+def _resized_counts(model, img, target, num_classes, amp_dtype):
+    """the two-step path: logits at mask size, then (N, C, C) confusion counts (rows = ground truth) and per-image accuracy"""
+    if amp_dtype is not None and img.is_cuda:
+        with torch.autocast("cuda", dtype=amp_dtype):
+            pred = model(img)
+    else:
+        pred = model(img)
+    pred = pred[0] if isinstance(pred, tuple) else pred
+    pred = pred.float()
+    # F.interpolate(pred, size, mode="bilinear") of test_detailviz.py:118 (align_corners=False): the HIP resize kernel on the device
+    pred = nnf.upsample_bilinear(pred, size=tuple(target.shape[-2:]), align_corners=False) if pred.is_cuda else \
+        F.interpolate(pred, target.shape[-2:], mode="bilinear")
+    conf = confusion_matrix_device(pred, target, num_classes)                  # (N, C, C), rows = ground truth
+    hits = (pred.argmax(dim=1) == target).flatten(1).double().mean(dim=1)       # Measurement.accuracy per image
+    return conf, hits
 
 
 @torch.no_grad()
 def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], num_classes: int,
-              device=None, amp_dtype=None) -> Dict[str, object]:
+              device=None, amp_dtype=None, fused: bool = False, tta=None) -> Dict[str, object]:
     """batches yields (images (N, 3, H, W) float in [0, 1], labels (N, Hm, Wm) int class ids)."""
+    if tta is not None and not fused:
+        raise ValueError("test_loop: tta needs fused=True (the views are averaged inside the fused resize + arg-max)")
+    views = Predictor(model, num_classes, amp_dtype=amp_dtype, tta=tta or ("none",)).views if fused else None
     was_training = model.training
     model.eval()
     meas = Measurement(num_classes)
@@ -28,18 +54,12 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
     for img, target in batches:
         if device is not None:
             img, target = img.to(device), target.to(device)
-        if amp_dtype is not None and img.is_cuda:
-            with torch.autocast("cuda", dtype=amp_dtype):
-                pred = model(img)
+        if fused:
+            logits, flips = views(img)
+            conf = nnf.resize_argmax(logits, tuple(target.shape[-2:]), flips=flips, target=target)[2]
+            hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (target.shape[-2] * target.shape[-1])
         else:
-            pred = model(img)
-        pred = pred[0] if isinstance(pred, tuple) else pred
-        pred = pred.float()
-        # F.interpolate(pred, size, mode="bilinear") of test_detailviz.py:118 (align_corners=False): the HIP resize kernel on the device
-        pred = nnf.upsample_bilinear(pred, size=tuple(target.shape[-2:]), align_corners=False) if pred.is_cuda else \
-            F.interpolate(pred, target.shape[-2:], mode="bilinear")
-        conf = confusion_matrix_device(pred, target, num_classes)                  # (N, C, C), rows = ground truth
-        hits = (pred.argmax(dim=1) == target).flatten(1).double().mean(dim=1)       # Measurement.accuracy per image
+            conf, hits = _resized_counts(model, img, target, num_classes, amp_dtype)
         conf_np = conf.cpu().numpy()
         miou, ious = meas.miou(conf_np)
         precision, _ = meas.precision(conf_np)

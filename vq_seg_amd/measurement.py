@@ -76,9 +76,11 @@ def confusion_matrix_device(logits: torch.Tensor, target: torch.Tensor, num_clas
                     _hip.tptr(tgt, "targets", dtype=torch.int64, numel=b * h * w), b, c, h * w,
                     _hip.tptr(out, "confusion counts", dtype=torch.int64, numel=b * c * c))
         return out
-    cats = num_classes * target.reshape(n, -1).long() + logits.argmax(dim=1).reshape(n, -1)
+    tgt = target.reshape(n, -1).long()
+    cats = num_classes * tgt + logits.argmax(dim=1).reshape(n, -1)
     cats = cats + (num_classes ** 2) * torch.arange(n, device=cats.device)[:, None]
-    return torch.bincount(cats.reshape(-1), minlength=n * num_classes ** 2).reshape(n, num_classes, num_classes)
+    valid = (tgt >= 0) & (tgt < num_classes)                 # targets outside the classes (255) are skipped, as the kernel skips them
+    return torch.bincount(cats[valid], minlength=n * num_classes ** 2).reshape(n, num_classes, num_classes)
 
 
 def miou_device(conf: torch.Tensor):

@@ -5,7 +5,9 @@ Layout: activations are NHWC in memory ("channels_last" views of logically NCHW 
 Precision follows the activation dtype: float32 -> "precise" kernels (bf16x3 split MFMA, fp32 storage;
 the parity mode), bfloat16 -> "fast" kernels (bf16 storage and operands, fp32 accumulate).
 
-Every function here has exactly one implementation; CPU tensors are refused (no fallback).
+Every function here has exactly one implementation; CPU tensors are refused (no fallback).  The one exception is the
+prediction path's `resize_argmax`, which restates itself with torch ops for tensors that are not on the GPU, the way
+measurement.confusion_matrix_device and evaluate.test_loop treat them.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ from typing import Optional
 import weakref
 
 import torch
+import torch.nn.functional as F
 
 from . import _hip
 from ._hip import lib
@@ -1746,4 +1749,91 @@ def percentile(values, percent: float):
 
 def softmax_stats_supported(logits) -> bool:
     return logits.is_cuda and logits.dim() == 4 and 2 <= logits.shape[1] <= 4
+
+
+# ------------------------------------------------------------------------------------------------
+# prediction: resize + mean over views + arg-max (+ top probability, confusion counts) in one pass
+# ------------------------------------------------------------------------------------------------
+FLIP_DIMS = ((), (3,), (2,), (2, 3))          # flip code -> dims of an (N, C, H, W) tensor: bit 0 columns, bit 1 rows
+RESIZE_ARGMAX_CALLS = 0                       # calls that reached the library (for tests, never read by the product)
+
+
+def _resize_argmax_torch(views, flips, size, want_top, target):
+    """resize_argmax with torch ops, for tensors that are not on the GPU"""
+    acc = None
+    for v, f in zip(views, flips):
+        r = F.interpolate(v.flip(FLIP_DIMS[f]) if f else v, size=size, mode="bilinear", align_corners=False)
+        acc = r if acc is None else acc + r
+    if len(views) > 1:
+        acc = acc * (1.0 / len(views))
+    b, c = acc.shape[:2]
+    label = acc.argmax(dim=1)
+    top = torch.softmax(acc, dim=1).max(dim=1).values if want_top else None
+    counts = None
+    if target is not None:
+        t = target.reshape(b, -1)
+        cats = c * t + label.reshape(b, -1) + (c * c) * torch.arange(b, device=t.device)[:, None]
+        counts = torch.bincount(cats[(t >= 0) & (t < c)], minlength=b * c * c).reshape(b, c, c)
+    return label.to(torch.uint8), top, counts
+
+
+def resize_argmax(logits, size, flips=None, want_top=False, target=None):
+    """(label (B, Ho, Wo) u8, top probability (B, Ho, Wo) f32 | None, confusion counts (B, C, C) i64 | None) of the logits resized
+    bilinearly (align_corners=False) to `size`, in one HIP pass without the (B, C, Ho, Wo) tensor (vqseg_resize_argmax_f).  `logits`:
+    one (B, C, H, W) fp32 tensor or a list of 1, 2 or 4 of them ("views": the networks of an ensemble, flipped test-time views),
+    NCHW-contiguous or channels_last; `flips`: one code per view (bit 0 columns, bit 1 rows) that is undone before the resize.  The
+    views' resized logits are summed in order and scaled by 1 / V; label is the first maximum, top its softmax probability, counts
+    (with `target` (B, Ho, Wo), any integer type; rows = ground truth, targets outside [0, C) skipped) the per-image confusion
+    matrix.  With one view it equals softmax_stats / confusion_matrix_device on upsample_bilinear(logits, size) bit for bit.
+    Tensors that are not on the GPU are computed with torch ops (F.interpolate, torch.flip).  No gradient flows."""
+    global RESIZE_ARGMAX_CALLS
+    E = _hip.HipLibraryError
+    views = [logits] if torch.is_tensor(logits) else list(logits)
+    nv = len(views)
+    if nv not in (1, 2, 4):
+        raise E(f"resize_argmax: 1, 2 or 4 views (the mean's 1 / V must be exact), got {nv}")
+    flips = [0] * nv if flips is None else [int(f) for f in flips]
+    if len(flips) != nv:
+        raise E(f"resize_argmax: one flip code per view required: {nv} views, {len(flips)} codes")
+    if any(f < 0 or f > 3 for f in flips):
+        raise E(f"resize_argmax: a flip code is 0..3 (bit 0 columns, bit 1 rows), got {flips}")
+    if not all(torch.is_tensor(v) and v.dim() == 4 for v in views):
+        raise E("resize_argmax: every view must be a (B, C, H, W) tensor")
+    x0 = views[0]
+    if any(v.shape != x0.shape or v.device != x0.device for v in views):
+        raise E(f"resize_argmax: every view must have view 0's shape and device, got shapes {[tuple(v.shape) for v in views]}")
+    b, c, h, w = x0.shape
+    if not 2 <= c <= 4:
+        raise E(f"resize_argmax: 2..4 classes, got {c}")
+    ho, wo = int(size[0]), int(size[1])
+    if min(b, h, w, ho, wo) < 1:
+        raise E("resize_argmax: empty input or output")
+    # one layout for all views: view 0's if it is dense (NCHW-contiguous or channels_last), else NCHW
+    fmt = torch.contiguous_format if x0.is_contiguous() or not x0.is_contiguous(memory_format=torch.channels_last) else torch.channels_last
+    views = [v.detach() for v in views]
+    views = [v if v.is_contiguous(memory_format=fmt) else v.contiguous(memory_format=fmt) for v in views]
+    ptrs = [_strided_f32(v, "logits" if nv == 1 else f"logits (view {i})", b * c * h * w) for i, v in enumerate(views)]
+    tgt = None
+    if target is not None:
+        if not torch.is_tensor(target) or target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+            raise E(f"resize_argmax: target must be an integer tensor, got {getattr(target, 'dtype', type(target).__name__)}")
+        if tuple(target.shape) != (b, ho, wo):
+            raise E(f"resize_argmax: target must have the output's shape {(b, ho, wo)}, got {tuple(target.shape)}")
+        tgt = target.detach().long().contiguous()
+    dev = x0.device
+    if not x0.is_cuda:
+        return _resize_argmax_torch(views, flips, (ho, wo), want_top, tgt)
+    label = torch.empty((b, ho, wo), dtype=torch.uint8, device=dev)
+    top = torch.empty((b, ho, wo), dtype=torch.float32, device=dev) if want_top else None
+    counts = torch.empty((b, c, c), dtype=torch.int64, device=dev) if tgt is not None else None
+    varr, farr = (ctypes.c_void_p * 4)(), (ctypes.c_int * 4)(*(flips + [0] * (4 - nv)))
+    for i, p in enumerate(ptrs):
+        varr[i] = _hip.on_gpu(p)
+    # tptr admits two dense layouts; the strides are stated from the layout (a size-1 dimension's own stride is arbitrary)
+    strides = (c * h * w, h * w, 1) if fmt == torch.contiguous_format else (c * h * w, 1, c)
+    _launch("vqseg_resize_argmax_f", dev, varr, farr, nv, *strides, b, c, h, w, ho, wo, _T(label, "labels", dtype=torch.uint8, numel=b * ho * wo),
+            _f32(top, "top probability", b * ho * wo), _T(tgt, "target", dtype=torch.int64, numel=b * ho * wo),
+            _T(counts, "confusion counts", dtype=torch.int64, numel=b * c * c))
+    RESIZE_ARGMAX_CALLS += 1
+    return label, top, counts
 

@@ -33,6 +33,7 @@ from .evaluate import test_loop
 from .models import init_weight
 from .models.networks import make_model
 from .optim import HipAdam
+from .predict import Prediction, Predictor
 from .utils.ckpoints import gather_rank_buffers, load_training_state, restore_initted, restore_rank_buffers, save_ckpoints
 from .utils.lr_schedulers import CosineAnnealingLR
 
@@ -542,15 +543,29 @@ class CPSTrainer:
         self.iter = int(state.get("iter", self.iter))
         return state.get("epoch", 0), state.get("batch_idx", 0)
 
-    def evaluate(self, batches, which: str = "student", index: int = 0):
-        """evaluate.test_loop on network `index` of the pair: which="student" scores the trained weights, which="teacher" their
-        exponential moving average (cfg.ema_decay), under cfg.amp_dtype.  `batches` yields (images, labels)."""
+    def _networks(self, which: str):
+        """the pair `which` names: "student" the trained weights, "teacher" their exponential moving averages (cfg.ema_decay)"""
         if which not in ("student", "teacher"):
             raise ValueError(f"which must be 'student' or 'teacher', got {which!r}")
         if which == "teacher" and not self.teachers:
             raise ValueError("which='teacher' needs a teacher: set CPSConfig.ema_decay")
-        model = (self.teachers if which == "teacher" else self.models)[index]
-        return test_loop(model, batches, self.cfg.num_classes, device=self.device, amp_dtype=self.cfg.amp_dtype)
+        return self.teachers if which == "teacher" else self.models
+
+    def evaluate(self, batches, which: str = "student", index: int = 0, fused: bool = False):
+        """evaluate.test_loop on network `index` of the pair: which="student" scores the trained weights, which="teacher" their
+        exponential moving average (cfg.ema_decay), under cfg.amp_dtype.  `batches` yields (images, labels).  `fused`: resize, arg-max
+        and confusion counts in one kernel (evaluate.test_loop's opt-in; the same numbers)."""
+        model = self._networks(which)[index]
+        return test_loop(model, batches, self.cfg.num_classes, device=self.device, amp_dtype=self.cfg.amp_dtype, fused=fused)
+
+    def predict(self, images, size=None, which: str = "student", index: int = 0, ensemble: bool = False, tta=("none",),
+                want_confidence: bool = False) -> Prediction:
+        """Class maps of `images` (N, 3, H, W) at `size` (None: their own): predict.Predictor on network `index` of the pair `which`
+        names, or with `ensemble` on both of them (mean of the two networks' logits), times the flipped views of `tta`, under
+        cfg.amp_dtype.  -> Prediction(label (N, Ho, Wo) uint8, confidence (N, Ho, Wo) f32 | None)."""
+        nets = self._networks(which)
+        return Predictor(list(nets) if ensemble else nets[index], self.cfg.num_classes, amp_dtype=self.cfg.amp_dtype, tta=tta,
+                         device=self.device)(images, size=size, want_confidence=want_confidence)
 
     def _weighted(self, pred, target, weight):
         """the configured criterion with this step's class weights: the module's own parameters (ignore index 255, the focal

@@ -52,6 +52,8 @@ const char* vqseg_kernel_name(const char* entry_point);
  *                                   filter + exact re-score (same indices and distances as the exact kernel); 0: exact kernel on every row.
  *                                   "vq_filter_force_all" = 1 (tests): the filter decides nothing, every row is re-scored;
  *                                   "vq_filter_launches": returns the number of launches that took the filter so far, sets the counter
+ *   "vq_s3_filter"                  1 (default): split-3 rows (row type 2) of such layers take the same filter on their [hi | lo] halves;
+ *                                   0: the exact kernel on every row, merging hi + lo as it loads
  *   "conv_xcd_pair"                 implicit-GEMM layers with 2..value Cout chunks launch 1-D so that the chunks of an
  *                                   M tile run on the same XCD and share the input rows through its L2 (default 8, r4; r3: 4; 0: off)
  *   "conv3x3_patch_chunk_stage"     1 (default): 3x3 layers with 32-channel K chunks and <= 64 outputs (or 32 inputs) load all nine
@@ -106,7 +108,7 @@ int vqseg_set_option(const char* key, int value);
 int vqseg_profile_begin(int capacity);
 int vqseg_profile_collect(int max_records, int64_t* n_rows_host, int* channels_host,
                           int* n_codes_host, float* ms_host,
-                          int* kind_host /* nullable; 0: exact fp32-MFMA kernel on f32 rows, 1: on bf16 rows, 2: bf16 candidate filter + exact re-score */);
+                          int* kind_host /* nullable; 0: exact fp32-MFMA kernel on f32 rows (or split-3 rows, merged on load), 1: on bf16 rows, 2: bf16 candidate filter + exact re-score (bf16 or split-3 rows) */);
 
 /* The same for the convolution kernels (forward, data gradient, fused-epilogue and split-3 launches of vqseg_conv2d_*): per launch
  * the ALGORITHMIC flops 2 * KH * KW * Cin * Cout * output pixels (logical channels for split-3; forward-layer pixels for the
@@ -142,15 +144,19 @@ int vqseg_vq_forward_f32(const float* x, const float* codebook, const void* prep
 
 /* The same forward for up to 4 independent layers ("levels") in ONE distance + argmin launch: the three VQ layers of a
  * VQ-UNet forward (net.py:1183-1191 calls them one after the other; they are independent).  Arrays of n_levels entries;
- * every level with its own workspace (vqseg_vq_workspace_bytes of ITS shape); one row type per call (bf16 != 0: bf16 rows /
- * quantised rows).  Results are bit-identical to n_levels single calls. */
+ * every level with its own workspace (vqseg_vq_workspace_bytes of ITS shape); one row type per call: bf16 = 0 f32 rows / quantised
+ * rows, 1 bf16 rows / quantised rows, 2 split-3 rows -- x[i] is [n_rows][2 * channels] bf16 = [hi | lo] (what vqseg_s3_split_f writes),
+ * its logical value the fp32 sum hi + lo (what vqseg_s3_merge_f writes): idx is that of the f32 call on the merged rows, and quant[i]
+ * is [n_rows][2 * channels] bf16 = the split of the winning fp32 code rows, byte for byte vqseg_s3_split_f of the f32 call's quant.
+ * Split-3 rows are an eval-mode format: bf16 = 2 needs training = 0 and channels % 8 == 0 (VQSEG_EINVAL otherwise, nothing is
+ * launched).  Results are bit-identical to n_levels single calls. */
 int vqseg_vq_forward_group(int n_levels, int bf16, const void* const* x, const float* const* codebook,
                            const void* const* prepared, const int64_t* n_rows, const int* channels, const int* n_codes,
                            int training, const float* commitment_weight, void* const* quant, int64_t* const* idx,
                            float* const* loss, float* const* dead_pct, void* const* workspace,
                            const size_t* workspace_bytes, void* stream);
 
-/* Diagnostics of the bf16 candidate filter (option "vq_bf16_filter"): byte offset, inside the workspace of a bf16 call of this shape,
+/* Diagnostics of the bf16 candidate filter (options "vq_bf16_filter", "vq_s3_filter"): byte offset, inside the workspace of a bf16 or split-3 call of this shape,
  * of the 64 int32 counters (one per sub-list; their sum = the (row, code) candidate pairs the filter handed to the exact re-score;
  * valid after the call's stream work has finished; a 65th int is the overflow flag: the exact kernel served the level); 0 if the shape does not take the filter
  * (needs n_codes % 256 == 0 and channels % 32 == 0). */
@@ -169,6 +175,12 @@ int vqseg_vq_assign_f32(const float* x, const float* codebook, const void* prepa
 int vqseg_vq_assign_bf16(const void* x, const float* codebook, const void* prepared,
                          int64_t n_rows, int channels, int n_codes, int64_t* idx, float* dmin,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same for split-3 rows: x [n_rows][2 * channels] bf16 = [hi | lo]; idx and dmin are those of vqseg_vq_assign_f32 on the merged
+ * rows (vqseg_s3_merge_f), without that pass over memory.  channels % 8 == 0.  Option "vq_s3_filter" chooses the kernels. */
+int vqseg_vq_assign_s3(const void* x, const float* codebook, const void* prepared,
+                       int64_t n_rows, int channels, int n_codes, int64_t* idx, float* dmin,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* Prepared codebook: the kernel-side image of an nn.Embedding weight (4-channel
  * interleaved, code-padded copy + |e_k|^2).  The reference's codebook never changes after

@@ -44,6 +44,8 @@ SYMBOLS = {
                                     c_size_t, c_void_p]),
     "vqseg_vq_assign_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_size_t, c_void_p]),
+    "vqseg_vq_assign_s3": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_size_t, c_void_p]),
     "vqseg_vq_prepared_bytes": (c_size_t, [c_int, c_int]),
     "vqseg_vq_prepare_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "vqseg_vq_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p,
@@ -337,40 +339,45 @@ def bind(path: str) -> ctypes.CDLL:
     return _bind_symbols(ctypes.CDLL(path))
 
 
-def vq_forward_group(rows_list, codebooks, prepared_list, training: bool, commitment_weights, handle=None):
+def vq_forward_group(rows_list, codebooks, prepared_list, training: bool, commitment_weights, handle=None, s3: bool = False):
     """vq_forward for several independent layers with ONE distance + argmin launch (vqseg_vq_forward_group).
     -> list of (quant, idx, loss (1,), dead_pct ()) per level; bit-identical to per-level vq_forward calls.
-    `handle`: another build of the library (bind()), for measurement code."""
+    `handle`: another build of the library (bind()), for measurement code.
+    `s3`: the rows are split-3 rows (N, 2C) bf16 = [hi | lo] (nnf.S3.rows, eval only); quant comes back in the same form."""
     L = handle or lib()
     nl = len(rows_list)
-    bf16 = rows_list[0].dtype == torch.bfloat16
+    bf16 = 2 if s3 else int(rows_list[0].dtype == torch.bfloat16)
+    if s3 and training:
+        raise HipLibraryError("vq_forward_group: split-3 rows are an eval-mode format (training must be False)")
     dev = rows_list[0].device
     ptr = lambda ps: (c_void_p * nl)(*map(on_gpu, ps))         # the pointers travel inside a host array: a CPU tensor raises here
     ns = np.array([r.shape[0] for r in rows_list], dtype=np.int64)
-    cs = np.array([r.shape[1] for r in rows_list], dtype=np.int32)
+    cs = np.array([w.shape[1] for w in codebooks], dtype=np.int32)            # logical channels (a split-3 row holds twice as many elements)
     ks = np.array([w.shape[0] for w in codebooks], dtype=np.int32)
     cw = np.array([float(w) for w in commitment_weights], dtype=np.float32)
     xs, wps, preps, quants, idxs, scals, wss = [], [], [], [], [], [], []
     for r, w in zip(rows_list, codebooks):
         if r.dtype != rows_list[0].dtype:
             raise HipLibraryError("vq_forward_group: one row type per call")
-        xs.append(tptr(r, "rows", bf=int(bf16)))
-        wps.append(_dev(w, torch.float32, "codebook", w.shape[0] * r.shape[1]))
+        if w.dim() != 2 or r.dim() != 2 or r.shape[1] != (2 if s3 else 1) * w.shape[1]:
+            raise HipLibraryError(f"vq_forward_group: rows {tuple(r.shape)} do not match a codebook {tuple(w.shape)}" + (" (split-3 rows: 2C columns)" if s3 else ""))
+        xs.append(tptr(r, "rows", bf=bf16, numel=r.shape[0] * r.shape[1]))
+        wps.append(_dev(w, torch.float32, "codebook", w.shape[0] * w.shape[1]))
         quants.append(torch.empty_like(r))
         idxs.append(torch.empty(r.shape[0], dtype=torch.int64, device=dev))
         scals.append(torch.empty(2, dtype=torch.float32, device=dev))
-        wss.append(_workspace(L.vqseg_vq_workspace_bytes(r.shape[0], r.shape[1], w.shape[0]), dev))
+        wss.append(_workspace(L.vqseg_vq_workspace_bytes(r.shape[0], w.shape[1], w.shape[0]), dev))
     for w, p_ in zip(codebooks, prepared_list):
         preps.append(tptr(p_, "prepared codebook", dtype=torch.uint8, numel=L.vqseg_vq_prepared_bytes(w.shape[1], w.shape[0])))
     wsb = (c_size_t * nl)(*[w.numel() for w in wss])
-    launch("vqseg_vq_forward_group", dev, nl, int(bf16), ptr(xs), ptr(wps), ptr(preps), ns.ctypes.data, cs.ctypes.data, ks.ctypes.data,
+    launch("vqseg_vq_forward_group", dev, nl, bf16, ptr(xs), ptr(wps), ptr(preps), ns.ctypes.data, cs.ctypes.data, ks.ctypes.data,
            int(bool(training)), cw.ctypes.data, ptr(q.data_ptr() for q in quants), ptr(i.data_ptr() for i in idxs),
            ptr(s.data_ptr() for s in scals), ptr(s.data_ptr() + 4 for s in scals), ptr(w.data_ptr() for w in wss),
            ctypes.cast(wsb, c_void_p), handle=handle)
     if FILTER_DIAG is not None and bf16:                     # diagnostics (tools/vq_filter_diag.py): per level (rows, channels, codes, counter of candidate pairs)
         for r, w, ws_ in zip(rows_list, codebooks, wss):
-            off = L.vqseg_vq_filter_counter_offset(r.shape[0], r.shape[1], w.shape[0])
-            FILTER_DIAG.append((r.shape[0], r.shape[1], w.shape[0], ws_[off:off + 256].view(torch.int32) if off else None))
+            off = L.vqseg_vq_filter_counter_offset(r.shape[0], w.shape[1], w.shape[0])
+            FILTER_DIAG.append((r.shape[0], w.shape[1], w.shape[0], ws_[off:off + 256].view(torch.int32) if off else None))
     return [(q, i, s[0:1], s[1]) for q, i, s in zip(quants, idxs, scals)]
 
 
@@ -395,24 +402,35 @@ def vq_tiles_per_wave(n_rows, n_codes) -> int:
 
 
 def vq_assign(rows: torch.Tensor, codebook: torch.Tensor, want_dmin: bool = False,
-              prepared: Optional[torch.Tensor] = None, want_filter_count: bool = False):
+              prepared: Optional[torch.Tensor] = None, want_filter_count: bool = False, s3: bool = False, want_filter_state: bool = False):
+    """`s3`: rows are split-3 rows (N, 2C) bf16 = [hi | lo]; the result is that of the merged fp32 rows.
+    `want_filter_state` (diagnostics, tests): appends the candidate filter's 65 int32 words of this call -- the 64 sub-list counters of
+    (row, code) pairs handed to the exact re-score, then the overflow flag (the exact kernel served the level) -- or None (no filter)."""
     L = lib()
     n, c = rows.shape
     k = codebook.shape[0]
     bf16 = rows.dtype == torch.bfloat16                      # bf16 activations: same fp32 arithmetic, bf16 quant
-    xp, wp = tptr(rows, "rows", bf=int(bf16), numel=n * c), _dev(codebook, torch.float32, "codebook", k * c)
+    if s3:
+        if c != 2 * codebook.shape[1]:
+            raise HipLibraryError(f"vq_assign: split-3 rows {tuple(rows.shape)} do not match a codebook {tuple(codebook.shape)} (2C columns)")
+        c //= 2
+    xp, wp = tptr(rows, "rows", bf=2 if s3 else int(bf16), numel=n * c * (2 if s3 else 1)), _dev(codebook, torch.float32, "codebook", k * c)
     dev = rows.device
     idx = torch.empty(n, dtype=torch.int64, device=dev)
     dmin = torch.empty(n, dtype=torch.float32, device=dev) if want_dmin else None
     nbytes = L.vqseg_vq_workspace_bytes(n, c, k)
     ws = _workspace(nbytes, dev)
-    launch("vqseg_vq_assign_bf16" if bf16 else "vqseg_vq_assign_f32", dev, xp, wp,                 # the entry point must match the row type
+    launch("vqseg_vq_assign_s3" if s3 else "vqseg_vq_assign_bf16" if bf16 else "vqseg_vq_assign_f32", dev, xp, wp,   # the entry point must match the row type
            tptr(prepared, "prepared codebook", dtype=torch.uint8, numel=L.vqseg_vq_prepared_bytes(c, k)), n, c, k,
            idx.data_ptr(), dmin.data_ptr() if want_dmin else None, ws.data_ptr(), nbytes)
     if want_filter_count:                                    # diagnostics: candidate pairs the bf16 filter handed to the exact re-score (None: no filter)
         off = L.vqseg_vq_filter_counter_offset(n, c, k) if bf16 else 0
         amb = ws[off:off + 256].view(torch.int32).sum() if off else None      # 64 sub-list counters
         return (idx, dmin, amb) if want_dmin else (idx, amb)
+    if want_filter_state:
+        off = L.vqseg_vq_filter_counter_offset(n, c, k) if bf16 else 0
+        state = ws[off:off + 260].view(torch.int32).clone() if off else None
+        return (idx, dmin, state) if want_dmin else (idx, state)
     return (idx, dmin) if want_dmin else idx
 
 

@@ -1,4 +1,5 @@
-// Device-only helpers shared by the NN kernel units (nn_bn / nn_spatial / nn_head / nn_stem; no other file includes this): element
+// Device-only helpers shared by the NN kernel units (nn_bn / nn_spatial / nn_head / nn_stem) and, for the split-3 row format, by the
+// vector quantiser (vq_internal.h); no other file includes this: element
 // and 16-byte vector access to NHWC "rows" (pixel-major, channels contiguous; T = float in precise mode, or __bf16), the flat-index
 // split, and the split-3 row format with its one pair of accessors.  Every function here is __device__ __forceinline__.
 #pragma once

@@ -78,8 +78,10 @@ __device__ __forceinline__ void glds16(const float* g, float* lds_wave_base) {
 
 template <typename TX> struct RawFrag { typedef f32x4 type; };
 template <> struct RawFrag<__bf16> { typedef u32x2 type; };
+template <> struct RawFrag<S3Row> { typedef u32x4 type; };   // 4 channels: [hi (2 words) | lo (2 words)]
 
-// TX: storage type of the pixel rows (float, or __bf16 -- every bf16 value is an exact float, the arithmetic is the same)
+// TX: storage type of the pixel rows (float, or __bf16 -- every bf16 value is an exact float, the arithmetic is the same -- or S3Row:
+// split-3 rows [N][2C], merged to the fp32 value hi + lo where bf16 rows are widened; everything after that load is the same)
 // One launch serves up to VQ_MAX_LEVELS independent quantisation problems ("levels": the three VQ layers of one forward).
 // Workgroup ids [wg_end of the previous level, wg_end) belong to a level; the host orders the levels longest workgroup
 // first (most channels), so that the short workgroups of the last level fill the tail of the launch.
@@ -134,7 +136,8 @@ __global__ __launch_bounds__(256, 2) void vq_assign_f32_kernel(const VqGroup g) 
     const long row0 = row_tile * ROWS_PER_WG + wave * ROWS_PER_WAVE;
     long row = row0 + r;
     if (row > N - 1) row = N - 1;                               // clamp: loads stay in bounds
-    const TX* xrow = x + row * (long)C + 4 * h;
+    constexpr bool S3 = __is_same(TX, S3Row);
+    const TX* xrow = x + row * (S3 ? 2L * C : (long)C) + 4 * h;
 
     f32x16 acc[T];
 #pragma unroll
@@ -168,6 +171,9 @@ __global__ __launch_bounds__(256, 2) void vq_assign_f32_kernel(const VqGroup g) 
             const int col = stage * BK + 8 * j + 4 * h;
             if (col >= C) {
                 a[j] = RawA{};
+            } else if constexpr (S3) {
+                const u32x2 hi = *reinterpret_cast<const u32x2*>(xrow + stage * BK + 8 * j), lo = *reinterpret_cast<const u32x2*>(xrow + C + stage * BK + 8 * j);
+                a[j] = RawA{hi[0], hi[1], lo[0], lo[1]};
             } else {
                 a[j] = *reinterpret_cast<const RawA*>(xrow + stage * BK + 8 * j);
             }
@@ -192,6 +198,11 @@ __global__ __launch_bounds__(256, 2) void vq_assign_f32_kernel(const VqGroup g) 
                 const unsigned lo = src[j][0], hi = src[j][1];
                 dst[j] = f32x4{__builtin_bit_cast(float, lo << 16), __builtin_bit_cast(float, lo & 0xFFFF0000u),
                                __builtin_bit_cast(float, hi << 16), __builtin_bit_cast(float, hi & 0xFFFF0000u)};
+                if constexpr (S3) {                                  // + the lo half: the merged value, as s3_load8 forms it
+                    const unsigned l0 = src[j][2], l1 = src[j][3];
+                    dst[j] += f32x4{__builtin_bit_cast(float, l0 << 16), __builtin_bit_cast(float, l0 & 0xFFFF0000u),
+                                    __builtin_bit_cast(float, l1 << 16), __builtin_bit_cast(float, l1 & 0xFFFF0000u)};
+                }
             }
         }
     };
@@ -402,7 +413,7 @@ static void launch_assign_t(const VqGroup& g, hipStream_t st) {
     hipLaunchKernelGGL((vq_assign_f32_kernel<T, TX>), dim3(g.lv[g.n - 1].wg_end), dim3(256), lds, st, g);
 }
 
-void launch_assign_levels(const VqLevel* lv, int n, int T, int x_bf16, hipStream_t st) {
+void launch_assign_levels(const VqLevel* lv, int n, int T, int row_type, hipStream_t st) {
     VqGroup g;
     g.n = n;
     for (int q = 0; q < n; ++q) g.lv[q] = lv[q];
@@ -410,7 +421,8 @@ void launch_assign_levels(const VqLevel* lv, int n, int T, int x_bf16, hipStream
     g.tl = g_timeline;
 #endif
 #define VQ_ASSIGN(T_)                                                 \
-    if (x_bf16) launch_assign_t<T_, __bf16>(g, st);                   \
+    if (row_type == VQ_ROWS_S3) launch_assign_t<T_, S3Row>(g, st);    \
+    else if (row_type) launch_assign_t<T_, __bf16>(g, st);            \
     else launch_assign_t<T_, float>(g, st)
     switch (T) {
         case 8: VQ_ASSIGN(8); break;

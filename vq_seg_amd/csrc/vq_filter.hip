@@ -37,6 +37,25 @@ namespace vqseg {
 // wins.  Hence: if D_a <= D_b (1 + 2^-20) then s~_a <= s~_b + 2 eps + 2^-20 (|x|^2 + E + 2 S_max) =: BAND (x 1.25 for margin).
 // Any code that can win or tie under the exact arithmetic lies within BAND of the approximate minimum.
 //
+// Split-3 rows (row type VQ_ROWS_S3, the template argument S3): a row is [hi | lo], two bf16 values per channel (nn_device.h), and
+// its logical value is x = fl(hi + lo), the fp32 sum s3_merge_kernel writes.  hi and lo ARE bf16 MFMA operands, so stage 1 issues
+//       s~_k = |e_k|^2 - 2 (x_hi . e_hi_k + x_hi . e_lo_k + x_lo . e_hi_k)
+// into the same accumulators (the LDS stage of Eb is read once for both row halves) and leaves out x_lo . e_lo -- a fourth product
+// would cost a third more MFMA time to remove a term that is a tenth of the band at C = 512 and less above (the truncation term
+// below dominates); stages 2 and 3 are row-type blind resp. read the merged value.  The band, term by term, S as above with |x| = |hi + lo|:
+//     exact chain of C fmaf's on the merged row            |dot_chain - x.e| <= C 2^-24 S                      (as for bf16 rows)
+//     the merge rounds once: x = (hi + lo)(1 + d), |d| <= 2^-24 (d = 0 for rows s3_store8 wrote from an fp32 value: hi + lo is then
+//     a multiple of that value's ulp below twice its binade; rows handed in through the ABI need not be)    <= 2^-24 S
+//     split residual of the codebook, |rho| <= 2^-16 |e|: hi = RN_bf16(e) leaves |e - hi| <= half an ulp of 8 significant bits
+//     <= 2^-8 |e| (attained just above a power of two), lo = RN_bf16(e - hi) leaves 2^-8 of that          |x.rho| <= 2^-16 S
+//     the dropped product: s3_store8 rounds hi = RN_bf16(v) (s3_pack2: the (__bf16) conversion, round to nearest even) and
+//     lo = RN_bf16(v - hi), v - hi exact in fp32, so |x_lo| <= 2^-8 |v| and |v| <= |x| (1 + 2^-15); with |e_lo| <= 2^-8 |e|
+//                                                           |x_lo . e_lo| <= 2^-16 S (1 + 2^-15)
+//       (NOT 2^-18 S: v = 1 + 2^-8 - 2^-23 splits into hi = 1, lo = 2^-8 - 2^-16; the margin factor absorbs the 2^-15)
+//     3 C / 16 bf16 MFMAs (three per 16 channels), each as above                      |dot~ - (the three products)| <= (3 C / 16) 17 2^-24 S
+//     |x|^2 of the band: the fp32 sum of squares of the merged values (the exact kernel's operand), the final roundings as above
+// so eps_S3 = 2 (C 2^-24 + 2^-24 + 2^-16 + 2^-16 + (3 C / 16) 17 2^-24) S_max + 2^-22 (|x|^2 + E + 2 S_max), BAND as above from eps_S3.
+//
 // Roles are swapped against the exact kernel: codes are the MFMA's M dimension (LDS, staged by LDS-DMA), pixels the N dimension
 // (registers, straight from global in fragment shape), so that a lane owns ONE pixel per fragment and the minimum / band count over
 // its codes needs no cross-lane traffic (the two half-waves meet in one shuffle).
@@ -67,8 +86,10 @@ struct FilterConsts {
     float c_s, c_r;             // BAND = c_s * sqrt(|x|^2 * E) + c_r * (|x|^2 + E)   (per level: depends on C)
 };
 
+template <bool S3>
 __global__ __launch_bounds__(256, 2) void vq_filter_bf16_kernel(const VqFilterGroup g, const FilterConsts fc0, const FilterConsts fc1,
                                                                 const FilterConsts fc2, const FilterConsts fc3) {
+    constexpr int NH = S3 ? 2 : 1;                              // bf16 fragments per channel of a row: hi, and lo of a split-3 row
     int lvl = 0;
     while (lvl + 1 < g.n && blockIdx.x >= g.lv[lvl].wg_end) ++lvl;
     const unsigned bid = blockIdx.x - (lvl ? g.lv[lvl - 1].wg_end : 0u);
@@ -101,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void vq_filter_bf16_kernel(const VqFilterGr
     for (int p = 0; p < 2; ++p) {
         long row = row_tile * F_ROWS + wp * 64 + p * 32 + r;
         if (row > N - 1) row = N - 1;
-        xrow[p] = x + row * (long)C + 8 * h;
+        xrow[p] = x + row * (long)(NH * C) + 8 * h;              // split-3: the lo half of the row starts C elements further
     }
 
     f32x16 acc[2][4];
@@ -125,21 +146,25 @@ __global__ __launch_bounds__(256, 2) void vq_filter_bf16_kernel(const VqFilterGr
             glds16b(src, dst + (hlslab * F_CODES + quarter * 64) * 16);
         }
     };
-    auto load_x = [&](int stage, u32x4 (&xf)[2][2]) {
+    auto load_x = [&](int stage, u32x4 (&xf)[2][2][NH]) {
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) xf[p][q] = *reinterpret_cast<const u32x4*>(xrow[p] + stage * F_BK + q * 16);
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int w = 0; w < NH; ++w) xf[p][q][w] = *reinterpret_cast<const u32x4*>(xrow[p] + w * C + stage * F_BK + q * 16);
     };
 
-    u32x4 xcur[2][2], xnxt[2][2];
+    u32x4 xcur[2][2][NH], xnxt[2][2][NH];
     fill(0, 0);
     if (n_stage > 1) fill(1, 1);
     load_x(0, xcur);
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
-        for (int q = 0; q < 2; ++q) xnxt[p][q] = u32x4{0u, 0u, 0u, 0u};
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int w = 0; w < NH; ++w) xnxt[p][q][w] = u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
 
     const char* a_lane = Bs + ((h * F_CODES) + wc * 128 + r) * 16;     // + buf * STAGE + ((hl * 4 + 2 q) * F_CODES + 32 t) * 16
@@ -156,10 +181,14 @@ __global__ __launch_bounds__(256, 2) void vq_filter_bf16_kernel(const VqFilterGr
             }
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                const bf16x8 xb = __builtin_bit_cast(bf16x8, xcur[p][q]);
+                const bf16x8 xb = __builtin_bit_cast(bf16x8, xcur[p][q][0]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {                     // |x|^2 of this lane's 8 channels (fp32; only the band needs it)
-                    const float lo = __builtin_bit_cast(float, xcur[p][q][e] << 16), hi = __builtin_bit_cast(float, xcur[p][q][e] & 0xFFFF0000u);
+                    float lo = __builtin_bit_cast(float, xcur[p][q][0][e] << 16), hi = __builtin_bit_cast(float, xcur[p][q][0][e] & 0xFFFF0000u);
+                    if constexpr (S3) {                           // of the merged values, as s3_load8 forms them
+                        lo += __builtin_bit_cast(float, xcur[p][q][NH - 1][e] << 16);
+                        hi += __builtin_bit_cast(float, xcur[p][q][NH - 1][e] & 0xFFFF0000u);
+                    }
                     xn_part[p] = __builtin_fmaf(lo, lo, xn_part[p]);
                     xn_part[p] = __builtin_fmaf(hi, hi, xn_part[p]);
                 }
@@ -168,6 +197,11 @@ __global__ __launch_bounds__(256, 2) void vq_filter_bf16_kernel(const VqFilterGr
                     acc[p][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], xb, acc[p][t], 0, 0, 0);
                     acc[p][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], xb, acc[p][t], 0, 0, 0);
                 }
+                if constexpr (S3) {                               // x_lo . e_hi (x_lo . e_lo is left to the band)
+                    const bf16x8 xl = __builtin_bit_cast(bf16x8, xcur[p][q][NH - 1]);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) acc[p][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], xl, acc[p][t], 0, 0, 0);
+                }
             }
         }
         __syncthreads();                                        // stage s + 1 landed (issued a whole stage ago); buffer s & 1 is free
@@ -175,7 +209,9 @@ __global__ __launch_bounds__(256, 2) void vq_filter_bf16_kernel(const VqFilterGr
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) xcur[p][q] = xnxt[p][q];
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int w = 0; w < NH; ++w) xcur[p][q][w] = xnxt[p][q][w];
     }
 
     // ---- epilogue: scores of this lane's 64 codes per pixel fragment, minimum, band count
@@ -346,16 +382,18 @@ __global__ __launch_bounds__(256) void vq_resolve_kernel(const VqFilterGroup g, 
 // Stage 3 (all levels): the exact kernel's arithmetic for the listed (row, code) pairs of OPEN rows, one lane per pair: dot = the
 // "mfma8" fmaf chain, |x|^2 its two half chains, |e|^2 from the prepared blob, d = sqrt(max(fmaf(-2, dot, |x|^2) + |e|^2, 0)),
 // key = (bits(d) << 32) | code merged by atomicMin like the exact kernel's code groups (the lowest code wins a tie).
+template <bool S3>
 struct RescoreTrip {                                        // 32 channels of one (row, code) pair
-    u32x4 xw[4];
+    u32x4 xw[4][S3 ? 2 : 1];                                // split-3 rows: [hi, lo], merged where the chain reads them
     f32x4 e0[4], e1[4];
 };
 
-template <bool ROWMAJOR>
-__device__ __forceinline__ void rescore_load(RescoreTrip& t, const unsigned short* xr, const float* er, int c, int Kp) {
+template <bool ROWMAJOR, bool S3>
+__device__ __forceinline__ void rescore_load(RescoreTrip<S3>& t, const unsigned short* xr, const float* er, int c, int Kp, int C) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-        t.xw[u] = *reinterpret_cast<const u32x4*>(xr + c + 8 * u);
+        t.xw[u][0] = *reinterpret_cast<const u32x4*>(xr + c + 8 * u);
+        if constexpr (S3) t.xw[u][1] = *reinterpret_cast<const u32x4*>(xr + C + c + 8 * u);
         if (ROWMAJOR) {
             t.e0[u] = *reinterpret_cast<const f32x4*>(er + c + 8 * u);
             t.e1[u] = *reinterpret_cast<const f32x4*>(er + c + 8 * u + 4);
@@ -366,13 +404,20 @@ __device__ __forceinline__ void rescore_load(RescoreTrip& t, const unsigned shor
     }
 }
 
-__device__ __forceinline__ void rescore_fma(const RescoreTrip& t, float& dot, float& xa, float& xb) {
+template <bool S3>
+__device__ __forceinline__ void rescore_fma(const RescoreTrip<S3>& t, float& dot, float& xa, float& xb) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-        const float xv[8] = {__builtin_bit_cast(float, t.xw[u][0] << 16), __builtin_bit_cast(float, t.xw[u][0] & 0xFFFF0000u),
-                             __builtin_bit_cast(float, t.xw[u][1] << 16), __builtin_bit_cast(float, t.xw[u][1] & 0xFFFF0000u),
-                             __builtin_bit_cast(float, t.xw[u][2] << 16), __builtin_bit_cast(float, t.xw[u][2] & 0xFFFF0000u),
-                             __builtin_bit_cast(float, t.xw[u][3] << 16), __builtin_bit_cast(float, t.xw[u][3] & 0xFFFF0000u)};
+        float xv[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            xv[2 * e] = __builtin_bit_cast(float, t.xw[u][0][e] << 16);
+            xv[2 * e + 1] = __builtin_bit_cast(float, t.xw[u][0][e] & 0xFFFF0000u);
+            if constexpr (S3) {                                   // the merged value (s3_load8)
+                xv[2 * e] += __builtin_bit_cast(float, t.xw[u][1][e] << 16);
+                xv[2 * e + 1] += __builtin_bit_cast(float, t.xw[u][1][e] & 0xFFFF0000u);
+            }
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             dot = __builtin_fmaf(xv[e], t.e0[u][e], dot);
@@ -385,7 +430,7 @@ __device__ __forceinline__ void rescore_fma(const RescoreTrip& t, float& dot, fl
 
 // one sub-list of one level: lane i takes pairs i, i + nthreads, ...; a chain is serial (C dependent fmaf's), so its loads run two
 // 32-channel trips ahead of the arithmetic
-template <bool ROWMAJOR>
+template <bool ROWMAJOR, bool S3>
 __device__ __forceinline__ void rescore_pairs(const VqFilterLevel& L, int list, int tid, int nthreads) {
     int n = L.pair_count[list];
     if (n > L.pair_cap) n = L.pair_cap;                        // overflow: the gated exact launch serves the level anyway
@@ -397,19 +442,19 @@ __device__ __forceinline__ void rescore_pairs(const VqFilterLevel& L, int list, 
         const long row = (long)(rc >> 32);
         const unsigned k = (unsigned)(rc & 0xffffffffull);
         if (L.brow[row] == -__builtin_inff()) continue;         // a decided row
-        const unsigned short* xr = x + row * (long)C;
+        const unsigned short* xr = x + row * (long)(S3 ? 2 * C : C);
         const float* er = ROWMAJOR ? L.W + (size_t)k * C : L.E4 + (size_t)k * 4;
         float dot = 0.0f, xa = 0.0f, xb = 0.0f;
-        RescoreTrip t0, t1, t2;                                  // C % 32 == 0 on this path
-        rescore_load<ROWMAJOR>(t0, xr, er, 0, Kp);
-        if (C > 32) rescore_load<ROWMAJOR>(t1, xr, er, 32, Kp);
+        RescoreTrip<S3> t0, t1, t2;                              // C % 32 == 0 on this path
+        rescore_load<ROWMAJOR>(t0, xr, er, 0, Kp, C);
+        if (C > 32) rescore_load<ROWMAJOR>(t1, xr, er, 32, Kp, C);
         int c = 0;
         for (; c + 96 <= C; c += 96) {
-            if (c + 64 < C) rescore_load<ROWMAJOR>(t2, xr, er, c + 64, Kp);
+            if (c + 64 < C) rescore_load<ROWMAJOR>(t2, xr, er, c + 64, Kp, C);
             rescore_fma(t0, dot, xa, xb);
-            if (c + 96 < C) rescore_load<ROWMAJOR>(t0, xr, er, c + 96, Kp);
+            if (c + 96 < C) rescore_load<ROWMAJOR>(t0, xr, er, c + 96, Kp, C);
             rescore_fma(t1, dot, xa, xb);
-            if (c + 128 < C) rescore_load<ROWMAJOR>(t1, xr, er, c + 128, Kp);
+            if (c + 128 < C) rescore_load<ROWMAJOR>(t1, xr, er, c + 128, Kp, C);
             rescore_fma(t2, dot, xa, xb);
         }
         if (c < C) {                                            // one or two trips left (already loaded into t0 / t1)
@@ -423,30 +468,32 @@ __device__ __forceinline__ void rescore_pairs(const VqFilterLevel& L, int list, 
 }
 
 // Stage 3 launch: every level gets its own workgroups (a multiple of F_LISTS), workgroup b of a level serves sub-list b % F_LISTS
+template <bool S3>
 __global__ __launch_bounds__(256) void vq_rescore_kernel(const VqFilterGroup g) {
     int lvl = 0;
     while (lvl + 1 < g.n && blockIdx.x >= g.lv[lvl].sblk_end) ++lvl;
     const unsigned first = lvl ? g.lv[lvl - 1].sblk_end : 0u;
     const unsigned b = blockIdx.x - first, per_list = (g.lv[lvl].sblk_end - first) / F_LISTS;
     const int list = (int)(b % F_LISTS), tid = (int)(b / F_LISTS) * 256 + threadIdx.x, nthreads = (int)per_list * 256;
-    if (g.lv[lvl].W) rescore_pairs<true>(g.lv[lvl], list, tid, nthreads);
-    else rescore_pairs<false>(g.lv[lvl], list, tid, nthreads);
+    if (g.lv[lvl].W) rescore_pairs<true, S3>(g.lv[lvl], list, tid, nthreads);
+    else rescore_pairs<false, S3>(g.lv[lvl], list, tid, nthreads);
 }
 
 // The exact kernel's distance of ONE given code per row on the vector ALU (tests ask for the winning distance; rows the filter
 // decided never went through the exact kernel): the same fmaf chains in the same order (file header, "mfma8").
+template <bool S3>
 __global__ __launch_bounds__(256) void vq_exact_dist_kernel(const unsigned short* __restrict__ x, const float* __restrict__ E4, int Kp,
                                                             const float* __restrict__ enorm, const long long* __restrict__ idx, long N, int C,
                                                             float* __restrict__ dmin) {
     const long row = (long)blockIdx.x * 256 + threadIdx.x;
     if (row >= N) return;
-    const unsigned short* xr = x + row * (long)C;
+    const unsigned short* xr = x + row * (long)(S3 ? 2 * C : C);
     const long long k = idx[row];
     float dot = 0.0f, xa = 0.0f, xb = 0.0f;
     for (int c = 0; c + 8 <= C; c += 8) {
         float xv[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) xv[e] = __builtin_bit_cast(float, (unsigned)xr[c + e] << 16);
+        for (int e = 0; e < 8; ++e) xv[e] = S3 ? s3_elem(xr, C, c + e) : __builtin_bit_cast(float, (unsigned)xr[c + e] << 16);
         const f32x4 e0 = *reinterpret_cast<const f32x4*>(E4 + ((size_t)(c / 4) * Kp + k) * 4);          // channels c .. c + 3 of code k
         const f32x4 e1 = *reinterpret_cast<const f32x4*>(E4 + ((size_t)(c / 4 + 1) * Kp + k) * 4);      // channels c + 4 .. c + 7
 #pragma unroll
@@ -516,28 +563,36 @@ void launch_prepare_filter(const float* W, int K, int C, int Kp, const float* en
     hipLaunchKernelGGL(vq_enorm_max, dim3(1), dim3(256), 0, st, enorm, K, en_max);
 }
 
-void launch_filter(const VqFilterGroup& fg, int force_all, hipStream_t st) {
+void launch_filter(const VqFilterGroup& fg, int row_type, int force_all, hipStream_t st) {
+    const bool s3 = row_type == VQ_ROWS_S3;
     FilterConsts fc[VQ_MAX_LEVELS] = {};
     for (int q = 0; q < fg.n; ++q) {
         // BAND = 1.25 * [ 2 eps + 2^-20 (|x|^2 + E + 2 S) ],  eps = 2 (C 2^-24 + 2^-18 + (C / 8) 17 2^-24) S + 2^-22 (|x|^2 + E + 2 S),
-        // S = sqrt(|x|^2 E)   (derivation at vq_filter_bf16_kernel)
+        // S = sqrt(|x|^2 E); split-3 rows: eps = 2 (C 2^-24 + 2^-24 + 2^-16 + 2^-16 + (3 C / 16) 17 2^-24) S + the same tail
+        // (both derivations at vq_filter_bf16_kernel)
         const double u = ldexp(1.0, -24), cc = (double)fg.lv[q].C;
-        const double per_s = 2.0 * (cc * u + ldexp(1.0, -18) + (cc / 8.0) * 17.0 * u);
+        const double per_s = s3 ? 2.0 * (cc * u + u + 2.0 * ldexp(1.0, -16) + (3.0 * cc / 16.0) * 17.0 * u)
+                                : 2.0 * (cc * u + ldexp(1.0, -18) + (cc / 8.0) * 17.0 * u);
         const double tail = 2.0 * ldexp(1.0, -22) + ldexp(1.0, -20);
         fc[q].c_s = (float)(1.25 * (2.0 * per_s + 2.0 * tail));
         fc[q].c_r = (float)(1.25 * tail);
     }
     const VqFilterLevel& last = fg.lv[fg.n - 1];
-    hipLaunchKernelGGL(vq_filter_bf16_kernel, dim3(last.wg_end), dim3(256), (size_t)(2 * F_STAGE_BYTES + F_CODES * sizeof(float)), st, fg, fc[0],
-                       fc[1], fc[2], fc[3]);
+    const size_t lds = (size_t)(2 * F_STAGE_BYTES + F_CODES * sizeof(float));
+    if (s3) hipLaunchKernelGGL(vq_filter_bf16_kernel<true>, dim3(last.wg_end), dim3(256), lds, st, fg, fc[0], fc[1], fc[2], fc[3]);
+    else hipLaunchKernelGGL(vq_filter_bf16_kernel<false>, dim3(last.wg_end), dim3(256), lds, st, fg, fc[0], fc[1], fc[2], fc[3]);
     hipLaunchKernelGGL(vq_resolve_kernel, dim3(last.rblk_end), dim3(256), 0, st, fg, force_all);
-    hipLaunchKernelGGL(vq_rescore_kernel, dim3(last.sblk_end), dim3(256), 0, st, fg);
+    if (s3) hipLaunchKernelGGL(vq_rescore_kernel<true>, dim3(last.sblk_end), dim3(256), 0, st, fg);
+    else hipLaunchKernelGGL(vq_rescore_kernel<false>, dim3(last.sblk_end), dim3(256), 0, st, fg);
 }
 
-void launch_exact_dist(const void* x, const float* E4, int Kp, const float* enorm, const int64_t* idx, int64_t N, int C, float* dmin,
-                       hipStream_t st) {
-    hipLaunchKernelGGL(vq_exact_dist_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, static_cast<const unsigned short*>(x), E4, Kp,
-                       enorm, reinterpret_cast<const long long*>(idx), (long)N, C, dmin);
+void launch_exact_dist(const void* x, int row_type, const float* E4, int Kp, const float* enorm, const int64_t* idx, int64_t N, int C,
+                       float* dmin, hipStream_t st) {
+    const dim3 grid((unsigned)((N + 255) / 256));
+    const unsigned short* xr = static_cast<const unsigned short*>(x);
+    const long long* ix = reinterpret_cast<const long long*>(idx);
+    if (row_type == VQ_ROWS_S3) hipLaunchKernelGGL(vq_exact_dist_kernel<true>, grid, dim3(256), 0, st, xr, E4, Kp, enorm, ix, (long)N, C, dmin);
+    else hipLaunchKernelGGL(vq_exact_dist_kernel<false>, grid, dim3(256), 0, st, xr, E4, Kp, enorm, ix, (long)N, C, dmin);
 }
 
 }  // namespace vqseg

@@ -43,12 +43,14 @@ static int g_vq_fine_split = 1;                             // option "vq_fine_s
 static int g_vq_bf16_filter = 1;                            // bf16 rows: candidate filter + exact re-score (0: the exact kernel on every row)
 static int g_vq_filter_force_all = 0;                       // tests: 1 = every row is re-scored by the exact kernel (the filter decides nothing)
 static int g_vq_filter_launches = 0;                        // launches that took the filter path (tests read and reset it)
+static int g_vq_s3_filter = 1;                              // split-3 rows: the same filter on [hi | lo] (0: the exact kernel, merging on load)
 static const Option VQ_OPTIONS[] = {
     {"vq_max_tiles_per_wave", &g_vq_max_tiles, OPT_POW2_FAIL, 1, 8},
     {"vq_fine_split", &g_vq_fine_split, OPT_FLAG},
     {"vq_bf16_filter", &g_vq_bf16_filter, OPT_FLAG},
     {"vq_filter_force_all", &g_vq_filter_force_all, OPT_FLAG},
     {"vq_filter_launches", &g_vq_filter_launches},
+    {"vq_s3_filter", &g_vq_s3_filter, OPT_FLAG},
 };
 
 int vq_set_option(const char* key, int value) { return apply_option(VQ_OPTIONS, key, value); }
@@ -104,7 +106,8 @@ struct ProfShape {
     int64_t n;
     int c, k;
     int slot, group;            // first record of the launch this level ran in (its event pair), number of levels in that launch
-    int kind;                   // 0: exact fp32 MFMA kernel on f32 rows, 1: on bf16 rows, 2: bf16 candidate filter + exact re-score
+    int kind;                   // 0: exact fp32 MFMA kernel on f32 rows (or split-3 rows merged on load), 1: on bf16 rows, 2: bf16 candidate
+                                // filter + exact re-score (bf16 or split-3 rows)
 };
 struct Profile {
     bool enabled = false;
@@ -199,9 +202,9 @@ hipError_t launch_assign_group(int n, const void* const* x, int x_bf16, const in
     for (int i = 0; i < n; ++i)                                  // longest workgroups (most channels) first
         for (int j = i + 1; j < n; ++j)
             if (C[order[j]] > C[order[i]]) { const int t = order[i]; order[i] = order[j]; order[j] = t; }
-    // bf16 rows of layers with whole 256-code chunks take the candidate filter: bf16 MFMA scores -> per-row decision -> the exact
-    // kernel (indirect mode) on the rows the filter left open.  Same keys as the exact kernel on every row.
-    bool filter = x_bf16 && g_vq_bf16_filter;
+    // bf16 and split-3 rows of layers with whole 256-code chunks take the candidate filter: bf16 MFMA scores -> per-row decision -> the
+    // exact kernel (indirect mode) on the rows the filter left open.  Same keys as the exact kernel on every row.
+    bool filter = x_bf16 == VQ_ROWS_S3 ? g_vq_s3_filter != 0 : (x_bf16 && g_vq_bf16_filter);
     for (int i = 0; i < n; ++i) filter = filter && filter_shape_ok(C[i], K[i]);
     VqLevel lv[VQ_MAX_LEVELS];
     VqFilterGroup fg;
@@ -250,12 +253,12 @@ hipError_t launch_assign_group(int n, const void* const* x, int x_bf16, const in
     const size_t slot = g_prof.shape.size();
     if (rec) {
         // one event pair for the launch; its time is apportioned to the levels by their flops (2 N K C) when collected
-        for (int i = 0; i < n; ++i) g_prof.shape.push_back({N[i], C[i], K[i], (int)slot, n, filter ? 2 : (x_bf16 ? 1 : 0)});
+        for (int i = 0; i < n; ++i) g_prof.shape.push_back({N[i], C[i], K[i], (int)slot, n, filter ? 2 : (x_bf16 == VQ_ROWS_BF16 ? 1 : 0)});
         (void)hipEventRecord(g_prof.ev[2 * slot], st);
     }
     if (filter) {
         ++g_vq_filter_launches;
-        launch_filter(fg, g_vq_filter_force_all, st);
+        launch_filter(fg, x_bf16, g_vq_filter_force_all, st);
     }
     launch_assign_levels(lv, n, T, x_bf16, st);
     if (rec) (void)hipEventRecord(g_prof.ev[2 * slot + 1], st);
@@ -266,7 +269,7 @@ hipError_t launch_assign_group(int n, const void* const* x, int x_bf16, const in
         if (filter && dmin && dmin[i]) {
             // rows the filter decided carry no exact distance: recompute the winner's on the vector ALU, in the exact kernel's order
             const PreparedView pv = prepared_view(prepared[i], C[i], K[i]);
-            launch_exact_dist(x[i], pv.E4, plans[i].Kp, pv.enorm, idx[i], N[i], C[i], dmin[i], st);
+            launch_exact_dist(x[i], x_bf16, pv.E4, plans[i].Kp, pv.enorm, idx[i], N[i], C[i], dmin[i], st);
         }
     }
     return hipGetLastError();

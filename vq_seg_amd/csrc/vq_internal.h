@@ -4,6 +4,7 @@
 // No struct in this file depends on a build flag, so a unit compiled with -DVQ_TIMELINE / -DVQ_SHAPE16 / -DVQ_BIG_STAGE links with the
 // regular objects.  The one struct whose layout does (VqGroup: the timeline pointer) is private to vq_assign.hip.
 #pragma once
+#include "nn_device.h"        // split-3 rows: S3Row, s3_pack2 (the one pair of split / merge functions of the format)
 #include "vq_kernels.h"
 
 namespace vqseg {
@@ -22,9 +23,18 @@ constexpr int GATHER_ROWS_PER_BLOCK = 16;   // 4 waves x 4 rows in flight
 constexpr int KM_RB = 1024;    // rows per block of the histogram / list passes
 constexpr int KM_SEG = 128;    // members per segment of the sum pass
 
+// ---- row types of the distance launch (the `x_bf16` / `bf16` argument of the launchers and of the C ABI): fp32 rows [N][C], bf16
+// rows [N][C], split-3 rows [N][2C] bf16 = [hi | lo] (nn_device.h).  The logical value of a split-3 element is the fp32 sum
+// hi + lo -- what s3_load8 / s3_merge_kernel produce -- and every result is defined by it.
+constexpr int VQ_ROWS_F32 = 0, VQ_ROWS_BF16 = 1, VQ_ROWS_S3 = 2;
+// the merged value of element c of a split-3 row (hi at [0, C), lo at [C, 2C)): s3_load8's sum, one element
+__device__ __forceinline__ float s3_elem(const unsigned short* row, int C, int c) {
+    return __builtin_bit_cast(float, (unsigned)row[c] << 16) + __builtin_bit_cast(float, (unsigned)row[C + c] << 16);
+}
+
 // ---- one level of the exact distance + argmin launch (vq_assign_f32_kernel)
 struct VqLevel {
-    const void* x;              // pixel rows [N][C] (f32 or bf16: one type per launch)
+    const void* x;              // pixel rows [N][C] (f32 or bf16) or [N][2C] (split-3): one type per launch
     const float* E4;            // prepared codebook
     const float* enorm;
     unsigned long long* keys;   // [N] (distance bits << 32 | code), pre-set to ~0
@@ -39,7 +49,7 @@ struct VqLevel {
 };
 // one level of the bf16 candidate filter launch (vq_filter_bf16_kernel)
 struct VqFilterLevel {
-    const void* x;              // bf16 pixel rows [N][C]
+    const void* x;              // bf16 pixel rows [N][C], or split-3 rows [N][2C] (one type per launch)
     const unsigned short* Eb;   // [2][C / 8][Kp][8] bf16: hi / lo split of the codebook
     const float* enorm;         // |e_k|^2 (the exact kernel's values)
     const float* en_max;        // max_k |e_k|^2
@@ -93,13 +103,13 @@ struct PreparedView {
 PreparedView prepared_view(const void* prepared, int C, int K);
 
 // ---- launchers one unit offers to vq_host.hip.  Like the kernels' own launches they report nothing: the caller reads hipGetLastError.
-// vq_assign.hip: n levels in one launch of vq_assign_f32_kernel<T, float | bf16>; the grid is lv[n - 1].wg_end
-void launch_assign_levels(const VqLevel* lv, int n, int T, int x_bf16, hipStream_t st);
+// vq_assign.hip: n levels in one launch of vq_assign_f32_kernel<T, float | bf16 | S3Row> (row_type: VQ_ROWS_*); the grid is lv[n - 1].wg_end
+void launch_assign_levels(const VqLevel* lv, int n, int T, int row_type, hipStream_t st);
 // vq_filter.hip: the filter's image of the codebook (after launch_prepare_exact: reads enorm); the three stages (grids: the last
 // level's wg_end / rblk_end / sblk_end); the exact distance of each row's winning code
 void launch_prepare_filter(const float* W, int K, int C, int Kp, const float* enorm, unsigned short* Eb, float* en_max, hipStream_t st);
-void launch_filter(const VqFilterGroup& fg, int force_all, hipStream_t st);
-void launch_exact_dist(const void* x, const float* E4, int Kp, const float* enorm, const int64_t* idx, int64_t N, int C, float* dmin,
+void launch_filter(const VqFilterGroup& fg, int row_type, int force_all, hipStream_t st);      // row_type: VQ_ROWS_BF16 or VQ_ROWS_S3
+void launch_exact_dist(const void* x, int row_type, const float* E4, int Kp, const float* enorm, const int64_t* idx, int64_t N, int C, float* dmin,
                        hipStream_t st);
 // vq_tail.hip: the pre-set of a grouped launch (grid: the last level's end); keys -> idx / dmin / histogram of level i
 void launch_group_init(const VqInitGroup& ig, hipStream_t st);

@@ -77,6 +77,9 @@ __device__ __forceinline__ void st4(TA* p, long v, const f32x4& q) {
     }
 }
 
+// TA = S3Row (eval only: split-3 rows never reach a training forward): quant is [N][2C] = [hi | lo] of the winning fp32 code row,
+// split by s3_store8 -- the function s3_split_kernel applies, so the bytes are those of the fp32 gather followed by that kernel; x
+// is not read.  8 channels per lane there (C % 8 == 0).
 template <typename TA>
 __global__ __launch_bounds__(256) void vq_gather_kernel(const TA* __restrict__ x, const float* __restrict__ W,
                                                         const long long* __restrict__ idx, long N, int C,
@@ -92,6 +95,24 @@ __global__ __launch_bounds__(256) void vq_gather_kernel(const TA* __restrict__ x
         long long k[RG];
 #pragma unroll
         for (int j = 0; j < RG; ++j) k[j] = row0 + j < N ? idx[row0 + j] : 0;
+        if constexpr (__is_same(TA, S3Row)) {
+            for (int v = lane; v < (C >> 3); v += 64) {
+                f32x4 e0[RG], e1[RG];
+#pragma unroll
+                for (int j = 0; j < RG; ++j)
+                    if (row0 + j < N) {
+                        e0[j] = reinterpret_cast<const f32x4*>(W + k[j] * (long)C)[2 * v];
+                        e1[j] = reinterpret_cast<const f32x4*>(W + k[j] * (long)C)[2 * v + 1];
+                    }
+#pragma unroll
+                for (int j = 0; j < RG; ++j)
+                    if (row0 + j < N) {
+                        const float q[8] = {e0[j][0], e0[j][1], e0[j][2], e0[j][3], e1[j][0], e1[j][1], e1[j][2], e1[j][3]};
+                        s3_store8(reinterpret_cast<unsigned short*>(quant) + (row0 + j) * 2L * C, C, 8 * v, q);
+                    }
+            }
+            continue;
+        }
         for (int v = lane; v < c4; v += 64) {
             f32x4 e[RG], xv[RG];
 #pragma unroll
@@ -219,7 +240,10 @@ hipError_t launch_gather(const void* x, int bf16, const float* W, const int64_t*
     int* hist = reinterpret_cast<int*>(ws + p.off_hist);
     float* partial = reinterpret_cast<float*>(ws + p.off_partial);
     // hist: filled by launch_assign (vq_unpack_keys), which every forward runs first on the same workspace
-    if (bf16)
+    if (bf16 == VQ_ROWS_S3)
+        hipLaunchKernelGGL(vq_gather_kernel<S3Row>, dim3(p.gather_blocks), dim3(256), 0, st, static_cast<const S3Row*>(x), W,
+                           reinterpret_cast<const long long*>(idx), (long)N, C, 0, static_cast<S3Row*>(quant), partial);
+    else if (bf16)
         hipLaunchKernelGGL(vq_gather_kernel<__bf16>, dim3(p.gather_blocks), dim3(256), 0, st, static_cast<const __bf16*>(x), W,
                            reinterpret_cast<const long long*>(idx), (long)N, C, training, static_cast<__bf16*>(quant), partial);
     else

@@ -102,7 +102,7 @@ int vqseg_vq_prepare_f32(const float* codebook, int c, int k, void* prepared, si
 static int vq_assign_any(const void* x, int x_bf16, const float* codebook, const void* prepared, int64_t n, int c, int k,
                          int64_t* idx, float* dmin, void* ws, size_t ws_bytes, void* stream) {
     if (int rc = check_shape(n, c, k)) return rc;
-    if (x_bf16 && c % 8) return fail(VQSEG_EINVAL, "bf16 rows need channels %% 8 == 0");
+    if (x_bf16 && c % 8) return fail(VQSEG_EINVAL, "%s rows need channels %% 8 == 0", x_bf16 == 2 ? "split-3" : "bf16");
     if (!x || !idx || !ws || (!codebook && !prepared)) return fail(VQSEG_EINVAL, "null pointer argument");
     if (!aligned16(x) || !aligned16(ws) || !aligned16(prepared) || !aligned16(codebook))
         return fail(VQSEG_EINVAL, "x, codebook, prepared and workspace must be 16-byte aligned");
@@ -128,6 +128,11 @@ int vqseg_vq_assign_f32(const float* x, const float* codebook, const void* prepa
 int vqseg_vq_assign_bf16(const void* x, const float* codebook, const void* prepared, int64_t n, int c, int k,
                          int64_t* idx, float* dmin, void* ws, size_t ws_bytes, void* stream) {
     return vq_assign_any(x, 1, codebook, prepared, n, c, k, idx, dmin, ws, ws_bytes, stream);
+}
+
+int vqseg_vq_assign_s3(const void* x, const float* codebook, const void* prepared, int64_t n, int c, int k,
+                       int64_t* idx, float* dmin, void* ws, size_t ws_bytes, void* stream) {
+    return vq_assign_any(x, 2, codebook, prepared, n, c, k, idx, dmin, ws, ws_bytes, stream);
 }
 
 static int vq_forward_any(const void* x, int bf16, const float* codebook, const void* prepared, int64_t n, int c, int k,
@@ -160,6 +165,8 @@ int vqseg_vq_forward_group(int n_levels, int bf16, const void* const* x, const f
                            int64_t* const* idx, float* const* loss, float* const* dead_pct, void* const* ws, const size_t* ws_bytes,
                            void* stream) {
     if (n_levels < 1 || n_levels > vqseg::VQ_MAX_LEVELS) return fail(VQSEG_EINVAL, "1 .. %d levels per grouped launch", vqseg::VQ_MAX_LEVELS);
+    if (bf16 < 0 || bf16 > 2) return fail(VQSEG_EINVAL, "row type must be 0 (f32), 1 (bf16) or 2 (split-3), got %d", bf16);
+    if (bf16 == 2 && training) return fail(VQSEG_EINVAL, "split-3 rows are an eval-mode format: training must be 0");
     if (!x || !codebook || !n || !c || !k || !cw || !quant || !idx || !loss || !dead_pct || !ws || !ws_bytes)
         return fail(VQSEG_EINVAL, "null pointer argument");
     vqseg::VqPlan plans[vqseg::VQ_MAX_LEVELS];
@@ -168,7 +175,7 @@ int vqseg_vq_forward_group(int n_levels, int bf16, const void* const* x, const f
     hipStream_t st = static_cast<hipStream_t>(stream);
     for (int i = 0; i < n_levels; ++i) {
         if (int rc = check_shape(n[i], c[i], k[i])) return rc;
-        if (bf16 && c[i] % 8) return fail(VQSEG_EINVAL, "bf16 rows need channels %% 8 == 0");
+        if (bf16 && c[i] % 8) return fail(VQSEG_EINVAL, "%s rows need channels %% 8 == 0", bf16 == 2 ? "split-3" : "bf16");
         if (!x[i] || !codebook[i] || !quant[i] || !idx[i] || !loss[i] || !dead_pct[i] || !ws[i]) return fail(VQSEG_EINVAL, "null pointer argument");
         if (!aligned16(x[i]) || !aligned16(ws[i]) || !aligned16(codebook[i]) || !aligned16(quant[i]) || (prepared && !aligned16(prepared[i])))
             return fail(VQSEG_EINVAL, "x, codebook, prepared, quant and workspace must be 16-byte aligned");

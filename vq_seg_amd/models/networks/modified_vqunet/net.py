@@ -73,11 +73,18 @@ class _VQRePTUnet1x1Base(nn.Module):
         loss = torch.zeros(1, device=feats[0].device)
         usage = []
         levels = [i for i, vq in enumerate(self.codebook) if not isinstance(vq, _IdentityVQ)]
-        for i in levels:                                     # VQ layers take fp32 rows (Identity levels pass split-3 tensors through)
-            if isinstance(feats[i], nnf.S3):
-                feats[i] = feats[i].float()
-        # the quantised levels are independent: their distance passes share ONE launch when they can (vq_img.quantize_group)
-        grouped = _quantize_group([self.codebook[i] for i in levels], [feats[i] for i in levels]) if nnf.py_opt("py_vq_group", 1) else None
+        vqs = [self.codebook[i] for i in levels]
+        group = nnf.py_opt("py_vq_group", 1)
+        # the quantised levels are independent: their distance passes share ONE launch when they can (vq_img.quantize_group).
+        # Split-3 levels go into it as they are when the group can take them (VQSEG_OPTS=py_vq_s3=0: never) and come back split-3 ...
+        grouped = None
+        if group and nnf.py_opt("py_vq_s3", 1) and any(isinstance(feats[i], nnf.S3) for i in levels):
+            grouped = _quantize_group(vqs, [feats[i] for i in levels])
+        if grouped is None:
+            for i in levels:                                 # ... everything else takes fp32 rows (Identity levels pass split-3 tensors through)
+                if isinstance(feats[i], nnf.S3):
+                    feats[i] = feats[i].float()
+            grouped = _quantize_group(vqs, [feats[i] for i in levels]) if group else None
         grouped = dict(zip(levels, grouped)) if grouped is not None else {}
         for i, vq in enumerate(self.codebook):
             quantize, _idx, commitment, dead = grouped[i] if i in grouped else vq(feats[i])

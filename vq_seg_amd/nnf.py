@@ -656,6 +656,13 @@ def to_s3(x) -> "S3":
     return S3(out, c)
 
 
+def s3_from_rows(rows: torch.Tensor, c: int) -> "S3":
+    """the split-3 tensor a kernel wrote as rows (N, H, W, 2C) bf16 = [hi | lo] (the VQ layers' quantised features)"""
+    if rows.dim() != 4 or rows.dtype != torch.bfloat16 or rows.shape[-1] != 2 * c or not rows.is_contiguous():
+        raise ValueError(f"split-3 rows must be contiguous (N, H, W, {2 * c}) bf16, got {tuple(rows.shape)} {rows.dtype}")
+    return S3(rows, c)
+
+
 def from_s3(x):
     return x.float() if isinstance(x, S3) else x
 

@@ -114,9 +114,16 @@ class _VQGroupFunction(torch.autograd.Function):
 def quantize_group(vqs, feats):
     """[vq(f) for vq, f in zip(vqs, feats)] for VectorQuantizer layers whose codebooks are ready, with their distance passes in
     one launch; None if the layers cannot be grouped (first training forward with k-means pending, the EMA extension, mixed row
-    types, CPU tensors) -- the caller then runs them one by one."""
+    types, CPU tensors) -- the caller then runs them one by one.
+
+    Split-3 features (nnf.S3: the no-grad eval forward in fp32 precision) are taken as they are when every level is one, no layer is
+    in training mode and every shape is one the candidate filter serves: their [hi | lo] rows go straight into the launch (row type 2
+    of vqseg_vq_forward_group) and each quantised feature comes back as an nnf.S3 -- no merge to fp32 in front, no split behind.
+    None otherwise: the caller merges the features (S3.float()) and calls again."""
     if len(vqs) < 2 or len(vqs) > 4:
         return None
+    if any(isinstance(f, nnf.S3) for f in feats):
+        return _quantize_group_s3(vqs, feats)
     rows = []
     for vq, f in zip(vqs, feats):
         cb = vq.codebook
@@ -144,6 +151,27 @@ def quantize_group(vqs, feats):
         b, c, h, w = f.shape
         quant, idx, loss, dead = flat[4 * i:4 * i + 4]
         outs.append((quant.reshape(b, h, w, c).permute(0, 3, 1, 2), idx.reshape(b, h, w), loss, dead))
+    return outs
+
+
+def _quantize_group_s3(vqs, feats):
+    """quantize_group for split-3 features (see there); indices, loss (0) and dead-code share are those of the merged fp32 rows"""
+    if not all(isinstance(f, nnf.S3) for f in feats) or torch.is_grad_enabled():
+        return None
+    L = _hip.lib()
+    for vq, f in zip(vqs, feats):
+        cb = vq.codebook
+        b, c, h, w = f.shape
+        if vq.training or cb.ema_update or not f.rows.is_cuda or c != cb.embedding_dim or \
+                not L.vqseg_vq_filter_counter_offset(b * h * w, c, cb.num_embeddings):      # 0: not a shape of the candidate filter
+            return None
+    rows = [f.rows.reshape(-1, 2 * f.c) for f in feats]
+    res = _hip.vq_forward_group(rows, [vq.codebook.embedding.weight.detach() for vq in vqs], [vq.codebook.prepared() for vq in vqs],
+                                False, [float(vq.commitment_weight) for vq in vqs], s3=True)
+    outs = []
+    for f, (quant, idx, loss, dead) in zip(feats, res):
+        b, c, h, w = f.shape
+        outs.append((nnf.s3_from_rows(quant.reshape(b, h, w, 2 * c), c), idx.reshape(b, h, w), loss, dead))
     return outs
 
 

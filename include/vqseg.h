@@ -756,6 +756,36 @@ int vqseg_resize_argmax_f(const float* const* views_host, const int* flips_host,
                           int64_t stride_px, int b, int c, int h, int w, int ho, int wo, uint8_t* label, float* top,
                           const int64_t* target, int64_t* counts, void* stream);
 
+/* Visualisation: the RGB bytes of a panel sheet for a batch in one pass (vq_seg_amd.nnf.render_sheet, vq_seg_amd.utils.visualize,
+ * Predictor.render).  The full-resolution sheet is rows = b * ho by cols pixels; image i takes rows i * ho .. (i + 1) * ho - 1 of every
+ * panel, panel p the columns x0[p] .. x0[p] + width[p] - 1.  Panel kinds:
+ *     0 IMAGE       the image resized bilinearly (align_corners = 0, the arithmetic of vqseg_bilinear_f) to ho x wo
+ *     1 TARGET      palette row t (the target, brought to ho x wo by ATen's nearest rule), row 2 c (`ignore`) for t outside [0, c)
+ *     2 PRED        palette row pr (the pred byte), row 2 c for pr >= c
+ *     3 DETAIL      palette row pr + c * [pr != t]  (a target outside [0, c) makes the pixel wrong), row 2 c for pr >= c
+ *     4 MIX_PRED    clip(image * (1 - alpha) + colour(PRED) * alpha, 0, 1)       f32: two products, one add
+ *     5 MIX_DETAIL  clip(image * (1 - alpha) + colour(DETAIL) * alpha, 0, 1)
+ *     6 FILL        the fill colour, any width
+ * Every panel but FILL is wo wide.  A byte is floor(clip(x, 0, 1) * 255) in f32, 0 for a NaN; TARGET / PRED / DETAIL / FILL pixels write
+ * the u8 palette rows as given.  box2: the canvas is the sheet halved in both directions, every canvas pixel the f32 mean
+ * ((c00 + c01) + (c10 + c11)) * 0.25 of its 2 x 2 sheet pixels' float colours, quantised after the mean (four pixels of one palette row
+ * write that row's u8 colour); rows and cols must be even.
+ *   image   f32 logical (b, 3, h, w), batch / channel / pixel strides in ELEMENTS as vqseg_resize_argmax_f takes them (planar or
+ *           interleaved, rows dense); pred u8 [b][ho][wo]; target i64 [b][ht][wt]: each may be NULL when no panel needs it
+ *   kinds_host / x0_host / width_host [n_panels]  HOST arrays, 1..8 panels, in any order, disjoint, inside the sheet
+ *   palette_f_host [2 c + 1][3] f32 HOST: c class colours, c "wrong" colours, the ignore colour; palette_u8_host the same rows as
+ *           bytes (floor(colour * 255) taken in float64 by the caller); fill_f_host [3] / fill_u8_host [3] the FILL colour; c in 2..4
+ *   canvas  u8 out, interleaved RGB, pitch bytes per row (>= 3 * canvas columns); rows / cols: the FULL-RESOLUTION sheet (rows = b * ho);
+ *           with box2 the canvas holds rows / 2 by cols / 2 pixels.  Only bytes of panel pixels are written.
+ * Panels and palette travel as kernel arguments: no device allocation, no host-to-device copy, no synchronisation.  A lane takes 4
+ * adjacent canvas pixels (three 4-byte stores when canvas and pitch are 4-byte aligned, byte stores otherwise), a wave 64 consecutive
+ * such groups.  Images up to 2^27 pixels, sheets up to 2^30.  Grid capped by option "nn_grid_cap". */
+int vqseg_render_sheet_u8(const float* image, int64_t stride_b, int64_t stride_c, int64_t stride_px, int h, int w, const uint8_t* pred,
+                          const int64_t* target, int ht, int wt, int b, int ho, int wo, int c, const int* kinds_host, const int* x0_host,
+                          const int* width_host, int n_panels, const float* palette_f_host, const uint8_t* palette_u8_host,
+                          const float* fill_f_host, const uint8_t* fill_u8_host, float alpha, int box2, uint8_t* canvas, int64_t pitch,
+                          int rows, int cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

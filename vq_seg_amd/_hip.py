@@ -145,6 +145,8 @@ SYMBOLS = {
     "vqseg_box_mix_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 3 + [c_void_p, ctypes.c_uint64, c_void_p]),
     "vqseg_affine_warp_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 4 + [c_void_p, ctypes.c_uint64, c_void_p]),
     "vqseg_resize_argmax_f": (c_int, [c_void_p, c_void_p, c_int] + [c_int64] * 3 + [c_int] * 6 + [c_void_p] * 5),
+    "vqseg_render_sheet_u8": (c_int, [c_void_p] + [c_int64] * 3 + [c_int] * 2 + [c_void_p] * 2 + [c_int] * 6 + [c_void_p] * 3 + [c_int] +
+                              [c_void_p] * 4 + [c_float, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -672,6 +674,77 @@ def affine_warp(src: torch.Tensor, matrices, mode: str = "bilinear", fill=0, out
            *inner, mats.ctypes.data, bits)
     AFFINE_WARP_CALLS += 1
     return out
+
+
+RENDER_KINDS = {"image": 0, "target": 1, "pred": 2, "detail": 3, "mix_pred": 4, "mix_detail": 5, "fill": 6}     # include/vqseg.h: vqseg_render_sheet_u8
+RENDER_SHEET_CALLS = 0        # calls of render_sheet that reached the library (as BOX_MIX_CALLS: for tests, never read by the product)
+
+
+def render_sheet(canvas: torch.Tensor, panels, size, num_classes: int, palette, fill=(1.0, 1.0, 1.0), image: Optional[torch.Tensor] = None,
+                 pred: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, alpha: float = 0.4, box2: bool = False,
+                 cols: Optional[int] = None) -> torch.Tensor:
+    """The RGB bytes of a panel sheet (include/vqseg.h: vqseg_render_sheet_u8) written into `canvas`, a (rows, cols, 3) uint8 tensor
+    whose pixels are dense (strides (pitch, 3, 1): a view of a larger canvas qualifies) -- the full-resolution sheet of b * ho rows, or
+    with `box2` its half in both directions.  `panels`: (kind, x0, width) rows, kind a key of RENDER_KINDS, x0 / width in full-resolution
+    columns; `size` = (b, ho, wo); `palette`: (2 C + 1, 3) floats in [0, 1] (C class colours, C "wrong" colours, the ignore colour),
+    taken in float64 for the byte rows; `image` (b, 3, h, w) f32 NCHW-contiguous or channels_last, `pred` (b, ho, wo) u8, `target`
+    (b, ht, wt) i64: each only where a panel needs it.  `cols`: the full-resolution sheet's width (default: the canvas's, doubled with
+    box2).  Returns `canvas`; bytes outside the panels keep their value.  There is no CPU path."""
+    global RENDER_SHEET_CALLS
+    E = HipLibraryError
+    b, ho, wo = (int(v) for v in size)
+    c = int(num_classes)
+    rows = b * ho
+    if not isinstance(canvas, torch.Tensor) or canvas.dim() != 3 or canvas.shape[2] != 3:
+        raise E("render_sheet: canvas must be a (rows, cols, 3) uint8 tensor")
+    orows, ocols = int(canvas.shape[0]), int(canvas.shape[1])
+    cols = ocols * (2 if box2 else 1) if cols is None else int(cols)
+    if box2 and (rows % 2 or cols % 2):
+        raise E(f"render_sheet: box2 needs a sheet of even height and width, got {rows} x {cols}")
+    if (orows, ocols) != ((rows // 2, cols // 2) if box2 else (rows, cols)):
+        raise E(f"render_sheet: a {rows} x {cols} sheet{' halved by box2' if box2 else ''} needs a canvas of "
+                f"{(rows // 2, cols // 2) if box2 else (rows, cols)} pixels, got {(orows, ocols)}")
+    if orows == 0 or ocols == 0:
+        raise E("render_sheet: empty canvas")
+    if canvas.stride(2) != 1 or (ocols > 1 and canvas.stride(1) != 3) or (orows > 1 and canvas.stride(0) < 3 * ocols):
+        raise E(f"render_sheet: canvas pixels must be dense RGB bytes with rows at least a row apart, got strides {tuple(canvas.stride())}")
+    pitch = canvas.stride(0) if orows > 1 else 3 * ocols
+    rows_ = [(RENDER_KINDS.get(k, -1) if isinstance(k, str) else int(k), int(x), int(wd)) for k, x, wd in panels]
+    if any(k < 0 for k, _, _ in rows_):
+        raise E(f"render_sheet: panel kinds are {sorted(RENDER_KINDS)}, got {[p[0] for p in panels]}")
+    pal = np.ascontiguousarray(palette, dtype=np.float64)
+    if pal.shape != (2 * c + 1, 3):
+        raise E(f"render_sheet: the palette of {c} classes has {2 * c + 1} rows of 3 (class, wrong, ignore), got shape {pal.shape}")
+    fil = np.ascontiguousarray(fill, dtype=np.float64).reshape(-1)
+    if fil.shape != (3,):
+        raise E("render_sheet: fill is one RGB colour")
+    pal_f, fil_f = pal.astype(np.float32), fil.astype(np.float32)
+    pal_u, fil_u = (np.floor(np.clip(a, 0.0, 1.0) * 255.0).astype(np.uint8) for a in (pal, fil))      # float64: float32(230 / 255) * 255 < 230
+    ip = pp = tp = None
+    strides, (h, w), (ht, wt) = (0, 0, 0), (0, 0), (0, 0)
+    if image is not None:
+        if not isinstance(image, torch.Tensor) or image.dim() != 4 or image.shape[0] != b or image.shape[1] != 3:
+            raise E(f"render_sheet: image must be a ({b}, 3, h, w) tensor")
+        h, w = int(image.shape[2]), int(image.shape[3])
+        ip = tptr(image, "image", dtype=torch.float32, numel=b * 3 * h * w)
+        # tptr admits two dense layouts; the strides are stated from the layout (a size-1 dimension's own stride is arbitrary)
+        strides = (3 * h * w, h * w, 1) if image.is_contiguous() else (3 * h * w, 1, 3)
+    if pred is not None:
+        if not isinstance(pred, torch.Tensor) or tuple(pred.shape) != (b, ho, wo):
+            raise E(f"render_sheet: pred must have the shape {(b, ho, wo)}, got {tuple(getattr(pred, 'shape', ()))}")
+        pp = tptr(pred, "pred", dtype=torch.uint8, numel=b * ho * wo)
+    if target is not None:
+        if not isinstance(target, torch.Tensor) or target.dim() != 3 or target.shape[0] != b:
+            raise E(f"render_sheet: target must be a ({b}, ht, wt) tensor")
+        ht, wt = int(target.shape[1]), int(target.shape[2])
+        tp = tptr(target, "target", dtype=torch.int64, numel=b * ht * wt)
+    cp = tptr(canvas, "canvas", dtype=torch.uint8, numel=orows * ocols * 3, dense=False)
+    arr = np.ascontiguousarray(rows_, dtype=np.int32).reshape(-1, 3).T.copy()           # kinds, x0s, widths
+    launch("vqseg_render_sheet_u8", canvas.device, ip, *strides, h, w, pp, tp, ht, wt, b, ho, wo, c, arr[0].ctypes.data, arr[1].ctypes.data,
+           arr[2].ctypes.data, len(rows_), pal_f.ctypes.data, pal_u.ctypes.data, fil_f.ctypes.data, fil_u.ctypes.data, float(alpha), int(bool(box2)),
+           cp, pitch, rows, cols)
+    RENDER_SHEET_CALLS += 1
+    return canvas
 
 
 def _checked(name: str, *args, counts: bool = False) -> int:

@@ -1,5 +1,5 @@
 // The two device functions every bilinear resize of the library goes through (nn_spatial.hip: the generic and the exact-2x kernels and
-// their split-3 instantiations; predict_kernels.hip: the fused resize + arg-max), in ONE copy: the kernels that share them round
+// their split-3 instantiations; predict_kernels.hip: the fused resize + arg-max; render_kernels.hip: the sheet's image panels), in ONE copy: the kernels that share them round
 // identically by construction.  ATen upsample_bilinear2d semantics:
 //   align_corners: src = dst * (in-1)/(out-1);  else src = max((dst+0.5)*in/out - 0.5, 0)
 #pragma once

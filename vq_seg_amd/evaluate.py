@@ -9,6 +9,13 @@ over the batches.  Only the (N, C, C) confusion counts and the per-image hit cou
 mask size are never written; the per-image accuracy is then trace(counts) / (Hm * Wm) -- the same number as the mean of the
 0 / 1 hits (an out-of-range target never equals a class, and a mean of 0 / 1 doubles is a ratio of integers), and the returned
 dict equals the unfused one.  `tta` (with fused: "hflip", "vflip", "hvflip" beside "none") scores the mean over flipped views.
+
+`visualize` (with fused) is a callable `(batch_index, viz_v1, viz_v2)` that receives, per batch, the two sheets test_detailviz.py:124-129
+builds -- viz_v1 = [input | target | detailed prediction], viz_v2 = 0.6 input + 0.4 detailed prediction, at half the mask size, the
+batch stacked vertically -- as uint8 numpy arrays: a second `nnf.resize_argmax` call at the display size and one render launch
+(utils.visualize.render_sheet), after which only the sheet's bytes cross to the host.  The labels shown are the arg-max of the
+network's logits resized directly to the display size (the reference resizes them to the mask size first, then again).  With None
+nothing changes: no extra launch, the same dict.
 """
 from typing import Dict, Iterable, Tuple
 
@@ -38,12 +45,23 @@ def _resized_counts(model, img, target, num_classes, amp_dtype):
     return conf, hits
 
 
+def _detail_sheets(img, logits, flips, target, num_classes):
+    """(viz_v1, viz_v2) of test_detailviz.py:124-129 for one batch, uint8 numpy: everything at half the mask size"""
+    from .utils.visualize import default_palette, render_sheet
+    size = (target.shape[-2] // 2, target.shape[-1] // 2)
+    sheet = render_sheet(["image", "target", "detail", "mix_detail"], img, logits, target, size=size, palette=default_palette(num_classes),
+                         flips=flips).cpu().numpy()
+    return np.ascontiguousarray(sheet[:, :3 * size[1]]), np.ascontiguousarray(sheet[:, 3 * size[1]:])
+
+
 @torch.no_grad()
 def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], num_classes: int,
-              device=None, amp_dtype=None, fused: bool = False, tta=None) -> Dict[str, object]:
+              device=None, amp_dtype=None, fused: bool = False, tta=None, visualize=None) -> Dict[str, object]:
     """batches yields (images (N, 3, H, W) float in [0, 1], labels (N, Hm, Wm) int class ids)."""
     if tta is not None and not fused:
         raise ValueError("test_loop: tta needs fused=True (the views are averaged inside the fused resize + arg-max)")
+    if visualize is not None and not fused:
+        raise ValueError("test_loop: visualize needs fused=True (the sheets are drawn from the fused path's views)")
     views = Predictor(model, num_classes, amp_dtype=amp_dtype, tta=tta or ("none",)).views if fused else None
     was_training = model.training
     model.eval()
@@ -58,6 +76,8 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
             logits, flips = views(img)
             conf = nnf.resize_argmax(logits, tuple(target.shape[-2:]), flips=flips, target=target)[2]
             hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (target.shape[-2] * target.shape[-1])
+            if visualize is not None:
+                visualize(n_batches, *_detail_sheets(img, logits, flips, target, num_classes))
         else:
             conf, hits = _resized_counts(model, img, target, num_classes, amp_dtype)
         conf_np = conf.cpu().numpy()

@@ -1844,3 +1844,68 @@ def resize_argmax(logits, size, flips=None, want_top=False, target=None):
     RESIZE_ARGMAX_CALLS += 1
     return label, top, counts
 
+
+
+# ------------------------------------------------------------------------------------------------
+# visualisation: labels, targets and the input image -> the RGB bytes of a panel sheet in one pass
+# ------------------------------------------------------------------------------------------------
+def sheet_layout(panels, wo):
+    """-> ([(kind, x0, width)], sheet width) of panels laid out left to right: a panel is a kind name of _hip.RENDER_KINDS (`wo` wide) or
+    ("fill", width)"""
+    rows, x = [], 0
+    for p in panels:
+        kind, width = (p, None) if isinstance(p, str) else (p[0], p[1] if len(p) > 1 else None)
+        if kind not in _hip.RENDER_KINDS:
+            raise _hip.HipLibraryError(f"render_sheet: panel kinds are {sorted(_hip.RENDER_KINDS)}, got {kind!r}")
+        if kind == "fill":
+            if width is None or int(width) < 1:
+                raise _hip.HipLibraryError("render_sheet: a fill panel is ('fill', width) with a positive width")
+            width = int(width)
+        elif width is not None and int(width) != wo:
+            raise _hip.HipLibraryError(f"render_sheet: every panel but 'fill' is as wide as the display size ({wo}), got {width}")
+        else:
+            width = wo
+        rows.append((kind, x, width))
+        x += width
+    if not rows:
+        raise _hip.HipLibraryError("render_sheet: no panels")
+    return rows, x
+
+
+def render_sheet(panels, size, num_classes, palette, image=None, pred=None, target=None, fill=(1.0, 1.0, 1.0), alpha=0.4, half=False,
+                 out=None):
+    """The panel sheet of a batch as uint8 RGB, (B * Ho, sheet width, 3) -- with `half` (B * Ho / 2, sheet width / 2, 3), every pixel
+    the mean of a 2 x 2 block of the full sheet -- in one HIP pass (vqseg_render_sheet_u8).  `panels`, left to right: "image" (the
+    input resized bilinearly, align_corners=False, to `size` = (Ho, Wo)), "target", "pred", "detail" (a wrong pixel takes the
+    palette's second block), "mix_pred" / "mix_detail" (clip((1 - alpha) image + alpha colour, 0, 1)), ("fill", width).  `pred`:
+    (B, Ho, Wo) uint8 labels as resize_argmax writes them; `target`: (B, Ht, Wt) integer labels at any size (nearest neighbour);
+    `image`: (B, 3, h, w) fp32.  `palette`: (2 C + 1, 3) floats.  `out`: a (rows, cols, 3) uint8 tensor to write into, which may be a
+    view of a larger canvas (dense pixels, any row pitch); bytes outside the panels are not touched.  Image i takes the rows
+    i Ho .. (i + 1) Ho - 1 of every panel.  Tensors must be on the GPU."""
+    E = _hip.HipLibraryError
+    ho, wo = int(size[0]), int(size[1])
+    rows, cols = sheet_layout(panels, wo)
+    src = next((t for t in (pred, image, target, out) if torch.is_tensor(t)), None)
+    if src is None:
+        raise E("render_sheet: at least one of image, pred, target or out must be a tensor (it names the batch and the device)")
+    b = int(pred.shape[0] if torch.is_tensor(pred) else image.shape[0] if torch.is_tensor(image) else target.shape[0] if torch.is_tensor(target)
+            else (out.shape[0] * (2 if half else 1)) // ho)
+    if half and ((b * ho) % 2 or cols % 2):
+        raise E(f"render_sheet: half needs a sheet of even height and width, got {b * ho} x {cols}")
+    shape = (b * ho // 2, cols // 2, 3) if half else (b * ho, cols, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    elif not torch.is_tensor(out) or tuple(out.shape) != shape:
+        raise E(f"render_sheet: out must have the shape {shape}, got {tuple(getattr(out, 'shape', ()))}")
+    if torch.is_tensor(image):
+        image = image.detach()
+        if image.dtype == torch.float32 and image.dim() == 4 and not image.is_contiguous() and not image.is_contiguous(memory_format=torch.channels_last):
+            image = image.contiguous()
+    if target is not None:
+        if not torch.is_tensor(target) or target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+            raise E(f"render_sheet: target must be an integer tensor, got {getattr(target, 'dtype', type(target).__name__)}")
+        target = target.detach().long().contiguous()
+    if pred is not None and torch.is_tensor(pred):
+        pred = pred.detach().contiguous()
+    return _hip.render_sheet(out, rows, (b, ho, wo), num_classes, palette, fill=fill, image=image, pred=pred, target=target, alpha=alpha,
+                             box2=half, cols=cols)

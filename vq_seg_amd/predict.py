@@ -80,6 +80,30 @@ class Predictor:
                 m.train(was_training)
         return Prediction(label, top)
 
+    @torch.no_grad()
+    def render(self, images: torch.Tensor, targets: Optional[torch.Tensor] = None, size: Optional[Sequence[int]] = None, panels=None,
+               half: bool = False, palette=None, alpha: float = 0.4) -> torch.Tensor:
+        """images (N, 3, H, W) -> the panel sheet of their prediction, a uint8 (N * Ho, cols, 3) tensor (halved with `half`) on the
+        images' device: the views of __call__ (ensemble and test-time views averaged inside nnf.resize_argmax), then one render
+        launch (utils.visualize.render_sheet; vqseg_render_sheet_u8 on the GPU) from the labels, `targets` (N, Ht, Wt) at any size
+        and the images themselves.  `panels` default: image | target | pred | 20 px white | mix_pred (without `targets`: no target
+        panel); size None: (H, W)."""
+        from .utils.visualize import GAP, render_sheet
+        size = tuple(images.shape[-2:]) if size is None else (int(size[0]), int(size[1]))
+        if panels is None:
+            panels = ["image"] + (["target"] if targets is not None else []) + ["pred", ("fill", GAP), "mix_pred"]
+        modes = [m.training for m in self.models]
+        for m in self.models:
+            m.eval()
+        try:
+            logits, flips = self.views(images)
+        finally:
+            for m, was_training in zip(self.models, modes):
+                m.train(was_training)
+        dev = logits[0].device
+        return render_sheet(panels, images.to(dev), logits, None if targets is None else targets.to(dev), size=size, palette=palette, alpha=alpha,
+                            half=half, flips=flips)
+
     def predict_batches(self, batches: Iterable, size: Optional[Sequence[int]] = None, want_confidence: bool = False) -> Iterator[Prediction]:
         """one Prediction per batch; a batch is the images or a tuple / list whose first entry they are ((images, labels), ...)"""
         for batch in batches:

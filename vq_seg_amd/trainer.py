@@ -30,6 +30,7 @@ from .measurement import confusion_matrix_device, miou_device
 from . import nnf
 from .averaging import AveragedNetwork
 from .evaluate import test_loop
+from .utils.visualize import default_palette
 from .models import init_weight
 from .models.networks import make_model
 from .optim import HipAdam
@@ -551,12 +552,34 @@ class CPSTrainer:
             raise ValueError("which='teacher' needs a teacher: set CPSConfig.ema_decay")
         return self.teachers if which == "teacher" else self.models
 
-    def evaluate(self, batches, which: str = "student", index: int = 0, fused: bool = False):
+    def evaluate(self, batches, which: str = "student", index: int = 0, fused: bool = False, visualize=None):
         """evaluate.test_loop on network `index` of the pair: which="student" scores the trained weights, which="teacher" their
         exponential moving average (cfg.ema_decay), under cfg.amp_dtype.  `batches` yields (images, labels).  `fused`: resize, arg-max
-        and confusion counts in one kernel (evaluate.test_loop's opt-in; the same numbers)."""
+        and confusion counts in one kernel (evaluate.test_loop's opt-in; the same numbers).  `visualize` (with fused): a callable
+        (batch_index, viz_v1, viz_v2) that receives the test script's two uint8 sheets per batch (evaluate.test_loop)."""
         model = self._networks(which)[index]
-        return test_loop(model, batches, self.cfg.num_classes, device=self.device, amp_dtype=self.cfg.amp_dtype, fused=fused)
+        return test_loop(model, batches, self.cfg.num_classes, device=self.device, amp_dtype=self.cfg.amp_dtype, fused=fused, visualize=visualize)
+
+    @torch.no_grad()
+    def example_image(self, l_input, l_target, ul_input, which: str = "student", index: int = 0, half: bool = True):
+        """The trainer's end-of-epoch sheet (train_vqreptunet1x1v2.py:239-244): [input | target | prediction | 20 px white |
+        0.6 unlabelled input + 0.4 its prediction], the batch stacked vertically, as a uint8 (B * H [/ 2], (4 W + 20) [/ 2], 3) numpy
+        array (utils.visualize.make_example_img; `half`: its resize_factor = 0.5).  The predictions are no-grad eval-mode forwards
+        of network `index` of the pair `which` names, under cfg.amp_dtype; the reference feeds the TRAIN-mode predictions of the
+        epoch's last step, which this trainer does not keep.  Every network's mode is restored on the way out."""
+        from .utils.visualize import make_example_img
+        model = self._networks(which)[index]
+        p = Predictor(model, self.cfg.num_classes, amp_dtype=self.cfg.amp_dtype, device=self.device)
+        was_training = model.training
+        model.eval()
+        try:
+            (sup,), _ = p.views(l_input)
+            (unsup,), _ = p.views(ul_input)
+        finally:
+            model.train(was_training)
+        dev = sup.device
+        return make_example_img(l_input.to(dev), l_target.to(dev), sup, ul_input.to(dev), unsup, colormap=default_palette(self.cfg.num_classes),
+                                resize_factor=0.5 if half else None)
 
     def predict(self, images, size=None, which: str = "student", index: int = 0, ensemble: bool = False, tta=("none",),
                 want_confidence: bool = False) -> Prediction:

@@ -786,6 +786,33 @@ int vqseg_render_sheet_u8(const float* image, int64_t stride_b, int64_t stride_c
                           const float* fill_f_host, const uint8_t* fill_u8_host, float alpha, int box2, uint8_t* canvas, int64_t pitch,
                           int rows, int cols, void* stream);
 
+/* ---------------------------------------------------------------------------------- *
+ * Pixel-pair supervised contrastive loss (loss/contrastive_loss.py:9-30; vq_seg_amd.nnf.supcon, vq_seg_amd.loss.SupConLoss) of the
+ * feature rows f1, f2 ([h * w][c], f32 or bf16 by the `bf16` flag, row_stride elements apart: images 0 and 1 of a channels_last
+ * tensor) and their int64 targets gt1, gt2 ([ht][wt] each; larger than the feature map: read through ATen's `nearest` rule):
+ *     z_ij = (f1_i . f2_j) / T,  pos_ij = (gt1_i == gt2_j)  -- the target VALUES are compared, 255 is a class like any other --
+ *     logA = log sum_ij exp z_ij,  logP = log sum_pos exp z_ij,  loss = (logA - logP) / (hw * hw)
+ * The (hw, hw) matrix is never written: an MFMA product over all row pairs (v_mfma_f32_32x32x2_f32 for f32 rows, v_mfma_f32_32x32x16_bf16
+ * for bf16 rows) reduced on the fly with a running maximum and a rescaled sum per row -- one pair over all columns, one over the positives --, so the value is finite at every finite input
+ * (the reference's exp overflows at z > 88) and equal to the reference's wherever that is finite.  No atomics: per-row partials of
+ * every column split go to the workspace and ONE workgroup merges them in a fixed order in double; two calls agree bit for bit.
+ *   forward : out[0] = loss (+inf when there is no positive pair, as the reference), out[1] = logA, out[2] = logP, out[3..7] = what the
+ *             backward reads (the base-2 logs as hi + lo floats, and whether a positive pair exists); out: 8 floats, DEVICE.
+ *   backward: dz_ij = g / (hw * hw) * (exp(z_ij - logA) - pos_ij exp(z_ij - logP)),  d_f1 = dz f2 / T,  d_f2 = dz^T f1 / T, with
+ *             g = g_scalar[0] read on the DEVICE (under a gradient scaler it holds the scale); `stats` is the forward's `out`.  The
+ *             z tile is recomputed; one kernel, launched twice with the roles of the images swapped, accumulates the gradient of
+ *             the rows it owns over all columns.  Gradients leave in the rows' type, grad_row_stride elements apart.  No positive
+ *             pair: the positive term is absent and the gradient finite (the reference: NaN).
+ * c: a multiple of 16 up to 128; h * w <= 2^30; rows 16-byte aligned.  workspace: vqseg_supcon_workspace_bytes(h * w).
+ * ---------------------------------------------------------------------------------- */
+size_t vqseg_supcon_workspace_bytes(int64_t hw);
+int vqseg_supcon_forward_f(int bf16, const void* f1, const void* f2, int64_t row_stride, int h, int w, int c, const int64_t* gt1,
+                           const int64_t* gt2, int ht, int wt, float temperature, void* workspace, size_t workspace_bytes, float* out,
+                           void* stream);
+int vqseg_supcon_backward_f(int bf16, const void* f1, const void* f2, int64_t row_stride, int h, int w, int c, const int64_t* gt1,
+                            const int64_t* gt2, int ht, int wt, float temperature, const float* stats, const float* g_scalar, void* d_f1,
+                            void* d_f2, int64_t grad_row_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,11 @@ SYMBOLS = {
     "vqseg_resize_argmax_f": (c_int, [c_void_p, c_void_p, c_int] + [c_int64] * 3 + [c_int] * 6 + [c_void_p] * 5),
     "vqseg_render_sheet_u8": (c_int, [c_void_p] + [c_int64] * 3 + [c_int] * 2 + [c_void_p] * 2 + [c_int] * 6 + [c_void_p] * 3 + [c_int] +
                               [c_void_p] * 4 + [c_float, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "vqseg_supcon_workspace_bytes": (c_size_t, [c_int64]),
+    "vqseg_supcon_forward_f": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float,
+                                       c_void_p, c_size_t, c_void_p, c_void_p]),
+    "vqseg_supcon_backward_f": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -29,4 +29,12 @@ __device__ __forceinline__ void bil_src(int d, int in, int out, int align, int& 
     l1 = s - (float)i0;
 }
 
+// ATen upsample_nearest ('nearest', not 'nearest-exact'): the source index of destination index d when `in` samples are read at `out`
+// positions -- min((int)(d * ((float)in / out)), in - 1).  The one copy: the sheet's target panels (render_kernels.hip) and the contrastive
+// loss's labels (supcon_kernels.hip) read a larger int64 target through it.
+__device__ __forceinline__ int nearest_src(int d, int in, int out) {
+    const int s = (int)((float)d * ((float)in / (float)out));
+    return s < in - 1 ? s : in - 1;
+}
+
 }  // namespace vqseg

@@ -101,8 +101,7 @@ __device__ __forceinline__ SheetPixel sheet_pixel(const RenderArgs& a, const flo
         long long t = -1;
         if (want_pred) pr = a.pred[((long)b * a.Ho + yy) * a.Wo + xx];
         if (want_tgt) {
-            int ty = (int)((float)yy * ((float)a.Ht / (float)a.Ho)), tx = (int)((float)xx * ((float)a.Wt / (float)a.Wo));
-            ty = ty < a.Ht - 1 ? ty : a.Ht - 1, tx = tx < a.Wt - 1 ? tx : a.Wt - 1;
+            const int ty = nearest_src((int)yy, a.Ht, a.Ho), tx = nearest_src((int)xx, a.Wt, a.Wo);
             t = a.target[((long)b * a.Ht + ty) * a.Wt + tx];
         }
         if (kind == RS_TARGET) row = t >= 0 && t < C ? (int)t : 2 * C;

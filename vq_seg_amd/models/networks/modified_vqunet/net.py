@@ -101,6 +101,17 @@ class _VQRePTUnet1x1Base(nn.Module):
             nnf.fanin_tag(decoder_out)
         return decoder_out, self.segmentation_head(decoder_out)
 
+    def _side_terms(self, decoder_out, gt, side):
+        """`side`: a dict the CALLER of finish() supplies and owns (trainer.CPSTrainer; nothing is kept on the module).  In training mode
+        the callable under "sup_con" (loss.SupConLoss) is evaluated on this forward's decoder output and targets -- here, on this network's
+        stream and under its autocast -- and its scalar left under "sup_con_loss"; with "keep", the decoder output under "decoder_out"."""
+        if side is None or not self.training:
+            return
+        if side.get("sup_con") is not None:
+            side["sup_con_loss"] = side["sup_con"](decoder_out, gt)
+        if side.get("keep"):
+            side["decoder_out"] = decoder_out.detach()
+
     def _trunk(self, x):
         feats, loss, usage = self.quantize(self.encode(x))
         decoder_out, logits = self.decode(feats)
@@ -138,8 +149,9 @@ class VQRePTUnet1x1(_VQRePTUnet1x1Base):
     def forward(self, x, gt=None, code_usage_loss=False, percent=None):
         return self.finish(*self.quantize(self.encode(x)), gt=gt, code_usage_loss=code_usage_loss, percent=percent)
 
-    def finish(self, feats, loss, usage, gt=None, code_usage_loss=False, percent=None):
+    def finish(self, feats, loss, usage, gt=None, code_usage_loss=False, percent=None, side=None):
         decoder_out, output = self.decode(feats)
+        self._side_terms(decoder_out, gt, side)
         prototype_loss = None
         if self.training:
             with torch.no_grad():
@@ -161,8 +173,9 @@ class VQRePTUnet1x1v2(_VQRePTUnet1x1Base):
     def forward(self, x, gt=None, code_usage_loss=False, th=None):
         return self.finish(*self.quantize(self.encode(x)), gt=gt, code_usage_loss=code_usage_loss, th=th)
 
-    def finish(self, feats, loss, usage, gt=None, code_usage_loss=False, th=None):
+    def finish(self, feats, loss, usage, gt=None, code_usage_loss=False, th=None, side=None):
         decoder_out, output = self.decode(feats)
+        self._side_terms(decoder_out, gt, side)
         prototype_loss = self.prototype_loss(decoder_out, gt, th) if self.training else None
         output = self.upsampling(output)
         if code_usage_loss:

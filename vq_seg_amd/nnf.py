@@ -1569,6 +1569,90 @@ def class_weight(num_classes: int, y):
     return weight, counts
 
 
+# ------------------------------------------------------------------------------------------------
+# Pixel-pair supervised contrastive loss (loss/contrastive_loss.py): fused forward / backward over all pixel pairs of images 0 and 1
+# (vqseg_supcon_*), no (HW, HW) matrix
+# ------------------------------------------------------------------------------------------------
+def _supcon_targets(x, target):
+    """the (B, Ht, Wt) int64 targets of a (B, C, H, W) feature tensor, or a HipLibraryError saying what is wrong"""
+    if not torch.is_tensor(target) or target.dim() not in (3, 4) or (target.dim() == 4 and target.shape[1] != 1):
+        raise _hip.HipLibraryError(f"supcon: targets must be a (B, Ht, Wt) or (B, 1, Ht, Wt) tensor, got {tuple(getattr(target, 'shape', ()))}")
+    if target.is_floating_point() or target.dtype == torch.bool:
+        raise _hip.HipLibraryError(f"supcon: targets must be integer class labels, got {target.dtype}")
+    if target.shape[0] < 2 or target.shape[0] != x.shape[0]:
+        raise _hip.HipLibraryError(f"supcon: one target per image of the batch of {x.shape[0]} (at least 2) required, got {target.shape[0]}")
+    tgt = target.reshape(target.shape[0], target.shape[-2], target.shape[-1])
+    return tgt if tgt.dtype == torch.int64 and tgt.is_contiguous() else tgt.long().contiguous()
+
+
+def _supcon_forward(x, target, temperature):
+    """-> the feature rows (B, H, W, C), the (B, Ht, Wt) int64 targets and the forward's 8-float result block (include/vqseg.h)"""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[0] < 2:
+        raise _hip.HipLibraryError(f"supcon: features must be a (B >= 2, C, H, W) tensor, got {tuple(getattr(x, 'shape', ()))}")
+    xr = _rows(x.detach())
+    bf = _is_bf16(xr)
+    b, h, w, c = xr.shape
+    if c % 16 or not 16 <= c <= 128:
+        raise _hip.HipLibraryError(f"supcon: channels must be a multiple of 16 up to 128, got {c}")
+    tgt = _supcon_targets(x, target)
+    ht, wt = tgt.shape[1:]
+    hw, dev = h * w, xr.device
+    nbytes = lib().vqseg_supcon_workspace_bytes(hw)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    _launch("vqseg_supcon_forward_f", dev, bf, _T(xr[0], "features of image 0", bf=bf, numel=hw * c), _T(xr[1], "features of image 1", bf=bf, numel=hw * c),
+            c, h, w, c, _T(tgt[0], "targets of image 0", dtype=torch.int64, numel=ht * wt), _T(tgt[1], "targets of image 1", dtype=torch.int64, numel=ht * wt),
+            ht, wt, float(temperature), _T(ws, "workspace", dtype=torch.uint8, numel=nbytes), nbytes, _f32(out, "loss", 8))
+    return xr, tgt, out
+
+
+class _SupCon(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, target, temperature):
+        xr, tgt, out = _supcon_forward(x, target, temperature)
+        ctx.save_for_backward(xr, tgt, out)
+        ctx.temperature = float(temperature)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_out):
+        xr, tgt, out = ctx.saved_tensors
+        b, h, w, c = xr.shape
+        ht, wt = tgt.shape[1:]
+        hw, bf = h * w, _is_bf16(xr)
+        g32 = g_out.detach().float().reshape(1).contiguous()   # stays on the device: under a gradient scaler it holds the scale
+        gx = torch.empty_like(xr)
+        gx[2:].zero_()                                         # only images 0 and 1 enter the loss
+        _launch("vqseg_supcon_backward_f", xr.device, bf, _T(xr[0], "features of image 0", bf=bf, numel=hw * c),
+                _T(xr[1], "features of image 1", bf=bf, numel=hw * c), c, h, w, c, _T(tgt[0], "targets of image 0", dtype=torch.int64, numel=ht * wt),
+                _T(tgt[1], "targets of image 1", dtype=torch.int64, numel=ht * wt), ht, wt, ctx.temperature, _f32(out, "forward statistics", 8),
+                _f32(g32, "loss gradient", 1), _T(gx[0], "feature gradient of image 0", bf=bf, numel=hw * c),
+                _T(gx[1], "feature gradient of image 1", bf=bf, numel=hw * c), c)
+        return _nchw(gx), None, None
+
+
+def supcon_supported(x, target) -> bool:
+    """what the fused contrastive pass takes: (B >= 2, C, H, W) float32 / bfloat16 GPU features with C a multiple of 16 up to 128 and
+    integer (B, Ht, Wt) or (B, 1, Ht, Wt) targets on the same device; everything else is SupConLoss's torch-op form"""
+    return (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.shape[0] >= 2 and x.dtype in (torch.float32, torch.bfloat16)
+            and x.shape[1] % 16 == 0 and 16 <= x.shape[1] <= 128 and x.shape[2] * x.shape[3] >= 1
+            and torch.is_tensor(target) and target.device == x.device and not target.is_floating_point() and target.dtype != torch.bool
+            and (target.dim() == 3 or (target.dim() == 4 and target.shape[1] == 1)) and target.shape[0] == x.shape[0])
+
+
+def supcon(x, target, temperature=0.04):
+    """SupConLoss.forward (loss/contrastive_loss.py:13-30) of (B, C, H, W) features and their integer targets: a 0-d float32 tensor,
+    (logA - logP) / (HW * HW) over all pixel pairs of images 0 and 1, finite wherever the inputs are and a positive pair exists.  The
+    gradient with respect to x is zero outside images 0 and 1 and returns to autograd in the ordinary way (no fan-in deposit).  The
+    value's companions logA and logP are `supcon_stats`'s."""
+    return _SupCon.apply(x, target, temperature)
+
+
+def supcon_stats(x, target, temperature=0.04):
+    """(loss, logA, logP) as a float32 device tensor, no gradient (tests, profiles)"""
+    return _supcon_forward(x, target, temperature)[2][:3]
+
+
 class _ConvBias(torch.autograd.Function):
     """k x k / stride 1 convolution WITH bias and a handful of output channels, fp32 (the plain Unet's segmentation head: 32 -> 3,
     segmentation_head.py:78-83) on the precise-mode kernels: output channels zero-padded to the kernels' 4-channel granule, the bias in

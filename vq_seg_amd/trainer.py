@@ -26,6 +26,7 @@ from .lanes import OFF, Lanes
 from .loss import compute_class_weight, cross_entropy, make_loss
 from .loss.dice_loss import DiceLoss, ce_dice_loss, dice_loss
 from .loss.focal_loss import FocalLoss
+from .loss.contrastive_loss import SupConLoss
 from .measurement import confusion_matrix_device, miou_device
 from . import nnf
 from .averaging import AveragedNetwork
@@ -88,6 +89,11 @@ class CPSConfig:
     easy_aug_per: str = "batch"               # "batch": one transform per step for all samples (the reference); "sample": one per image
     easy_aug_max_angle: float = 90.0          # rotation angles are drawn of [0, max) degrees (the reference: 90)
     easy_aug_codes: Sequence[int] = tuple(range(10))      # the transform codes drawn from (0 / 9 identity, 1 / 2 flips, 3-8 rotations without / with a flip)
+    sup_con_loss_weight: Optional[float] = None   # pixel-pair supervised contrastive term (deprecated/train_supcon_unet.py:116-153, config/sup_con_loss.json: 0.5):
+                                              # each network's LABELLED training forward evaluates loss.SupConLoss on its decoder output and l_target, on its
+                                              # own stream, and weight * (l_1 + l_2) joins the total (reported as `sup_con_loss`).  Needs more than 2 labelled
+                                              # images.  None = today's step: nothing of it is entered, launches and tensors are the same
+    sup_con_temperature: float = 0.04         # SupConLoss(temperature)
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -104,6 +110,8 @@ class CPSConfig:
             raise ValueError(f"easy_aug_codes must be a non-empty selection of 0..9, got {self.easy_aug_codes!r}")
         if not 0.0 <= float(self.easy_aug_max_angle) <= 180.0:
             raise ValueError(f"easy_aug_max_angle must lie in [0, 180], got {self.easy_aug_max_angle!r}")
+        if self.sup_con_loss_weight is not None and not float(self.sup_con_temperature) > 0.0:
+            raise ValueError(f"sup_con_temperature must be positive, got {self.sup_con_temperature!r}")
         if self.recipe != "v1" and (self.criterion != "dice_loss" or self.class_weight is not None):
             raise ValueError("criterion / class_weight apply to recipe 'v1', the single-criterion recipe; the reference has no weighted or "
                              "focal form of recipe 'v2' (CE + Dice)")
@@ -205,6 +213,7 @@ class CPSTrainer:
         self.criterion = make_loss(cfg.criterion, cfg.num_classes, ignore_index=255, weight=fixed)
         if isinstance(self.criterion, FocalLoss):
             self.criterion.alpha, self.criterion.gamma = cfg.focal_alpha, cfg.focal_gamma
+        self.sup_con = SupConLoss(cfg.sup_con_temperature) if cfg.sup_con_loss_weight is not None else None
         self.iter = 0
 
     @property
@@ -217,13 +226,14 @@ class CPSTrainer:
     def _two_streams(self, on: bool):
         self.lanes.enabled = on
 
-    def _fwd_pair(self, a1, a2, use_amp=True, models=None, **kw):
+    def _fwd_pair(self, a1, a2, use_amp=True, models=None, sides=None, **kw):
         """model 1 on a1 = (x[, gt]) and model 2 on a2, phase by phase: encoders overlap on the two streams, the VQ phases
         run one after the other with the other stream idle (the distance kernels fill the GPU on their own, and their
         in-stream timing -- bench.py's roofline -- then measures the kernel, not the sharing), decoders overlap again.
         One stream or two, the phases are enqueued in this order (also the order of the RNG draws of the k-means inits).
         `use_amp=False`: this pair runs outside autocast whatever cfg.amp_dtype says (the pseudo-label passes).
-        `models`: the pair of modules to run (the teachers, for their pseudo labels), on the same streams; default the students."""
+        `models`: the pair of modules to run (the teachers, for their pseudo labels), on the same streams; default the students.
+        `sides`: a pair of dicts, one per network, handed to its finish() as `side` (the contrastive term of the labelled pair)."""
         m1, m2 = models or self.models
         L, amp = self.lanes, self.cfg.amp_dtype if use_amp else None
 
@@ -242,7 +252,11 @@ class CPSTrainer:
         q2 = run(1, m2.quantize, f2)
         if alone:
             L.hold(0)                                                   # ... and model 1 stays idle meanwhile
-        o1, o2 = run(0, m1.finish, *q1, *a1[1:], **kw), run(1, m2.finish, *q2, *a2[1:], **kw)
+        if sides is None:
+            o1, o2 = run(0, m1.finish, *q1, *a1[1:], **kw), run(1, m2.finish, *q2, *a2[1:], **kw)
+        else:
+            o1, o2 = run(0, m1.finish, *q1, *a1[1:], side=sides[0], **kw), run(1, m2.finish, *q2, *a2[1:], side=sides[1], **kw)
+            L.to_caller(*(v for d in sides for v in d.values()))
         L.to_caller(*o1, *o2)
         return o1, o2
 
@@ -288,12 +302,15 @@ class CPSTrainer:
         score_1, score_2 = self._pseudo_scores(ul_input)
         ul_train, score_1, score_2 = self._cutmix(ul_input, score_1, score_2)
         gt_ul_1, gt_ul_2, kw = self._targets(score_1, score_2, epoch_frac)
-        sup, unsup = self._train_forwards(l_input, l_target, ul_train, gt_ul_1, gt_ul_2, kw)
+        sup, unsup, sup_con = self._train_forwards(l_input, l_target, ul_train, gt_ul_1, gt_ul_2, kw)
         fused, ps1, sup_terms, cps_terms = self._terms(l_target, sup, unsup, score_1, score_2, kw)
         lr = self.sched.get_lr(self.iter)
         for o in self.opts:
             o.param_groups[0]["lr"] = lr
         loss, terms = self._total_loss(fused, sup_terms, cps_terms, [o[1] for o in sup + unsup], [o[3] for o in sup + unsup])
+        if sup_con is not None:                                         # train_supcon_unet.py:143-153: weight * (l_1 + l_2) joins the total
+            terms["sup_con_loss"] = (sup_con[0] + sup_con[1]) * cfg.sup_con_loss_weight
+            loss = loss + terms["sup_con_loss"]
         self._backward_and_step(loss)
         self.iter += 1
         with torch.no_grad():
@@ -377,16 +394,27 @@ class CPSTrainer:
         return gt_ul_1, gt_ul_2, dict(percent=100 - cfg.unsup_loss_drop_percent * (1 - epoch_frac))
 
     def _train_forwards(self, l_input, l_target, ul_train, gt_ul_1, gt_ul_2, kw):
-        """the labelled and the unlabelled training forward pair -> ((out_1, out_2), (out_1, out_2)), out = (pred, commitment,
-        usage, prototype).  The targets cross lanes: as of now (they are ready), waited for only before the unlabelled pair."""
+        """the labelled and the unlabelled training forward pair -> ((out_1, out_2), (out_1, out_2), sup_con), out = (pred, commitment,
+        usage, prototype).  The targets cross lanes: as of now (they are ready), waited for only before the unlabelled pair.
+        sup_con: cfg.sup_con_loss_weight -- each network's contrastive scalar of its labelled forward, made inside that forward on its
+        stream (the dicts are this call's own: nothing stays on the modules); else None, and the pair runs exactly as without the option."""
         g = self._glue
         ready = g.mark()
-        sup = self._fwd_pair((l_input, l_target), (l_input, l_target), **kw)
+        sup_con = None
+        if self.sup_con is None:
+            sup = self._fwd_pair((l_input, l_target), (l_input, l_target), **kw)
+        else:
+            sides = tuple(dict(sup_con=self.sup_con, keep=self.cfg.keep_aux) for _ in self.models)
+            sup = self._fwd_pair((l_input, l_target), (l_input, l_target), sides=sides, **kw)
+            sup_con = tuple(d["sup_con_loss"] for d in sides)
+            if self.cfg.keep_aux:
+                self.aux.update(decoder_out_1=sides[0]["decoder_out"], decoder_out_2=sides[1]["decoder_out"], sup_con_1=sup_con[0].detach(),
+                                sup_con_2=sup_con[1].detach())
         g.exchange(gt_ul_2, gt_ul_1, marks=ready)
         unsup = self._fwd_pair((ul_train, gt_ul_1), (ul_train, gt_ul_2), **kw)
         if g is OFF:
             self._join()
-        return sup, unsup
+        return sup, unsup, sup_con
 
     def _criterion(self, cls_weight, pred):
         """-> (crit(pred, target), fused): what the four terms of a step are computed with.  fused: the terms stay as their

@@ -756,6 +756,49 @@ int vqseg_resize_argmax_f(const float* const* views_host, const int* flips_host,
                           int64_t stride_px, int b, int c, int h, int w, int ho, int wo, uint8_t* label, float* top,
                           const int64_t* target, int64_t* counts, void* stream);
 
+/* Tiled (sliding-window) prediction: the network runs on native-resolution windows of an image and overlapping windows are blended
+ * (vq_seg_amd.nnf.extract_windows / merge_argmax, vq_seg_amd.predict.Predictor(window=...)).  The window rule, per axis, which host and
+ * device share (vq_seg_amd.nnf.window_starts):
+ *     n = ceil((extent - window) / stride) + 1,   start[k] = min(k * stride, extent - window),   1 <= stride <= window <= extent
+ * The last window is clamped to end at the border.  A grid is ny x nx windows per image, row-major (t = j * nx + i); window rows are
+ * image-major (row = b * T + t, T = ny * nx).  Both entry points take (extent, window, stride) per axis and derive the starts: there is
+ * no start table and no cap on the number of windows.  Windows up to 4096 a side (the linear blend's weights and their products
+ * are then exact f32 integers; their sum ws is an f32 running sum in the order stated below, exact while it stays below 2^24 --
+ * strides near window / 2 -- and rounded like any other f32 sum beyond that).
+ *
+ * vqseg_extract_windows_f: images f32 logical (b, 3, h, w), batch / channel / pixel strides in ELEMENTS as vqseg_resize_argmax_f takes
+ * them (planar or interleaved, rows dense) -> out [n_flips][b * T][3][nh][nw] f32.  Every window's crop (wh x ww image pixels at its
+ * start) is resized bilinearly (align_corners = 0, the arithmetic of vqseg_bilinear_f, bit for bit) to the network's size nh x nw with
+ * the taps clamped INSIDE the window, and stored once per flip code of flips_host (0..3: bit 0 columns, bit 1 rows; an index map on
+ * the output).  With (wh, ww) == (nh, nw) the crop is copied exactly.  Down-scaling is ATen's un-antialiased rule (two taps per axis
+ * whatever the factor), as everywhere in this library.  Pointers and scalars travel as kernel arguments: no device allocation, no
+ * host-to-device copy, no synchronisation.  Images and network inputs up to 2^27 pixels.  Grid capped by option "nn_grid_cap".
+ *
+ * vqseg_merge_argmax_f: n_views (1, 2 or 4) f32 logit tensors of logical shape (b * T, c, lh, lw), window rows stride_b ELEMENTS apart,
+ * planar or interleaved as vqseg_resize_argmax_f takes them, one flip code per view -> label / top / counts at ho x wo.  For output
+ * pixel (y, x) of image b and view v:
+ *     acc = 0, ws = 0
+ *     for j ascending over the windows with ys[j] <= y < ys[j] + wh,  for i ascending over those with xs[i] <= x < xs[i] + ww:
+ *         s   = bilinear sample (align_corners = 0, lh x lw -> wh x ww, the arithmetic of vqseg_bilinear_f) of the un-flipped view's
+ *               row b * T + j * nx + i at the local position (y - ys[j], x - xs[i])
+ *         w   = wy(y - ys[j]) * wx(x - xs[i]);   acc = fmaf(w, s, acc);   ws += w
+ *     m_v = acc / ws                                                     (IEEE f32 division)
+ *     z   = m_0 (+ m_1 (+ m_2 + m_3)) in view order;  n_views > 1: z *= 1 / n_views
+ * blend VQSEG_BLEND_UNIFORM: w = 1;  VQSEG_BLEND_LINEAR: wy(r) = min(r + 1, wh - r), wx(r) = min(r + 1, ww - r) -- integers.
+ * label, top and counts from z, their NULL rules, target and the argument errors: exactly as vqseg_resize_argmax_f.  With one window
+ * per image and the uniform blend the result is vqseg_resize_argmax_f's, bit for bit; with disjoint windows and the uniform blend it is
+ * vqseg_resize_argmax_f of every window on its own, pasted together.  Kernel shape as vqseg_resize_argmax_f (a wave takes 256 consecutive
+ * output pixels, four per lane and 64 apart; packed label stores; ballots, LDS histogram and integer atomics for the counts); the
+ * window loops run between per-pixel bounds that change only at window edges.  Window logits up to 2^27 pixels, outputs up to 2^30.
+ * Grid capped by option "nn_grid_cap". */
+#define VQSEG_BLEND_UNIFORM 0
+#define VQSEG_BLEND_LINEAR 1
+int vqseg_extract_windows_f(const float* images, int64_t stride_b, int64_t stride_c, int64_t stride_px, int b, int h, int w, int wh, int ww,
+                            int sy, int sx, int nh, int nw, const int* flips_host, int n_flips, float* out, void* stream);
+int vqseg_merge_argmax_f(const float* const* views_host, const int* flips_host, int n_views, int64_t stride_b, int64_t stride_c,
+                         int64_t stride_px, int b, int c, int lh, int lw, int ho, int wo, int wh, int ww, int sy, int sx, int blend,
+                         uint8_t* label, float* top, const int64_t* target, int64_t* counts, void* stream);
+
 /* Visualisation: the RGB bytes of a panel sheet for a batch in one pass (vq_seg_amd.nnf.render_sheet, vq_seg_amd.utils.visualize,
  * Predictor.render).  The full-resolution sheet is rows = b * ho by cols pixels; image i takes rows i * ho .. (i + 1) * ho - 1 of every
  * panel, panel p the columns x0[p] .. x0[p] + width[p] - 1.  Panel kinds:

@@ -145,6 +145,8 @@ SYMBOLS = {
     "vqseg_box_mix_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 3 + [c_void_p, ctypes.c_uint64, c_void_p]),
     "vqseg_affine_warp_f": (c_int, [c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 4 + [c_void_p, ctypes.c_uint64, c_void_p]),
     "vqseg_resize_argmax_f": (c_int, [c_void_p, c_void_p, c_int] + [c_int64] * 3 + [c_int] * 6 + [c_void_p] * 5),
+    "vqseg_extract_windows_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_int] * 9 + [c_void_p, c_int, c_void_p, c_void_p]),
+    "vqseg_merge_argmax_f": (c_int, [c_void_p, c_void_p, c_int] + [c_int64] * 3 + [c_int] * 11 + [c_void_p] * 5),
     "vqseg_render_sheet_u8": (c_int, [c_void_p] + [c_int64] * 3 + [c_int] * 2 + [c_void_p] * 2 + [c_int] * 6 + [c_void_p] * 3 + [c_int] +
                               [c_void_p] * 4 + [c_float, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "vqseg_supcon_workspace_bytes": (c_size_t, [c_int64]),

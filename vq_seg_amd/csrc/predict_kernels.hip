@@ -29,14 +29,11 @@
 #include "../../include/vqseg.h"
 #include "bilinear_device.h"
 #include "nn_kernels.h"
+#include "predict_epilogue.h"     // RA_PX, RA_TILE and everything after the mean logits, shared with tile_kernels.hip
 
 extern "C" int vqseg_set_error(int code, const char* msg);   // vqseg_abi.hip
 
 namespace vqseg {
-
-constexpr int RA_MAXV = 4, RA_MAXC = 4;
-constexpr int RA_PX = 4;                                    // output pixels per thread (64 apart: see above)
-constexpr int RA_TILE = 256 * RA_PX;                        // output pixels per workgroup and iteration
 
 struct ResizeArgmaxArgs {                                   // the views travel as kernel arguments: no device-side table, no copy
     const float* view[RA_MAXV];
@@ -118,23 +115,7 @@ __global__ __launch_bounds__(256, 4) void resize_argmax_kernel(const ResizeArgma
             }
 #pragma unroll
         for (int j = 0; j < RA_PX; ++j) {
-            float mx = -__builtin_inff();
-            arg[j] = 0;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if (a.V > 1) acc[j][c] = acc[j][c] * scale;
-                if (acc[j][c] > mx) {                       // first maximum, as torch.argmax
-                    mx = acc[j][c];
-                    arg[j] = c;
-                }
-            }
-            inv[j] = 0.0f;
-            if (a.top) {                                    // uniform
-                float sum = 0.0f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) sum += expf(acc[j][c] - mx);
-                inv[j] = 1.0f / sum;                        // exp(0) / sum: the probability of the arg-max class
-            }
+            ra_argmax_top<C>(acc[j], a.V > 1, scale, a.top != nullptr, arg[j], inv[j]);
             key[j] = tg[j] >= 0 && tg[j] < C ? (int)tg[j] * C + arg[j] : -1;
         }
         if (a.top) {                                        // 256 contiguous bytes per wave and store
@@ -142,40 +123,12 @@ __global__ __launch_bounds__(256, 4) void resize_argmax_kernel(const ResizeArgma
             for (int j = 0; j < RA_PX; ++j)
                 if (pw + j * 64 + lane < HW) a.top[img + pw + j * 64 + lane] = inv[j];
         }
-        if (a.label) {
-            if (pw + 64 * RA_PX <= HW && a.vec && (img & 3) == 0) {      // uniform across the wave: lane q stores the labels of pixels 4 q .. 4 q + 3
-                const unsigned mine4 = (unsigned)arg[0] | ((unsigned)arg[1] << 8) | ((unsigned)arg[2] << 16) | ((unsigned)arg[3] << 24);
-                const int shift = (lane >> 4) * 8;          // pixel 4 q + i sits in lane (4 q + i) & 63 as its byte (4 q + i) >> 6 = q >> 4
-                unsigned word = 0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) word |= (((unsigned)__shfl((int)mine4, (4 * lane + i) & 63) >> shift) & 0xffu) << (8 * i);
-                *reinterpret_cast<unsigned*>(a.label + img + pw + 4 * lane) = word;
-            } else {
-#pragma unroll
-                for (int j = 0; j < RA_PX; ++j)
-                    if (pw + j * 64 + lane < HW) a.label[img + pw + j * 64 + lane] = (uint8_t)arg[j];
-            }
-        }
+        if (a.label) ra_store_labels(a.label + img, img, pw, HW, lane, a.vec, arg);
         if (counting) {
-#pragma unroll
-            for (int j = 0; j < RA_PX; ++j)
-#pragma unroll
-                for (int k = 0; k < C * C; ++k) {
-                    const unsigned n = (unsigned)__popcll(__ballot(key[j] == k));
-                    mine += lane == k ? n : 0u;
-                }
+            ra_count<C>(key, lane, mine);
             const long next = tile + gridDim.x;
-            if (next >= tiles || (int)(next / per) != b) {  // leaving image b (uniform): waves -> LDS histogram -> one atomic per bin
-                if (lane < C * C && mine) atomicAdd(&cnt[lane], mine);
-                mine = 0;
-                __syncthreads();
-                if (threadIdx.x < C * C) {
-                    const unsigned n = cnt[threadIdx.x];
-                    if (n) atomicAdd(&a.counts[(long)b * C * C + threadIdx.x], (unsigned long long)n);
-                    cnt[threadIdx.x] = 0;
-                }
-                __syncthreads();
-            }
+            if (next >= tiles || (int)(next / per) != b)    // leaving image b (uniform): waves -> LDS histogram -> one atomic per bin
+                ra_flush_counts<C>(cnt, mine, lane, a.counts + (long)b * C * C);
         }
     }
 }

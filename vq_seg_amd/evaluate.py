@@ -16,6 +16,10 @@ batch stacked vertically -- as uint8 numpy arrays: a second `nnf.resize_argmax` 
 (utils.visualize.render_sheet), after which only the sheet's bytes cross to the host.  The labels shown are the arg-max of the
 network's logits resized directly to the display size (the reference resizes them to the mask size first, then again).  With None
 nothing changes: no extra launch, the same dict.
+
+`window` (with fused; `stride`, `blend`, `window_batch`, `net_size` as predict.Predictor takes them) scores tiled prediction: the
+network runs on windows of the images and one `nnf.merge_argmax` call blends them and counts.  The images and masks of a batch must
+then have the same size (e.g. BaseDataset(resize=None)); the sheets of `visualize` are not built for it.
 """
 from typing import Dict, Iterable, Tuple
 
@@ -56,42 +60,58 @@ def _detail_sheets(img, logits, flips, target, num_classes):
 
 @torch.no_grad()
 def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], num_classes: int,
-              device=None, amp_dtype=None, fused: bool = False, tta=None, visualize=None) -> Dict[str, object]:
+              device=None, amp_dtype=None, fused: bool = False, tta=None, visualize=None, window=None, stride=None,
+              blend: str = "linear", window_batch=None, net_size=None) -> Dict[str, object]:
     """batches yields (images (N, 3, H, W) float in [0, 1], labels (N, Hm, Wm) int class ids)."""
+    if window is not None and not fused:
+        raise ValueError("test_loop: window needs fused=True (the windows are blended inside the fused merge + arg-max)")
+    if window is not None and visualize is not None:
+        raise ValueError("test_loop: visualize is not built for tiled scoring (window=...)")
     if tta is not None and not fused:
         raise ValueError("test_loop: tta needs fused=True (the views are averaged inside the fused resize + arg-max)")
     if visualize is not None and not fused:
         raise ValueError("test_loop: visualize needs fused=True (the sheets are drawn from the fused path's views)")
-    views = Predictor(model, num_classes, amp_dtype=amp_dtype, tta=tta or ("none",)).views if fused else None
+    predictor = Predictor(model, num_classes, amp_dtype=amp_dtype, tta=tta or ("none",), window=window, stride=stride, blend=blend,
+                          window_batch=window_batch, net_size=net_size) if fused else None
+    views = predictor.views if fused else None
     was_training = model.training
     model.eval()
     meas = Measurement(num_classes)
     sums = dict(test_acc=0.0, test_miou=0.0, test_precision=0.0, test_recall=0.0, test_f1score=0.0)
     iou_per_class = np.zeros(num_classes, dtype=np.float64)
     n_batches = 0
-    for img, target in batches:
-        if device is not None:
-            img, target = img.to(device), target.to(device)
-        if fused:
-            logits, flips = views(img)
-            conf = nnf.resize_argmax(logits, tuple(target.shape[-2:]), flips=flips, target=target)[2]
-            hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (target.shape[-2] * target.shape[-1])
-            if visualize is not None:
-                visualize(n_batches, *_detail_sheets(img, logits, flips, target, num_classes))
-        else:
-            conf, hits = _resized_counts(model, img, target, num_classes, amp_dtype)
-        conf_np = conf.cpu().numpy()
-        miou, ious = meas.miou(conf_np)
-        precision, _ = meas.precision(conf_np)
-        recall, _ = meas.recall(conf_np)
-        sums["test_acc"] += float(hits.mean())
-        sums["test_miou"] += float(miou)
-        sums["test_precision"] += float(precision)
-        sums["test_recall"] += float(recall)
-        sums["test_f1score"] += float(meas.f1score(recall, precision))
-        iou_per_class += np.array(ious)
-        n_batches += 1
-    model.train(was_training)
+    try:
+        for img, target in batches:
+            if device is not None:
+                img, target = img.to(device), target.to(device)
+            if fused and window is not None:
+                if tuple(img.shape[-2:]) != tuple(target.shape[-2:]):
+                    raise ValueError(f"test_loop: tiled scoring needs images and masks of one size, got {tuple(img.shape[-2:])} and "
+                                     f"{tuple(target.shape[-2:])} (e.g. BaseDataset(resize=None))")
+                logits, flips, grid = predictor.tiled_views(img)
+                conf = nnf.merge_argmax(logits, grid, flips=flips, blend=blend, target=target)[2]
+                hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (target.shape[-2] * target.shape[-1])
+            elif fused:
+                logits, flips = views(img)
+                conf = nnf.resize_argmax(logits, tuple(target.shape[-2:]), flips=flips, target=target)[2]
+                hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (target.shape[-2] * target.shape[-1])
+                if visualize is not None:
+                    visualize(n_batches, *_detail_sheets(img, logits, flips, target, num_classes))
+            else:
+                conf, hits = _resized_counts(model, img, target, num_classes, amp_dtype)
+            conf_np = conf.cpu().numpy()
+            miou, ious = meas.miou(conf_np)
+            precision, _ = meas.precision(conf_np)
+            recall, _ = meas.recall(conf_np)
+            sums["test_acc"] += float(hits.mean())
+            sums["test_miou"] += float(miou)
+            sums["test_precision"] += float(precision)
+            sums["test_recall"] += float(recall)
+            sums["test_f1score"] += float(meas.f1score(recall, precision))
+            iou_per_class += np.array(ious)
+            n_batches += 1
+    finally:                                                 # whatever ends the loop, a refusal included
+        model.train(was_training)
     if n_batches == 0:
         raise ValueError("test_loop: no batches")
     out = {k: v / n_batches for k, v in sums.items()}

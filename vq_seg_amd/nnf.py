@@ -1929,6 +1929,205 @@ def resize_argmax(logits, size, flips=None, want_top=False, target=None):
     return label, top, counts
 
 
+# ------------------------------------------------------------------------------------------------
+# tiled prediction: windows of the images -> network inputs; window logits -> blended arg-max
+# ------------------------------------------------------------------------------------------------
+BLENDS = {"uniform": 0, "linear": 1}          # include/vqseg.h: VQSEG_BLEND_*
+MAX_WINDOW = 4096
+EXTRACT_WINDOWS_CALLS = 0                     # calls that reached the library (for tests, never read by the product)
+MERGE_ARGMAX_CALLS = 0
+
+# what extract_windows hands out and merge_argmax takes back: the images' batch and size, the window and stride in image pixels,
+# the windows per axis and the size the network sees
+WindowGrid = namedtuple("WindowGrid", "batch height width window stride ny nx net_size")
+
+
+def window_starts(extent, window, stride):
+    """the starts of the windows along one axis: n = ceil((extent - window) / stride) + 1, start[k] = min(k * stride, extent - window).
+    The last window is clamped to end at the border.  The kernels derive the same starts from (extent, window, stride)."""
+    extent, window, stride = int(extent), int(window), int(stride)
+    if not 1 <= stride <= window <= extent:
+        raise ValueError(f"window_starts: 1 <= stride <= window <= extent required, got stride {stride}, window {window}, extent {extent}")
+    n = -((window - extent) // stride) + 1
+    return [min(k * stride, extent - window) for k in range(n)]
+
+
+def _pair(v, what, E):
+    try:
+        h, w = (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+    except (TypeError, ValueError, IndexError):
+        raise E(f"{what} must be an int or a (h, w) pair, got {v!r}") from None
+    return h, w
+
+
+def _window_grid(batch, height, width, window, stride, net_size, who):
+    """the checked WindowGrid of a batch of `height` x `width` images"""
+    E = _hip.HipLibraryError
+    wh, ww = _pair(window, f"{who}: window", E)
+    sy, sx = (max(wh // 2, 1), max(ww // 2, 1)) if stride is None else _pair(stride, f"{who}: stride", E)
+    nh, nw = (wh, ww) if net_size is None else _pair(net_size, f"{who}: net_size", E)
+    if min(wh, ww, sy, sx, nh, nw) < 1:
+        raise E(f"{who}: window, stride and net_size must be positive, got {(wh, ww)}, {(sy, sx)}, {(nh, nw)}")
+    if wh > height or ww > width:
+        raise E(f"{who}: a window of {(wh, ww)} is larger than the image of {(height, width)} (no padding)")
+    if sy > wh or sx > ww:
+        raise E(f"{who}: a stride of {(sy, sx)} larger than the window of {(wh, ww)} leaves pixels uncovered")
+    if max(wh, ww) > MAX_WINDOW:
+        raise E(f"{who}: a window side above {MAX_WINDOW}, got {(wh, ww)}")
+    return WindowGrid(int(batch), int(height), int(width), (wh, ww), (sy, sx), len(window_starts(height, wh, sy)),
+                      len(window_starts(width, ww, sx)), (nh, nw))
+
+
+def _extract_windows_torch(images, grid, flips):
+    wh, ww = grid.window
+    crops = []
+    for b in range(grid.batch):
+        for y0 in window_starts(grid.height, wh, grid.stride[0]):
+            for x0 in window_starts(grid.width, ww, grid.stride[1]):
+                crops.append(images[b, :, y0:y0 + wh, x0:x0 + ww])
+    rows = torch.stack(crops)
+    if grid.net_size != grid.window:
+        rows = F.interpolate(rows, size=grid.net_size, mode="bilinear", align_corners=False)
+    return torch.stack([rows.flip(FLIP_DIMS[f]) if f else rows for f in flips])
+
+
+def extract_windows(images, window, stride=None, net_size=None, flips=(0,)):
+    """(windows (F, B * T, 3, nh, nw) f32, grid): every window of the window rule (window_starts; `window` and `stride` an int or
+    (h, w) in image pixels, stride default window // 2) cropped from `images` (B, 3, H, W) fp32, NCHW-contiguous or channels_last,
+    resized bilinearly (align_corners=False, taps clamped inside the window; ATen's un-antialiased rule when it shrinks) to
+    `net_size` (default: the window, an exact copy) and flipped by each code of `flips` (1..4 codes 0..3: bit 0 columns, bit 1 rows)
+    -- one HIP launch (vqseg_extract_windows_f).  Window rows are image-major, a grid row-major: row = b * T + j * nx + i.  Entry f
+    equals nnf.upsample_bilinear(crop, net_size).flip(dims of flips[f]) bit for bit.  `grid` is the WindowGrid merge_argmax takes
+    back.  Tensors that are not on the GPU are computed with torch ops.  No gradient flows."""
+    global EXTRACT_WINDOWS_CALLS
+    E = _hip.HipLibraryError
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3:
+        raise E(f"extract_windows: images must be a (B, 3, H, W) tensor, got {tuple(getattr(images, 'shape', ()))}")
+    flips = [int(f) for f in flips]
+    if not 1 <= len(flips) <= 4:
+        raise E(f"extract_windows: 1..4 flip codes, got {len(flips)}")
+    if any(f < 0 or f > 3 for f in flips):
+        raise E(f"extract_windows: a flip code is 0..3 (bit 0 columns, bit 1 rows), got {flips}")
+    b, _, h, w = images.shape
+    if min(b, h, w) < 1:
+        raise E("extract_windows: empty images")
+    grid = _window_grid(b, h, w, window, stride, net_size, "extract_windows")
+    x = images.detach()
+    fmt = torch.contiguous_format if x.is_contiguous() or not x.is_contiguous(memory_format=torch.channels_last) else torch.channels_last
+    x = x if x.is_contiguous(memory_format=fmt) else x.contiguous(memory_format=fmt)
+    ptr = _strided_f32(x, "images", b * 3 * h * w)
+    if not x.is_cuda:
+        return _extract_windows_torch(x, grid, flips), grid
+    rows, (nh, nw) = b * grid.ny * grid.nx, grid.net_size
+    out = torch.empty((len(flips), rows, 3, nh, nw), dtype=torch.float32, device=x.device)
+    farr = (ctypes.c_int * 4)(*(flips + [0] * (4 - len(flips))))
+    strides = (3 * h * w, h * w, 1) if fmt == torch.contiguous_format else (3 * h * w, 1, 3)
+    _launch("vqseg_extract_windows_f", x.device, ptr, *strides, b, h, w, *grid.window, *grid.stride, nh, nw, farr, len(flips),
+            _f32(out, "windows", out.numel()))
+    EXTRACT_WINDOWS_CALLS += 1
+    return out, grid
+
+
+def _merge_argmax_torch(views, flips, grid, linear, want_top, target):
+    """merge_argmax with torch ops, for tensors that are not on the GPU"""
+    (wh, ww), (sy, sx), T = grid.window, grid.stride, grid.ny * grid.nx
+    c = views[0].shape[1]
+    ry, rx = torch.arange(wh, dtype=torch.float32), torch.arange(ww, dtype=torch.float32)
+    wgt = (torch.minimum(ry + 1, wh - ry)[:, None] * torch.minimum(rx + 1, ww - rx)[None, :]) if linear else torch.ones(wh, ww)
+    wgt = wgt.to(views[0].device)
+    ys, xs = window_starts(grid.height, wh, sy), window_starts(grid.width, ww, sx)
+    z = None
+    for v, f in zip(views, flips):
+        s = F.interpolate(v.flip(FLIP_DIMS[f]) if f else v, size=(wh, ww), mode="bilinear", align_corners=False)
+        s = s.reshape(grid.batch, T, c, wh, ww)
+        acc = torch.zeros((grid.batch, c, grid.height, grid.width), dtype=torch.float32, device=v.device)
+        ws = torch.zeros((grid.height, grid.width), dtype=torch.float32, device=v.device)
+        for j, y0 in enumerate(ys):
+            for i, x0 in enumerate(xs):
+                acc[:, :, y0:y0 + wh, x0:x0 + ww] += wgt * s[:, j * grid.nx + i]
+                ws[y0:y0 + wh, x0:x0 + ww] += wgt
+        m = acc / ws
+        z = m if z is None else z + m
+    if len(views) > 1:
+        z = z * (1.0 / len(views))
+    b = grid.batch
+    label = z.argmax(dim=1)
+    top = torch.softmax(z, dim=1).max(dim=1).values if want_top else None
+    counts = None
+    if target is not None:
+        t = target.reshape(b, -1)
+        cats = c * t + label.reshape(b, -1) + (c * c) * torch.arange(b, device=t.device)[:, None]
+        counts = torch.bincount(cats[(t >= 0) & (t < c)], minlength=b * c * c).reshape(b, c, c)
+    return label.to(torch.uint8), top, counts
+
+
+def merge_argmax(views, grid, flips=None, blend="linear", want_top=False, target=None):
+    """(label (B, H, W) u8, top probability (B, H, W) f32 | None, confusion counts (B, C, C) i64 | None) of the images whose windows
+    (`grid`, as extract_windows returned it) went through the network: `views` is one (B * T, C, lh, lw) fp32 logit tensor or a list of
+    1, 2 or 4 of them with one flip code each (`flips`: undone as an index map).  Per pixel and view, the windows that hold the pixel
+    are summed in grid order, each resized bilinearly (align_corners=False) from (lh, lw) to the window's extent and weighted by
+    `blend` -- "uniform": 1, "linear": min(r + 1, window - r) along each axis, so a window counts least at its border -- and divided
+    by the weights' sum; the views' means are averaged, label is the first maximum, top its softmax probability, counts (with
+    `target` (B, H, W), any integer type) the per-image confusion matrix -- in one HIP pass (vqseg_merge_argmax_f), without the
+    (B, C, H, W) logit tensor.  With one window per image and "uniform" it equals resize_argmax bit for bit.  Tensors that are
+    not on the GPU are computed with torch ops.  No gradient flows."""
+    global MERGE_ARGMAX_CALLS
+    E = _hip.HipLibraryError
+    views = [views] if torch.is_tensor(views) else list(views)
+    nv = len(views)
+    if nv not in (1, 2, 4):
+        raise E(f"merge_argmax: 1, 2 or 4 views (the mean's 1 / V must be exact), got {nv}")
+    flips = [0] * nv if flips is None else [int(f) for f in flips]
+    if len(flips) != nv:
+        raise E(f"merge_argmax: one flip code per view required: {nv} views, {len(flips)} codes")
+    if any(f < 0 or f > 3 for f in flips):
+        raise E(f"merge_argmax: a flip code is 0..3 (bit 0 columns, bit 1 rows), got {flips}")
+    if blend not in BLENDS:
+        raise E(f"merge_argmax: blend is one of {sorted(BLENDS)}, got {blend!r}")
+    if not isinstance(grid, WindowGrid):
+        raise E(f"merge_argmax: grid must be the WindowGrid extract_windows returned, got {type(grid).__name__}")
+    grid = _window_grid(grid.batch, grid.height, grid.width, grid.window, grid.stride, grid.net_size, "merge_argmax")
+    if not all(torch.is_tensor(v) and v.dim() == 4 for v in views):
+        raise E("merge_argmax: every view must be a (B * T, C, lh, lw) tensor")
+    x0 = views[0]
+    if any(v.shape != x0.shape or v.device != x0.device for v in views):
+        raise E(f"merge_argmax: every view must have view 0's shape and device, got shapes {[tuple(v.shape) for v in views]}")
+    n, c, lh, lw = x0.shape
+    b, ho, wo = grid.batch, grid.height, grid.width
+    if not 2 <= c <= 4:
+        raise E(f"merge_argmax: 2..4 classes, got {c}")
+    if min(b, lh, lw) < 1:
+        raise E("merge_argmax: empty input")
+    if n != b * grid.ny * grid.nx:
+        raise E(f"merge_argmax: the grid has {b} x {grid.ny} x {grid.nx} = {b * grid.ny * grid.nx} windows, the views have {n} rows")
+    fmt = torch.contiguous_format if x0.is_contiguous() or not x0.is_contiguous(memory_format=torch.channels_last) else torch.channels_last
+    views = [v.detach() for v in views]
+    views = [v if v.is_contiguous(memory_format=fmt) else v.contiguous(memory_format=fmt) for v in views]
+    ptrs = [_strided_f32(v, "window logits" if nv == 1 else f"window logits (view {i})", n * c * lh * lw) for i, v in enumerate(views)]
+    tgt = None
+    if target is not None:
+        if not torch.is_tensor(target) or target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+            raise E(f"merge_argmax: target must be an integer tensor, got {getattr(target, 'dtype', type(target).__name__)}")
+        if tuple(target.shape) != (b, ho, wo):
+            raise E(f"merge_argmax: target must have the output's shape {(b, ho, wo)}, got {tuple(target.shape)}")
+        tgt = target.detach().long().contiguous()
+    dev = x0.device
+    if not x0.is_cuda:
+        return _merge_argmax_torch(views, flips, grid, blend == "linear", want_top, tgt)
+    label = torch.empty((b, ho, wo), dtype=torch.uint8, device=dev)
+    top = torch.empty((b, ho, wo), dtype=torch.float32, device=dev) if want_top else None
+    counts = torch.empty((b, c, c), dtype=torch.int64, device=dev) if tgt is not None else None
+    varr, farr = (ctypes.c_void_p * 4)(), (ctypes.c_int * 4)(*(flips + [0] * (4 - nv)))
+    for i, p in enumerate(ptrs):
+        varr[i] = _hip.on_gpu(p)
+    strides = (c * lh * lw, lh * lw, 1) if fmt == torch.contiguous_format else (c * lh * lw, 1, c)
+    _launch("vqseg_merge_argmax_f", dev, varr, farr, nv, *strides, b, c, lh, lw, ho, wo, *grid.window, *grid.stride, BLENDS[blend],
+            _T(label, "labels", dtype=torch.uint8, numel=b * ho * wo), _f32(top, "top probability", b * ho * wo),
+            _T(tgt, "target", dtype=torch.int64, numel=b * ho * wo), _T(counts, "confusion counts", dtype=torch.int64, numel=b * c * c))
+    MERGE_ARGMAX_CALLS += 1
+    return label, top, counts
+
+
 
 # ------------------------------------------------------------------------------------------------
 # visualisation: labels, targets and the input image -> the RGB bytes of a panel sheet in one pass

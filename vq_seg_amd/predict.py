@@ -8,6 +8,17 @@ model-major, then in `tta` order; their number (models x tta) is 1, 2 or 4, so t
 
     Predictor(model, num_classes)(images).label                        # (N, H, W) uint8
     Predictor([m1, m2], 3, tta=("none", "hflip"))(images, size=(966, 1296), want_confidence=True)
+
+Tiled (sliding-window) prediction, `window=...`: the network runs on native-resolution windows of the images instead of the whole
+image squeezed to its training size, and overlapping windows are blended with a weight that falls off towards each window's border.
+ONE `nnf.extract_windows` launch (vqseg_extract_windows_f) cuts, resizes and flips the windows of all test-time views, the forwards
+run over them in chunks of `window_batch`, and ONE `nnf.merge_argmax` launch (vqseg_merge_argmax_f) blends the windows, averages the
+views and takes the arg-max -- again without a full-resolution logit tensor.  The window grid is nnf.window_starts' (the last window
+of an axis is clamped to end at the border).  Not built: windows larger than the image (padding), rotated views, averaging
+probabilities instead of logits.
+
+    Predictor(model, 3, window=512)(images).label                      # stride 256, "linear" blend, at the images' own size
+    Predictor([m1, m2], 3, tta=("none", "hflip"), window=(512, 640), stride=384, window_batch=8)(images, want_confidence=True)
 """
 from collections import namedtuple
 from typing import Iterable, Iterator, List, Optional, Sequence, Tuple, Union
@@ -25,10 +36,16 @@ Prediction = namedtuple("Prediction", "label confidence")      # (N, H, W) uint8
 class Predictor:
     """`models`: one nn.Module or a sequence (two: the CPS ensemble); `tta`: a selection of "none", "hflip", "vflip", "hvflip";
     len(models) * len(tta) must be 1, 2 or 4.  `amp_dtype`: the forwards run under torch.autocast on the GPU (None: fp32).
-    `device`: where the images are moved to before the forward (None: they stay where they are)."""
+    `device`: where the images are moved to before the forward (None: they stay where they are).
+    `window` (an int or (h, w) in image pixels; None: the whole image goes through the network, as above) turns tiled prediction on:
+    `stride` (default window // 2), `blend` ("linear" or "uniform": nnf.merge_argmax), `net_size` (what the network sees of a
+    window, if not the window itself: the windows are resized bilinearly on the way in and their logits on the way out) and
+    `window_batch` (how many windows go through one forward, default all of a view: it bounds the forward's activations).  The
+    logits of ALL windows are held until the merge: B * T * C * lh * lw * 4 bytes per view (B images, T windows each, C classes,
+    lh x lw logits per window)."""
 
     def __init__(self, models: Union[nn.Module, Sequence[nn.Module]], num_classes: int, amp_dtype=None, tta: Sequence[str] = ("none",),
-                 device=None):
+                 device=None, window=None, stride=None, blend: str = "linear", window_batch: Optional[int] = None, net_size=None):
         self.models: List[nn.Module] = [models] if isinstance(models, nn.Module) else list(models)
         self.tta: Tuple[str, ...] = (tta,) if isinstance(tta, str) else tuple(tta)
         unknown = [t for t in self.tta if t not in TTA_FLIPS]
@@ -43,6 +60,58 @@ class Predictor:
         if not 2 <= int(num_classes) <= 4:
             raise ValueError(f"num_classes must be 2..4, got {num_classes}")
         self.num_classes, self.amp_dtype, self.device = int(num_classes), amp_dtype, device
+        if window is None and (stride is not None or window_batch is not None or net_size is not None):
+            raise ValueError("stride, window_batch and net_size belong to tiled prediction: give a window")
+        if blend not in nnf.BLENDS:
+            raise ValueError(f"blend is one of {sorted(nnf.BLENDS)}, got {blend!r}")
+        if window_batch is not None and int(window_batch) < 1:
+            raise ValueError(f"window_batch must be positive, got {window_batch}")
+        self.window, self.stride, self.blend, self.net_size = window, stride, blend, net_size
+        self.window_batch = None if window_batch is None else int(window_batch)
+
+    def _forward(self, model: nn.Module, x: torch.Tensor) -> torch.Tensor:
+        """fp32 logits of one forward, under autocast on the GPU if asked for"""
+        if self.amp_dtype is not None and x.is_cuda:
+            with torch.autocast("cuda", dtype=self.amp_dtype):
+                out = model(x)
+        else:
+            out = model(x)
+        out = out[0] if isinstance(out, tuple) else out
+        if out.dim() != 4 or out.shape[1] != self.num_classes:
+            raise ValueError(f"the model returned logits of shape {tuple(out.shape)}, expected (N, {self.num_classes}, h, w)")
+        return out.float()
+
+    def tiled_views(self, images: torch.Tensor):
+        """tiled mode -> (fp32 window logits (B * T, C, lh, lw) per view, flip code per view, the nnf.WindowGrid): one extract launch
+        for the flips of all views, then the forwards in chunks of `window_batch` per model x flip.  Views are ordered as `views`
+        orders them.  The models' modes are the caller's business."""
+        if self.window is None:
+            raise ValueError("tiled_views: this Predictor has no window")
+        if self.device is not None:
+            images = images.to(self.device)
+        if images.dim() != 4:
+            raise ValueError(f"images must be (N, 3, H, W), got {tuple(images.shape)}")
+        wh, ww = (int(self.window),) * 2 if isinstance(self.window, int) else (int(self.window[0]), int(self.window[1]))
+        if wh > images.shape[-2] or ww > images.shape[-1]:
+            raise ValueError(f"a window of {(wh, ww)} is larger than the images of {tuple(images.shape[-2:])}: padding is not built")
+        codes = [TTA_FLIPS[name] for name in self.tta]
+        windows, grid = nnf.extract_windows(images.float(), (wh, ww), self.stride, self.net_size, flips=codes)
+        rows = windows.shape[1]
+        step = rows if self.window_batch is None else self.window_batch
+        logits, flips = [], []
+        for model in self.models:
+            for k, code in enumerate(codes):
+                outs = [self._forward(model, windows[k, at:at + step]) for at in range(0, rows, step)]
+                logits.append(outs[0] if len(outs) == 1 else torch.cat(outs))
+                flips.append(code)
+        return logits, flips, grid
+
+    def _own_size(self, images: torch.Tensor, size) -> Tuple[int, int]:
+        """tiled mode predicts at the images' own size only"""
+        own = tuple(int(n) for n in images.shape[-2:])
+        if size is not None and (int(size[0]), int(size[1])) != own:
+            raise ValueError(f"tiled prediction is at the images' own size {own}, got size {tuple(size)}")
+        return own
 
     def views(self, images: torch.Tensor):
         """-> (fp32 logits per view, flip code per view), model-major then tta order.  The models' modes are the caller's business."""
@@ -53,28 +122,26 @@ class Predictor:
             for name in self.tta:
                 code = TTA_FLIPS[name]
                 x = images.flip(nnf.FLIP_DIMS[code]) if code else images          # an exact permutation: the un-flip is the same index map
-                if self.amp_dtype is not None and x.is_cuda:
-                    with torch.autocast("cuda", dtype=self.amp_dtype):
-                        out = model(x)
-                else:
-                    out = model(x)
-                out = out[0] if isinstance(out, tuple) else out
-                if out.dim() != 4 or out.shape[1] != self.num_classes:
-                    raise ValueError(f"the model returned logits of shape {tuple(out.shape)}, expected (N, {self.num_classes}, h, w)")
-                logits.append(out.float())
+                logits.append(self._forward(model, x))
                 flips.append(code)
         return logits, flips
 
     @torch.no_grad()
     def __call__(self, images: torch.Tensor, size: Optional[Sequence[int]] = None, want_confidence: bool = False) -> Prediction:
-        """images (N, 3, H, W) -> Prediction(label (N, Ho, Wo) uint8, confidence (N, Ho, Wo) f32 | None); size None: (H, W)."""
-        size = tuple(images.shape[-2:]) if size is None else (int(size[0]), int(size[1]))
+        """images (N, 3, H, W) -> Prediction(label (N, Ho, Wo) uint8, confidence (N, Ho, Wo) f32 | None); size None: (H, W).
+        Tiled mode: `size` must be None or the images' own."""
+        size = self._own_size(images, size) if self.window is not None else \
+            tuple(images.shape[-2:]) if size is None else (int(size[0]), int(size[1]))
         modes = [m.training for m in self.models]
         for m in self.models:
             m.eval()
         try:
-            logits, flips = self.views(images)
-            label, top, _ = nnf.resize_argmax(logits, size, flips=flips, want_top=want_confidence)
+            if self.window is not None:
+                logits, flips, grid = self.tiled_views(images)
+                label, top, _ = nnf.merge_argmax(logits, grid, flips=flips, blend=self.blend, want_top=want_confidence)
+            else:
+                logits, flips = self.views(images)
+                label, top, _ = nnf.resize_argmax(logits, size, flips=flips, want_top=want_confidence)
         finally:
             for m, was_training in zip(self.models, modes):
                 m.train(was_training)
@@ -87,20 +154,29 @@ class Predictor:
         images' device: the views of __call__ (ensemble and test-time views averaged inside nnf.resize_argmax), then one render
         launch (utils.visualize.render_sheet; vqseg_render_sheet_u8 on the GPU) from the labels, `targets` (N, Ht, Wt) at any size
         and the images themselves.  `panels` default: image | target | pred | 20 px white | mix_pred (without `targets`: no target
-        panel); size None: (H, W)."""
+        panel); size None: (H, W).  Tiled mode: the merged labels of __call__ are what the sheet shows (`size`: None or the
+        images' own)."""
         from .utils.visualize import GAP, render_sheet
-        size = tuple(images.shape[-2:]) if size is None else (int(size[0]), int(size[1]))
+        size = self._own_size(images, size) if self.window is not None else \
+            tuple(images.shape[-2:]) if size is None else (int(size[0]), int(size[1]))
         if panels is None:
             panels = ["image"] + (["target"] if targets is not None else []) + ["pred", ("fill", GAP), "mix_pred"]
         modes = [m.training for m in self.models]
         for m in self.models:
             m.eval()
         try:
-            logits, flips = self.views(images)
+            if self.window is not None:
+                logits, flips, grid = self.tiled_views(images)
+                label = nnf.merge_argmax(logits, grid, flips=flips, blend=self.blend)[0]
+            else:
+                logits, flips = self.views(images)
         finally:
             for m, was_training in zip(self.models, modes):
                 m.train(was_training)
         dev = logits[0].device
+        if self.window is not None:
+            return render_sheet(panels, images.to(dev), label, None if targets is None else targets.to(dev), size=size, palette=palette,
+                                alpha=alpha, half=half, num_classes=self.num_classes)
         return render_sheet(panels, images.to(dev), logits, None if targets is None else targets.to(dev), size=size, palette=palette, alpha=alpha,
                             half=half, flips=flips)
 
@@ -112,6 +188,9 @@ class Predictor:
 
 
 def predict_batches(models, batches: Iterable, num_classes: int, amp_dtype=None, tta: Sequence[str] = ("none",), device=None,
-                    size: Optional[Sequence[int]] = None, want_confidence: bool = False) -> Iterator[Prediction]:
-    """Predictor(models, num_classes, amp_dtype, tta, device).predict_batches(batches, size, want_confidence)"""
-    return Predictor(models, num_classes, amp_dtype=amp_dtype, tta=tta, device=device).predict_batches(batches, size, want_confidence)
+                    size: Optional[Sequence[int]] = None, want_confidence: bool = False, window=None, stride=None, blend: str = "linear",
+                    window_batch: Optional[int] = None, net_size=None) -> Iterator[Prediction]:
+    """Predictor(models, num_classes, amp_dtype, tta, device, window, stride, blend, window_batch, net_size)
+    .predict_batches(batches, size, want_confidence)"""
+    return Predictor(models, num_classes, amp_dtype=amp_dtype, tta=tta, device=device, window=window, stride=stride, blend=blend,
+                     window_batch=window_batch, net_size=net_size).predict_batches(batches, size, want_confidence)

@@ -856,6 +856,36 @@ int vqseg_supcon_backward_f(int bf16, const void* f1, const void* f2, int64_t ro
                             const int64_t* gt2, int ht, int wt, float temperature, const float* stats, const float* g_scalar, void* d_f1,
                             void* d_f2, int64_t grad_row_stride, void* stream);
 
+/* ---------------------------------------------------------------------------------- *
+ * Confidence-weighted soft cross-pseudo-supervision loss (conf_ce_loss of deprecated/train_vq_pt_unet_conf_ce.py:50-113;
+ * vq_seg_amd.nnf.conf_ce / conf_ce_pair, vq_seg_amd.loss.conf_ce_loss) of INPUT logits x and TARGET logits t, both logical
+ * (b, c, hw) f32 with 2..4 classes, each addressed through its own batch / class / pixel strides in ELEMENTS (NCHW or channels_last,
+ * as the Dice sums take them).  Per pixel, q = softmax(t), w = max q, k = first arg-max of t, p = softmax(x):
+ *     pos = w * (logsumexp(x) - x_k), summed over the M pixels with w >= threshold
+ *     n_c = -[c != k'] log clamp(1 - p_c, 1e-7, 1), summed over the Mn elements with softmax(t / temperature)_c < threshold_neg
+ *           (k' = first arg-max of t / temperature; the element c == k' adds 0 but counts)
+ *     loss = sum pos / M + [threshold_neg > 0] (sum n / Mn + 0.5 sum p_c^2 / (b c hw)),   a sum over nothing divided by 0 is 0
+ * 1 - p_c is (sum of the other classes' exponentials) / (sum of all), never a subtraction.  pair = 1: stats / loss slot 0 is
+ * loss(x <- t), slot 1 is loss(t <- x), the roles swapped, from one read of both tensors.
+ *   forward : stats [pair + 1][8] f64 DEVICE = (sum pos, sum n, sum p^2, M, Mn, 1/M or 0, 1/Mn or 0, loss); loss [pair + 1] f32.
+ *             Block sums in double and integer counts, folded in a fixed order by one workgroup: no atomics, two calls agree
+ *             bit for bit; nothing returns to the host.  workspace: vqseg_conf_ce_workspace_bytes(b, hw), 8-byte aligned.
+ *   backward: `stats` as the forward wrote it, g_scalar [pair + 1] f32 DEVICE (the upstream scalar of each slot).
+ *             pair = 0: g_x = g[0] d loss / d x; g_t = g[0] d loss / d t -- the path through the weight w: the targets are NOT
+ *             detached -- unless detach_targets (then g_t may be NULL and is not written).
+ *             pair = 1: g_x = g[0] d loss(x <- t) / d x + g[1] d loss(t <- x) / d x, g_t likewise; detach_targets drops the
+ *             target-side half of each.  Masks and arg-maxes are constants.  g_x takes x's strides, g_t takes t's.
+ * temperature > 0, threshold_neg >= 0, b <= 65535.
+ * ---------------------------------------------------------------------------------- */
+size_t vqseg_conf_ce_workspace_bytes(int b, int64_t hw);
+int vqseg_conf_ce_forward_f(const float* x, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_px, const float* t, int64_t t_stride_b,
+                            int64_t t_stride_c, int64_t t_stride_px, int b, int c, int64_t hw, float threshold, float threshold_neg,
+                            float temperature, int pair, void* workspace, size_t workspace_bytes, double* stats, float* loss, void* stream);
+int vqseg_conf_ce_backward_f(const float* x, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_px, const float* t, int64_t t_stride_b,
+                             int64_t t_stride_c, int64_t t_stride_px, int b, int c, int64_t hw, float threshold, float threshold_neg,
+                             float temperature, int pair, int detach_targets, const double* stats, const float* g_scalar, float* g_x,
+                             float* g_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 # Lists the gfx950 kernels that spill registers (device assembly; the host object's disassembly shows nothing of this):
 #   bash tools/check_spills.sh [file.hip ...]          (default: every kernel file)
 cd "$(dirname "$0")/../vq_seg_amd/csrc"
-for f in ${@:-vq_assign.hip vq_filter.hip vq_tail.hip vq_codebook.hip conv_igemm.hip conv_patch.hip conv_wgrad.hip conv_pack.hip nn_bn.hip nn_spatial.hip nn_head.hip nn_stem.hip loss_kernels.hip supcon_kernels.hip}; do
+for f in ${@:-vq_assign.hip vq_filter.hip vq_tail.hip vq_codebook.hip conv_igemm.hip conv_patch.hip conv_wgrad.hip conv_pack.hip nn_bn.hip nn_spatial.hip nn_head.hip nn_stem.hip loss_kernels.hip supcon_kernels.hip conf_ce_kernels.hip}; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S "$f" -o /tmp/spills_$$.s 2>/dev/null || { echo "$f: compile failed"; continue; }
   python3 - "$f" /tmp/spills_$$.s <<'PY'
 import re, sys

@@ -154,6 +154,11 @@ SYMBOLS = {
                                        c_void_p, c_size_t, c_void_p, c_void_p]),
     "vqseg_supcon_backward_f": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "vqseg_conf_ce_workspace_bytes": (c_size_t, [c_int, c_int64]),
+    "vqseg_conf_ce_forward_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p] + [c_int64] * 3 + [c_int, c_int, c_int64, c_float, c_float, c_float,
+                                        c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "vqseg_conf_ce_backward_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p] + [c_int64] * 3 + [c_int, c_int, c_int64, c_float, c_float, c_float,
+                                         c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

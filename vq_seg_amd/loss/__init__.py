@@ -7,6 +7,7 @@ from torch import nn
 from .dice_loss import DiceLoss, dice_loss  # noqa: F401
 from .focal_loss import FocalLoss, focal_loss  # noqa: F401
 from .contrastive_loss import SupConLoss  # noqa: F401  (not a criterion of the factory: loss_dict keeps the reference's four keys)
+from .conf_ce_loss import ConfCELoss, conf_ce_loss, unreliable_weight  # noqa: F401  (not in loss_func_dict: its entries take labels)
 
 
 def cross_entropy(input, target, weight=None, *args, **kwargs):

@@ -1653,6 +1653,112 @@ def supcon_stats(x, target, temperature=0.04):
     return _supcon_forward(x, target, temperature)[2][:3]
 
 
+# ------------------------------------------------------------------------------------------------
+# Confidence-weighted soft CPS loss (conf_ce_loss of deprecated/train_vq_pt_unet_conf_ce.py:50-113): one pass forward, one backward
+# over input AND target logits (vqseg_conf_ce_*); the pair form gives both directions from one read of the two tensors
+# ------------------------------------------------------------------------------------------------
+CONF_CE_STATS = ("sum_pos", "sum_neg", "sum_p2", "m", "mn", "inv_m", "inv_mn", "loss")      # the columns of the stats record
+
+
+def conf_ce_supported(x, t) -> bool:
+    """what the fused pass takes: two (B, C, H, W) float32 GPU logit tensors of one shape and device, 2..4 classes (the shapes and
+    layouts of dice_sums_supported); everything else is loss.conf_ce_loss's torch-op form"""
+    return (torch.is_tensor(x) and torch.is_tensor(t) and x.dim() == 4 and dice_sums_supported(x, x.shape[1]) and t.shape == x.shape
+            and t.dtype == torch.float32 and t.device == x.device and x.numel() > 0 and x.shape[0] <= 65535)
+
+
+def _conf_logits(v, name):
+    """dense logits, NCHW or channels_last (the gradient is allocated with the same strides), and their (batch, class, pixel) strides"""
+    if not torch.is_tensor(v) or v.dim() != 4:
+        raise _hip.HipLibraryError(f"conf_ce: {name} must be a (B, C, H, W) tensor, got {tuple(getattr(v, 'shape', ()))}")
+    if not (v.is_contiguous() or v.is_contiguous(memory_format=torch.channels_last)):
+        v = v.contiguous()
+    sb, sc, _sh, sw = v.stride()
+    return v, (sb, sc, sw)
+
+
+def _conf_forward(x, t, threshold, threshold_neg, temperature, pair):
+    x, xs = _conf_logits(x.detach(), "inputs")
+    t, ts = _conf_logits(t.detach(), "targets")
+    if t.shape != x.shape:
+        raise _hip.HipLibraryError(f"conf_ce: inputs and targets must have one shape, got {tuple(x.shape)} and {tuple(t.shape)}")
+    b, c, h, w = x.shape
+    hw, dev, nd = h * w, x.device, 2 if pair else 1
+    nbytes = lib().vqseg_conf_ce_workspace_bytes(b, hw)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)     # (8-byte aligned)
+    stats = torch.empty(nd, len(CONF_CE_STATS), dtype=torch.float64, device=dev)
+    loss = torch.empty(nd, dtype=torch.float32, device=dev)
+    cfg = (b, c, hw, xs, ts, float(threshold), float(threshold_neg), float(temperature), int(bool(pair)))
+    _launch("vqseg_conf_ce_forward_f", dev, _strided_f32(x, "input logits", b * c * hw), *xs, _strided_f32(t, "target logits", b * c * hw), *ts,
+            b, c, hw, cfg[5], cfg[6], cfg[7], cfg[8], _T(ws, "workspace", dtype=torch.float64, numel=nbytes // 8), nbytes,
+            _T(stats, "statistics", dtype=torch.float64, numel=nd * len(CONF_CE_STATS)), _f32(loss, "loss", nd))
+    return x, t, stats, loss, cfg
+
+
+def _conf_backward(x, t, stats, cfg, g, want_t):
+    """-> (g_x, g_t or None): each with its tensor's strides.  `g`: the upstream scalar of each slot, on the device"""
+    b, c, hw, xs, ts, threshold, threshold_neg, temperature, pair = cfg
+    nd = pair + 1
+    g_x = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
+    g_t = torch.empty_strided(t.shape, t.stride(), dtype=torch.float32, device=t.device) if (want_t or pair) else None
+    _launch("vqseg_conf_ce_backward_f", x.device, _strided_f32(x, "input logits", b * c * hw), *xs, _strided_f32(t, "target logits", b * c * hw), *ts,
+            b, c, hw, threshold, threshold_neg, temperature, pair, int(not want_t),
+            _T(stats, "statistics", dtype=torch.float64, numel=nd * len(CONF_CE_STATS)), _f32(g, "loss gradient", nd),
+            _strided_f32(g_x, "input gradient", b * c * hw), _strided_f32(g_t, "target gradient", b * c * hw))
+    return g_x, g_t
+
+
+class _ConfCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, threshold, threshold_neg, temperature, detach_targets):
+        xd, td, stats, loss, cfg = _conf_forward(x, t, threshold, threshold_neg, temperature, False)
+        ctx.save_for_backward(xd, td, stats)
+        ctx.cfg, ctx.detach = cfg, bool(detach_targets)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g_out):
+        xd, td, stats = ctx.saved_tensors
+        g = g_out.detach().float().reshape(1).contiguous()       # stays on the device: this is where a weight on the term enters
+        g_x, g_t = _conf_backward(xd, td, stats, ctx.cfg, g, not ctx.detach and ctx.needs_input_grad[1])
+        return g_x, g_t, None, None, None, None
+
+
+class _ConfCEPair(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, threshold, threshold_neg, temperature, detach_targets):
+        ad, bd, stats, loss, cfg = _conf_forward(a, b, threshold, threshold_neg, temperature, True)
+        ctx.save_for_backward(ad, bd, stats)
+        ctx.cfg, ctx.detach = cfg, bool(detach_targets)
+        return loss[0], loss[1]
+
+    @staticmethod
+    def backward(ctx, g_ab, g_ba):
+        ad, bd, stats = ctx.saved_tensors
+        g = torch.stack([g_ab.detach().float().reshape(()), g_ba.detach().float().reshape(())])
+        g_a, g_b = _conf_backward(ad, bd, stats, ctx.cfg, g, not ctx.detach)
+        return g_a, g_b, None, None, None, None
+
+
+def conf_ce(x, t, threshold=0.6, threshold_neg=0.0, temperature=1.0, detach_targets=False):
+    """conf_ce_loss of input logits x against target LOGITS t (both pass conf_ce_supported): a 0-d float32 tensor.  The targets are
+    not detached unless asked: their gradient is the path through the per-pixel weight max softmax(t).  M == 0 gives an attached 0
+    with zero gradients, Mn == 0 a zero negative term (include/vqseg.h)."""
+    return _ConfCE.apply(x, t, threshold, threshold_neg, temperature, detach_targets)
+
+
+def conf_ce_pair(a, b, threshold=0.6, threshold_neg=0.0, temperature=1.0, detach_targets=False):
+    """(conf_ce(a <- b), conf_ce(b <- a)): one forward launch reads a and b once for both directions, one backward launch writes both
+    gradients, each the sum over the two directions scaled by that direction's own upstream scalar (read on the device).  Bit for bit
+    the values of two conf_ce calls, and with unit upstream scalars their summed gradients."""
+    return _ConfCEPair.apply(a, b, threshold, threshold_neg, temperature, detach_targets)
+
+
+def conf_ce_stats(x, t, threshold=0.6, threshold_neg=0.0, temperature=1.0, pair=False):
+    """the forward's statistics record, (1 or 2, 8) float64 on the device with the columns CONF_CE_STATS, no gradient (tests, profiles)"""
+    return _conf_forward(x, t, threshold, threshold_neg, temperature, pair)[2]
+
+
 class _ConvBias(torch.autograd.Function):
     """k x k / stride 1 convolution WITH bias and a handful of output channels, fp32 (the plain Unet's segmentation head: 32 -> 3,
     segmentation_head.py:78-83) on the precise-mode kernels: output channels zero-padded to the kernels' 4-channel granule, the bias in

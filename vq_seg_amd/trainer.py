@@ -27,6 +27,7 @@ from .loss import compute_class_weight, cross_entropy, make_loss
 from .loss.dice_loss import DiceLoss, ce_dice_loss, dice_loss
 from .loss.focal_loss import FocalLoss
 from .loss.contrastive_loss import SupConLoss
+from .loss.conf_ce_loss import conf_ce_loss, unreliable_weight
 from .measurement import confusion_matrix_device, miou_device
 from . import nnf
 from .averaging import AveragedNetwork
@@ -94,6 +95,15 @@ class CPSConfig:
                                               # own stream, and weight * (l_1 + l_2) joins the total (reported as `sup_con_loss`).  Needs more than 2 labelled
                                               # images.  None = today's step: nothing of it is entered, launches and tensors are the same
     sup_con_temperature: float = 0.04         # SupConLoss(temperature)
+    unsup_criterion: Optional[str] = None     # recipe v1 only.  "conf_ce": the confidence-weighted soft CPS term of deprecated/train_vq_pt_unet_conf_ce.py:
+                                              # 222-229 -- network k's CPS term becomes crit(labelled predictions, the other's mask) + uw * conf_ce_loss(its
+                                              # unlabelled logits <- the other's unlabelled LOGITS), both directions from one nnf.conf_ce_pair call on the
+                                              # caller's stream (the gradient crosses networks).  None = today's step: nothing of it is entered
+    conf_ce_threshold: float = 0.6            # conf_ce_loss(threshold, threshold_neg, temperature_value): the reference's call uses its defaults
+    conf_ce_threshold_neg: float = 0.0
+    conf_ce_temperature: float = 1.0
+    conf_ce_unreliable_weight: bool = True    # uw = loss.unreliable_weight(the target-side logits, 100 - unsup_loss_drop_percent * (1 - epoch_frac)); False: 1
+    conf_ce_detach_targets: bool = False      # True: no gradient to the network that made the targets (not the reference's)
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -112,6 +122,15 @@ class CPSConfig:
             raise ValueError(f"easy_aug_max_angle must lie in [0, 180], got {self.easy_aug_max_angle!r}")
         if self.sup_con_loss_weight is not None and not float(self.sup_con_temperature) > 0.0:
             raise ValueError(f"sup_con_temperature must be positive, got {self.sup_con_temperature!r}")
+        if self.unsup_criterion not in (None, "conf_ce"):
+            raise ValueError(f"unsup_criterion must be None or 'conf_ce', got {self.unsup_criterion!r}")
+        if self.unsup_criterion is not None:
+            if self.recipe != "v1":
+                raise ValueError("unsup_criterion applies to recipe 'v1': the reference's conf_ce trainer is a single-criterion one")
+            if not float(self.conf_ce_temperature) > 0.0:
+                raise ValueError(f"conf_ce_temperature must be positive, got {self.conf_ce_temperature!r}")
+            if not float(self.conf_ce_threshold_neg) >= 0.0:
+                raise ValueError(f"conf_ce_threshold_neg must be >= 0, got {self.conf_ce_threshold_neg!r}")
         if self.recipe != "v1" and (self.criterion != "dice_loss" or self.class_weight is not None):
             raise ValueError("criterion / class_weight apply to recipe 'v1', the single-criterion recipe; the reference has no weighted or "
                              "focal form of recipe 'v2' (CE + Dice)")
@@ -422,6 +441,8 @@ class CPSTrainer:
         cfg, crt = self.cfg, self.criterion
         if cls_weight is not None or not isinstance(crt, DiceLoss):    # recipe v1 only (cfg.__post_init__)
             return (lambda p, t: self._weighted(p, t, cls_weight)), False
+        if cfg.unsup_criterion is not None:                            # the CPS terms gain a scalar the one-launch combination does not take
+            return crt, False
         if (crt.weight is None and crt.ignore_index is not None and pred.is_cuda and nnf.dice_sums_supported(pred, crt.num_classes)
                 and nnf.py_opt("py_loss_combine", 1) == 1):
             sums = nnf.dice_sums if cfg.recipe == "v1" else nnf.dice_ce_sums
@@ -453,18 +474,42 @@ class CPSTrainer:
             ps2, pu2, pred_2, mask_2 = self._own_mask(sup[1][0], unsup[1][0], kw)
         g.exchange(mask_1, mask_2)
         crit, fused = self._criterion(cls_weight, pred_1)
+        soft = cfg.unsup_criterion is not None                          # the unlabelled half of the CPS terms is _soft_cps's
+        b_l = ps1.shape[0]
         with g.on(0):
-            cps_1, sup_1 = crit(pred_1, mask_2), crit(ps1, l_target)
+            cps_1, sup_1 = (crit(ps1, mask_2[:b_l]) if soft else crit(pred_1, mask_2)), crit(ps1, l_target)
         with g.on(1):
-            cps_2, sup_2 = crit(pred_2, mask_1), crit(ps2, l_target)
+            cps_2, sup_2 = (crit(ps2, mask_1[:b_l]) if soft else crit(pred_2, mask_1)), crit(ps2, l_target)
         g.join()
         g.to_caller(cps_1, sup_1, cps_2, sup_2, ps1, pu2, mask_1, mask_2, score_1, score_2)
+        if soft:
+            g.to_caller(pu1, ps2)
+            cps_1, cps_2 = self._soft_cps(cps_1, cps_2, ps1, ps2, pu1, pu2, kw)
         if cfg.keep_aux:
             self.aux.update(mask_1=mask_1, mask_2=mask_2, pred_sup_1=ps1.detach(), pred_ul_2=pu2.detach())
             if cls_weight is not None or not isinstance(self.criterion, DiceLoss):     # what the criterion arms' terms are restated from
                 self.aux.update(pred_1=pred_1.detach(), pred_2=pred_2.detach(), class_weight=cls_weight)
                 g.to_caller(pred_1, pred_2)
         return fused, ps1, (sup_1, sup_2), (cps_1, cps_2)
+
+    def _soft_cps(self, cps_1, cps_2, ps1, ps2, pu1, pu2, kw):
+        """cfg.unsup_criterion == "conf_ce" -> the two CPS terms with their unlabelled halves added, on the caller's stream after the
+        lanes have joined (the term's gradient reaches both networks): network k's is uw_other * conf_ce_loss(pu_k <- pu_other),
+        uw_other the unreliable weight of the logits that serve as targets (train_vq_pt_unet_conf_ce.py:225-228)."""
+        cfg = self.cfg
+        par = (cfg.conf_ce_threshold, cfg.conf_ce_threshold_neg, cfg.conf_ce_temperature)
+        if nnf.conf_ce_supported(pu1, pu2):
+            l_1, l_2 = nnf.conf_ce_pair(pu1, pu2, *par, cfg.conf_ce_detach_targets)      # one launch forward, one backward, both directions
+        else:
+            l_1 = conf_ce_loss(pu1, pu2, True, *par, detach_targets=cfg.conf_ce_detach_targets)
+            l_2 = conf_ce_loss(pu2, pu1, True, *par, detach_targets=cfg.conf_ce_detach_targets)
+        if cfg.conf_ce_unreliable_weight:
+            uw_1, uw_2 = unreliable_weight(pu1.detach(), kw["percent"]), unreliable_weight(pu2.detach(), kw["percent"])
+        else:
+            uw_1 = uw_2 = torch.ones((), dtype=torch.float32, device=pu1.device)
+        if cfg.keep_aux:                                                # uw_k: of network k's logits, so it weighs the OTHER network's term
+            self.aux.update(conf_ce_1=l_1.detach(), conf_ce_2=l_2.detach(), uw_1=uw_1, uw_2=uw_2, pred_ul_1=pu1.detach(), pred_sup_2=ps2.detach())
+        return cps_1 + uw_2 * l_1, cps_2 + uw_1 * l_2
 
     def _total_loss(self, fused, sup, cps, commit, proto):
         """-> loss and the reported terms.  fused: the whole combination -- terms from their sums, commitment, prototype, total, and

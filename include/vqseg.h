@@ -886,6 +886,44 @@ int vqseg_conf_ce_backward_f(const float* x, int64_t x_stride_b, int64_t x_strid
                              float temperature, int pair, int detach_targets, const double* stats, const float* g_scalar, float* g_x,
                              float* g_t, void* stream);
 
+/* ---------------------------------------------------------------------------------- *
+ * Fully connected CRF refinement of class probabilities (utils/crf.py: DenseCRF; vq_seg_amd.nnf.dense_crf,
+ * vq_seg_amd.utils.crf.DenseCRF, vq_seg_amd.predict.Predictor(crf=...)): mean-field inference with a Potts compatibility and
+ * symmetrically normalised kernels, computed EXACTLY over all pixel pairs of a truncated support -- no lattice, no approximation of
+ * the filter.  Inference only.  Per image, pixels i, j at integer (x, y), c in 2..4 classes:
+ *     rgb      = trunc(clamp(image, 0, 1) * 255)  (the product in f32), integers 0..255;   U = -log(clip(prob, 1e-5, 1))
+ *     k_pos    = exp(-(dx^2 + dy^2) / (2 pos_xy_std^2))                                                 inside |dx|, |dy| <= R_pos
+ *     k_bi     = exp(-(dx^2 + dy^2) / (2 bi_xy_std^2) - |rgb_i - rgb_j|^2 / (2 bi_rgb_std^2))            inside |dx|, |dy| <= R_bi
+ *     R        = ceil(truncate * xy_std) of that kernel (in double); k = 0 outside its support; both include j = i;
+ *                truncate = +inf: full support.  The truncation is part of the definition.
+ *     n_i      = 1 / sqrt(sum_j k(i, j) + 1e-20)  per kernel;      m_i[c] = n_i sum_j k(i, j) n_j Q_j[c]
+ *     E_i      = -U_i + pos_w m_pos,i + bi_w m_bi,i;   Q_i = softmax_c(E_i);   Q^0 = softmax(-U) = clip(prob) / sum_c clip(prob)
+ * All buffers are the caller's, none larger than b * c * h * w elements; internal layout planar: rgb u32 [b][h * w] (r | g << 8 |
+ * b << 16), unary / q [b][c][h * w] f32, norm_pos f32 [h * w] (the same for every image), norm_bi f32 [b][h * w], table f32 [w + h].
+ *
+ * vqseg_crf_prepare_f: image f32 logical (b, 3, h, w) and prob f32 logical (b, c, h, w), each through its own batch / channel / pixel
+ * strides in ELEMENTS as vqseg_resize_argmax_f takes them (planar or interleaved, rows dense) -> rgb, unary, q0 and, when
+ * iter_max > 0, both kernels' n_i: the positional one from its separable row and column sums (table, taken in double), the bilateral
+ * one from an all-pairs pass of its own.  iter_max = 0: norm_pos, norm_bi and table may be NULL and are not written.
+ *
+ * vqseg_crf_step_f: one update q_in -> q_out (two different buffers: ping-pong) for all b images in one launch; energies != 0 writes
+ * E instead of Q (the last launch of a caller that wants logits: softmax(E) = Q).  A workgroup owns 8 x 64 pixels i and streams the
+ * pixels j of its window through LDS; it touches the pairs inside the larger support plus the tile's overhang, never all (h w)^2; both
+ * kernels share that one pass, the positional one costing an exponential only inside its own window.  No atomics, fixed summation
+ * order (j rows ascending, columns ascending): two calls agree bit for bit.  Colour differences and squared distances are exact
+ * integers; the weight is one v_exp_f32.
+ *
+ * Errors (VQSEG_EINVAL before anything touches a device): null pointers, c outside 2..4, non-positive b / h / w, b > 65535, a side
+ * above 2048, stds that are not in (0, 1e18], iter_max < 0, truncate < 0 or NaN, non-finite weights, q_in == q_out.
+ * ---------------------------------------------------------------------------------- */
+int vqseg_crf_prepare_f(const float* image, int64_t image_stride_b, int64_t image_stride_c, int64_t image_stride_px, const float* prob,
+                        int64_t prob_stride_b, int64_t prob_stride_c, int64_t prob_stride_px, int b, int c, int h, int w, int iter_max,
+                        double bi_xy_std, double bi_rgb_std, double pos_xy_std, double truncate, uint32_t* rgb, float* unary, float* q0,
+                        float* norm_pos, float* norm_bi, float* table, void* stream);
+int vqseg_crf_step_f(const uint32_t* rgb, const float* unary, const float* norm_pos, const float* norm_bi, const float* q_in, float* q_out,
+                     int b, int c, int h, int w, double bi_w, double bi_xy_std, double bi_rgb_std, double pos_w, double pos_xy_std,
+                     double truncate, int energies, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,8 @@ SYMBOLS = {
                                         c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "vqseg_conf_ce_backward_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p] + [c_int64] * 3 + [c_int, c_int, c_int64, c_float, c_float, c_float,
                                          c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vqseg_crf_prepare_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p] + [c_int64] * 3 + [c_int] * 5 + [c_double] * 4 + [c_void_p] * 7),
+    "vqseg_crf_step_f": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_double] * 6 + [c_int, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -20,6 +20,10 @@ nothing changes: no extra launch, the same dict.
 `window` (with fused; `stride`, `blend`, `window_batch`, `net_size` as predict.Predictor takes them) scores tiled prediction: the
 network runs on windows of the images and one `nnf.merge_argmax` call blends them and counts.  The images and masks of a batch must
 then have the same size (e.g. BaseDataset(resize=None)); the sheets of `visualize` are not built for it.
+
+`crf` (with fused; a utils.crf.DenseCRF or True for its defaults) scores the dense-CRF refinement of the prediction at the mask size,
+as deprecated/test _crf.py does between the forward and the metrics: predict.Predictor(crf=...).refined, then the counts from one
+`nnf.resize_argmax` call on the refined energies.  Not built with `window` or `visualize`.
 """
 from typing import Dict, Iterable, Tuple
 
@@ -61,7 +65,7 @@ def _detail_sheets(img, logits, flips, target, num_classes):
 @torch.no_grad()
 def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], num_classes: int,
               device=None, amp_dtype=None, fused: bool = False, tta=None, visualize=None, window=None, stride=None,
-              blend: str = "linear", window_batch=None, net_size=None) -> Dict[str, object]:
+              blend: str = "linear", window_batch=None, net_size=None, crf=None) -> Dict[str, object]:
     """batches yields (images (N, 3, H, W) float in [0, 1], labels (N, Hm, Wm) int class ids)."""
     if window is not None and not fused:
         raise ValueError("test_loop: window needs fused=True (the windows are blended inside the fused merge + arg-max)")
@@ -71,8 +75,12 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
         raise ValueError("test_loop: tta needs fused=True (the views are averaged inside the fused resize + arg-max)")
     if visualize is not None and not fused:
         raise ValueError("test_loop: visualize needs fused=True (the sheets are drawn from the fused path's views)")
+    if crf is not None and not fused:
+        raise ValueError("test_loop: crf needs fused=True (the refined energies are scored by the fused arg-max + counts)")
+    if crf is not None and visualize is not None:
+        raise ValueError("test_loop: visualize is not built for CRF scoring (crf=...)")
     predictor = Predictor(model, num_classes, amp_dtype=amp_dtype, tta=tta or ("none",), window=window, stride=stride, blend=blend,
-                          window_batch=window_batch, net_size=net_size) if fused else None
+                          window_batch=window_batch, net_size=net_size, crf=crf) if fused else None
     views = predictor.views if fused else None
     was_training = model.training
     model.eval()
@@ -91,6 +99,10 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
                 logits, flips, grid = predictor.tiled_views(img)
                 conf = nnf.merge_argmax(logits, grid, flips=flips, blend=blend, target=target)[2]
                 hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (target.shape[-2] * target.shape[-1])
+            elif fused and predictor.crf is not None:
+                size = tuple(target.shape[-2:])
+                conf = nnf.resize_argmax(predictor.refined(img, size), size, target=target)[2]
+                hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (size[0] * size[1])
             elif fused:
                 logits, flips = views(img)
                 conf = nnf.resize_argmax(logits, tuple(target.shape[-2:]), flips=flips, target=target)[2]

@@ -2298,3 +2298,111 @@ def render_sheet(panels, size, num_classes, palette, image=None, pred=None, targ
         pred = pred.detach().contiguous()
     return _hip.render_sheet(out, rows, (b, ho, wo), num_classes, palette, fill=fill, image=image, pred=pred, target=target, alpha=alpha,
                              box2=half, cols=cols)
+
+
+# ------------------------------------------------------------------------------------------------
+# dense-CRF refinement of class probabilities: exact mean-field on a truncated support (vqseg_crf_prepare_f, vqseg_crf_step_f)
+# ------------------------------------------------------------------------------------------------
+CRF_MAX_SIDE = 2048                           # include/vqseg.h: squared pixel distances stay exact f32 integers
+CRF_DEFAULTS = dict(iter_max=10, bi_w=7.0, bi_xy_std=50.0, bi_rgb_std=4.0, pos_w=3.0, pos_xy_std=3.0, truncate=4.0)     # utils/crf.py:6
+
+
+def crf_settings(iter_max=10, bi_w=7.0, bi_xy_std=50.0, bi_rgb_std=4.0, pos_w=3.0, pos_xy_std=3.0, truncate=4.0, who="dense_crf"):
+    """the checked settings of a dense CRF as (iter_max, bi_w, bi_xy_std, bi_rgb_std, pos_w, pos_xy_std, truncate); truncate None
+    (full support) comes back as +inf.  One rule for nnf.dense_crf and utils.crf.DenseCRF."""
+    if isinstance(iter_max, bool) or int(iter_max) != iter_max or int(iter_max) < 0:
+        raise ValueError(f"{who}: iter_max must be an integer >= 0, got {iter_max!r}")
+    vals = [float(bi_w), float(bi_xy_std), float(bi_rgb_std), float(pos_w), float(pos_xy_std)]
+    for name, v in zip(("bi_xy_std", "bi_rgb_std", "pos_xy_std"), (vals[1], vals[2], vals[4])):
+        if not 0.0 < v <= 1e18:
+            raise ValueError(f"{who}: {name} must be positive (and at most 1e18), got {v}")
+    for name, v in zip(("bi_w", "pos_w"), (vals[0], vals[3])):
+        if not abs(v) <= 1e18:
+            raise ValueError(f"{who}: {name} must be finite, got {v}")
+    t = float("inf") if truncate is None else float(truncate)
+    if not t >= 0.0:
+        raise ValueError(f"{who}: truncate must be >= 0 or None (full support), got {truncate!r}")
+    return (int(iter_max), *vals, t)
+
+
+def dense_crf_supported(images, probs) -> bool:
+    """what the kernels take: float32 GPU tensors images (B, 3, H, W) and probs (B, C, H, W) of one batch, size and device, 2..4
+    classes, sides up to CRF_MAX_SIDE, at most 65535 images"""
+    return (torch.is_tensor(images) and torch.is_tensor(probs) and images.is_cuda and probs.device == images.device and images.dim() == 4
+            and probs.dim() == 4 and images.dtype == torch.float32 and probs.dtype == torch.float32 and images.shape[1] == 3
+            and 2 <= probs.shape[1] <= 4 and images.shape[0] == probs.shape[0] and images.shape[2:] == probs.shape[2:]
+            and 1 <= probs.shape[0] <= 65535 and 1 <= probs.shape[2] <= CRF_MAX_SIDE and 1 <= probs.shape[3] <= CRF_MAX_SIDE)
+
+
+def _crf_dense(v):
+    """dense NCHW or channels_last storage and its (batch, channel, pixel) strides, stated from the layout"""
+    v = v.detach()
+    if not (v.is_contiguous() or v.is_contiguous(memory_format=torch.channels_last)):
+        v = v.contiguous()
+    b, c, h, w = v.shape
+    return v, ((c * h * w, h * w, 1) if v.is_contiguous() else (c * h * w, 1, c))
+
+
+def dense_crf(images, probs, iter_max=10, bi_w=7.0, bi_xy_std=50.0, bi_rgb_std=4.0, pos_w=3.0, pos_xy_std=3.0, truncate=4.0, out="prob"):
+    """Fully connected CRF refinement (utils/crf.py: DenseCRF) of class probabilities `probs` (B, C, H, W) under `images` (B, 3, H, W)
+    in [0, 1], both float32 on the GPU, NCHW-contiguous or channels_last: `iter_max` mean-field updates with a Potts compatibility
+    and symmetrically normalised kernels, computed exactly over all pixel pairs with |dx|, |dy| <= R = ceil(truncate * xy_std) of
+    each kernel (`truncate` None: all pairs) -- the contract of include/vqseg.h, one prepare launch and one step launch per
+    iteration.  `out` "prob": Q (B, C, H, W), NCHW-contiguous; "logits": the last update's energies E, softmax(E) = Q (with
+    iter_max = 0: -U = log of the clipped probabilities), which resize_argmax takes at equal size for labels, top probability and
+    counts.  No gradient flows.  There is no CPU form here (utils.crf.DenseCRF has one)."""
+    E = _hip.HipLibraryError
+    if out not in ("prob", "logits"):
+        raise ValueError(f"dense_crf: out is 'prob' or 'logits', got {out!r}")
+    iters, bi_w, bi_xy_std, bi_rgb_std, pos_w, pos_xy_std, trunc = crf_settings(iter_max, bi_w, bi_xy_std, bi_rgb_std, pos_w, pos_xy_std, truncate)
+    if not (torch.is_tensor(images) and torch.is_tensor(probs) and images.dim() == 4 and probs.dim() == 4):
+        raise E("dense_crf: images must be a (B, 3, H, W) tensor and probs a (B, C, H, W) tensor")
+    b, c, h, w = probs.shape
+    if images.shape[1] != 3 or images.shape[0] != b or tuple(images.shape[2:]) != (h, w):
+        raise E(f"dense_crf: images must be (B, 3, H, W) of the probabilities' batch and size, got {tuple(images.shape)} and {tuple(probs.shape)}")
+    if not 2 <= c <= 4:
+        raise E(f"dense_crf: 2..4 classes, got {c}")
+    if min(b, h, w) < 1 or b > 65535 or max(h, w) > CRF_MAX_SIDE:
+        raise E(f"dense_crf: 1..65535 images with sides of 1..{CRF_MAX_SIDE}, got {tuple(probs.shape)}")
+    if images.device != probs.device:
+        raise E(f"dense_crf: images and probs must be on one device, got {images.device} and {probs.device}")
+    state = _crf_prepare(images, probs, iters, bi_xy_std, bi_rgb_std, pos_xy_std, trunc)
+    q, unary = state[0], state[2]
+    if iters == 0:
+        return q[0] if out == "prob" else unary.neg_()
+    for it in range(iters):
+        _crf_step(state, it & 1, bi_w, bi_xy_std, bi_rgb_std, pos_w, pos_xy_std, trunc, out == "logits" and it == iters - 1)
+    return q[iters & 1]
+
+
+def _crf_prepare(images, probs, iters, bi_xy_std, bi_rgb_std, pos_xy_std, trunc):
+    """one vqseg_crf_prepare_f launch -> (q ping-pong pair (q[0] = Q0), colours, unary, positional norm, bilateral norm): the buffers
+    the step launches work on, none larger than the probabilities"""
+    b, c, h, w = probs.shape
+    images, istr = _crf_dense(images)
+    probs, pstr = _crf_dense(probs)
+    n, dev = h * w, probs.device
+    ip, pp = _strided_f32(images, "images", b * 3 * n), _strided_f32(probs, "probabilities", b * c * n)
+    if dev.type != "cuda":                       # before any buffer is asked for on a device that has no HIP path
+        _launch("vqseg_crf_prepare_f", dev, ip, *istr, pp, *pstr, b, c, h, w, iters, bi_xy_std, bi_rgb_std, pos_xy_std, trunc,
+                None, None, None, None, None, None)
+    rgb = torch.empty((b, n), dtype=torch.int32, device=dev)
+    unary = torch.empty((b, c, h, w), dtype=torch.float32, device=dev)
+    q = [torch.empty((b, c, h, w), dtype=torch.float32, device=dev) for _ in range(2 if iters else 1)]          # ping-pong
+    npos = torch.empty(n, dtype=torch.float32, device=dev) if iters else None
+    nbi = torch.empty((b, n), dtype=torch.float32, device=dev) if iters else None
+    table = torch.empty(h + w, dtype=torch.float32, device=dev) if iters else None
+    _launch("vqseg_crf_prepare_f", dev, ip, *istr, pp, *pstr, b, c, h, w, iters, bi_xy_std, bi_rgb_std, pos_xy_std, trunc,
+            _T(rgb, "colours", dtype=torch.int32, numel=b * n), _f32(unary, "unary", b * c * n), _f32(q[0], "q", b * c * n),
+            _f32(npos, "positional norm", n), _f32(nbi, "bilateral norm", b * n), _f32(table, "positional table", h + w))
+    return q, rgb, unary, npos, nbi
+
+
+def _crf_step(state, at, bi_w, bi_xy_std, bi_rgb_std, pos_w, pos_xy_std, trunc, energies):
+    """one vqseg_crf_step_f launch: q[at] -> q[1 - at] (E instead of Q with `energies`)"""
+    q, rgb, unary, npos, nbi = state
+    b, c, h, w = unary.shape
+    n = h * w
+    _launch("vqseg_crf_step_f", unary.device, _T(rgb, "colours", dtype=torch.int32, numel=b * n), _f32(unary, "unary", b * c * n),
+            _f32(npos, "positional norm", n), _f32(nbi, "bilateral norm", b * n), _f32(q[at], "q in", b * c * n),
+            _f32(q[1 - at], "q out", b * c * n), b, c, h, w, bi_w, bi_xy_std, bi_rgb_std, pos_w, pos_xy_std, trunc, int(bool(energies)))

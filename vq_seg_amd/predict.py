@@ -19,6 +19,16 @@ probabilities instead of logits.
 
     Predictor(model, 3, window=512)(images).label                      # stride 256, "linear" blend, at the images' own size
     Predictor([m1, m2], 3, tta=("none", "hflip"), window=(512, 640), stride=384, window_batch=8)(images, want_confidence=True)
+
+Dense-CRF refinement, `crf=...` (a utils.crf.DenseCRF, or True for the reference's defaults; untiled mode only): the views' logits are
+resized to `size` (nnf.upsample_bilinear, align_corners=False), un-flipped, averaged and passed through softmax; the images are
+resized the same way if `size` is not their own; `nnf.dense_crf(out="logits")` refines the probabilities under the images
+(vqseg_crf_prepare_f, vqseg_crf_step_f) and `nnf.resize_argmax` at equal size takes labels, top probability and counts from the
+refined energies.  Not built: the CRF under tiled prediction, and the reference script's order "CRF at the network's size, then
+resize Q" -- which `size=` equal to the network's gives.
+
+    Predictor(model, 3, crf=True)(images).label
+    Predictor(model, 3, crf=DenseCRF(iter_max=5, truncate=None))(images, size=(966, 1296), want_confidence=True)
 """
 from collections import namedtuple
 from typing import Iterable, Iterator, List, Optional, Sequence, Tuple, Union
@@ -33,6 +43,25 @@ TTA_FLIPS = {"none": 0, "hflip": 1, "vflip": 2, "hvflip": 3}   # test-time view 
 Prediction = namedtuple("Prediction", "label confidence")      # (N, H, W) uint8 class ids; (N, H, W) f32 top probability or None
 
 
+def _as_crf(crf):
+    """None, a utils.crf.DenseCRF, or True for one with the reference's defaults"""
+    from .utils.crf import DenseCRF
+    if crf is None or crf is False:
+        return None
+    if crf is True:
+        return DenseCRF()
+    if not isinstance(crf, DenseCRF):
+        raise TypeError(f"crf must be a utils.crf.DenseCRF, True or None, got {type(crf).__name__}")
+    return crf
+
+
+def _resize(x: torch.Tensor, size) -> torch.Tensor:
+    """bilinear, align_corners=False: the HIP resize kernel on the GPU, F.interpolate elsewhere"""
+    if x.is_cuda:
+        return nnf.upsample_bilinear(x, size=tuple(size), align_corners=False)
+    return torch.nn.functional.interpolate(x, tuple(size), mode="bilinear", align_corners=False)
+
+
 class Predictor:
     """`models`: one nn.Module or a sequence (two: the CPS ensemble); `tta`: a selection of "none", "hflip", "vflip", "hvflip";
     len(models) * len(tta) must be 1, 2 or 4.  `amp_dtype`: the forwards run under torch.autocast on the GPU (None: fp32).
@@ -42,10 +71,10 @@ class Predictor:
     window, if not the window itself: the windows are resized bilinearly on the way in and their logits on the way out) and
     `window_batch` (how many windows go through one forward, default all of a view: it bounds the forward's activations).  The
     logits of ALL windows are held until the merge: B * T * C * lh * lw * 4 bytes per view (B images, T windows each, C classes,
-    lh x lw logits per window)."""
+    lh x lw logits per window).  `crf`: a utils.crf.DenseCRF, or True for its defaults, refines the prediction (untiled mode)."""
 
     def __init__(self, models: Union[nn.Module, Sequence[nn.Module]], num_classes: int, amp_dtype=None, tta: Sequence[str] = ("none",),
-                 device=None, window=None, stride=None, blend: str = "linear", window_batch: Optional[int] = None, net_size=None):
+                 device=None, window=None, stride=None, blend: str = "linear", window_batch: Optional[int] = None, net_size=None, crf=None):
         self.models: List[nn.Module] = [models] if isinstance(models, nn.Module) else list(models)
         self.tta: Tuple[str, ...] = (tta,) if isinstance(tta, str) else tuple(tta)
         unknown = [t for t in self.tta if t not in TTA_FLIPS]
@@ -68,6 +97,9 @@ class Predictor:
             raise ValueError(f"window_batch must be positive, got {window_batch}")
         self.window, self.stride, self.blend, self.net_size = window, stride, blend, net_size
         self.window_batch = None if window_batch is None else int(window_batch)
+        self.crf = _as_crf(crf)
+        if self.crf is not None and window is not None:
+            raise ValueError("crf together with window: the CRF under tiled prediction is not built")
 
     def _forward(self, model: nn.Module, x: torch.Tensor) -> torch.Tensor:
         """fp32 logits of one forward, under autocast on the GPU if asked for"""
@@ -126,6 +158,26 @@ class Predictor:
                 flips.append(code)
         return logits, flips
 
+    def refined(self, images: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+        """crf mode -> the refined energies (N, C, Ho, Wo) fp32 at `size`: softmax of the views' mean logits there, then the dense
+        CRF under the images brought to the same size.  The models' modes are the caller's business."""
+        if self.crf is None:
+            raise ValueError("refined: this Predictor has no crf")
+        if self.device is not None:
+            images = images.to(self.device)
+        logits, flips = self.views(images)
+        acc = None
+        for v, code in zip(logits, flips):
+            r = v if tuple(v.shape[-2:]) == tuple(size) else _resize(v, size)
+            r = r.flip(nnf.FLIP_DIMS[code]) if code else r
+            acc = r if acc is None else acc + r
+        if len(logits) > 1:
+            acc = acc * (1.0 / len(logits))
+        x = images.to(acc.device).float()
+        if tuple(x.shape[-2:]) != tuple(size):
+            x = _resize(x, size)
+        return self.crf.batch(x, torch.softmax(acc, dim=1), out="logits")
+
     @torch.no_grad()
     def __call__(self, images: torch.Tensor, size: Optional[Sequence[int]] = None, want_confidence: bool = False) -> Prediction:
         """images (N, 3, H, W) -> Prediction(label (N, Ho, Wo) uint8, confidence (N, Ho, Wo) f32 | None); size None: (H, W).
@@ -139,6 +191,8 @@ class Predictor:
             if self.window is not None:
                 logits, flips, grid = self.tiled_views(images)
                 label, top, _ = nnf.merge_argmax(logits, grid, flips=flips, blend=self.blend, want_top=want_confidence)
+            elif self.crf is not None:
+                label, top, _ = nnf.resize_argmax(self.refined(images, size), size, want_top=want_confidence)
             else:
                 logits, flips = self.views(images)
                 label, top, _ = nnf.resize_argmax(logits, size, flips=flips, want_top=want_confidence)
@@ -155,7 +209,7 @@ class Predictor:
         launch (utils.visualize.render_sheet; vqseg_render_sheet_u8 on the GPU) from the labels, `targets` (N, Ht, Wt) at any size
         and the images themselves.  `panels` default: image | target | pred | 20 px white | mix_pred (without `targets`: no target
         panel); size None: (H, W).  Tiled mode: the merged labels of __call__ are what the sheet shows (`size`: None or the
-        images' own)."""
+        images' own).  crf mode: likewise the refined labels of __call__."""
         from .utils.visualize import GAP, render_sheet
         size = self._own_size(images, size) if self.window is not None else \
             tuple(images.shape[-2:]) if size is None else (int(size[0]), int(size[1]))
@@ -168,13 +222,16 @@ class Predictor:
             if self.window is not None:
                 logits, flips, grid = self.tiled_views(images)
                 label = nnf.merge_argmax(logits, grid, flips=flips, blend=self.blend)[0]
+            elif self.crf is not None:
+                logits = [self.refined(images, size)]
+                label = nnf.resize_argmax(logits, size)[0]
             else:
                 logits, flips = self.views(images)
         finally:
             for m, was_training in zip(self.models, modes):
                 m.train(was_training)
         dev = logits[0].device
-        if self.window is not None:
+        if self.window is not None or self.crf is not None:
             return render_sheet(panels, images.to(dev), label, None if targets is None else targets.to(dev), size=size, palette=palette,
                                 alpha=alpha, half=half, num_classes=self.num_classes)
         return render_sheet(panels, images.to(dev), logits, None if targets is None else targets.to(dev), size=size, palette=palette, alpha=alpha,
@@ -189,8 +246,8 @@ class Predictor:
 
 def predict_batches(models, batches: Iterable, num_classes: int, amp_dtype=None, tta: Sequence[str] = ("none",), device=None,
                     size: Optional[Sequence[int]] = None, want_confidence: bool = False, window=None, stride=None, blend: str = "linear",
-                    window_batch: Optional[int] = None, net_size=None) -> Iterator[Prediction]:
-    """Predictor(models, num_classes, amp_dtype, tta, device, window, stride, blend, window_batch, net_size)
+                    window_batch: Optional[int] = None, net_size=None, crf=None) -> Iterator[Prediction]:
+    """Predictor(models, num_classes, amp_dtype, tta, device, window, stride, blend, window_batch, net_size, crf)
     .predict_batches(batches, size, want_confidence)"""
     return Predictor(models, num_classes, amp_dtype=amp_dtype, tta=tta, device=device, window=window, stride=stride, blend=blend,
-                     window_batch=window_batch, net_size=net_size).predict_batches(batches, size, want_confidence)
+                     window_batch=window_batch, net_size=net_size, crf=crf).predict_batches(batches, size, want_confidence)

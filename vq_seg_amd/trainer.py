@@ -626,15 +626,16 @@ class CPSTrainer:
         return self.teachers if which == "teacher" else self.models
 
     def evaluate(self, batches, which: str = "student", index: int = 0, fused: bool = False, visualize=None, window=None, stride=None,
-                 blend: str = "linear", window_batch=None, net_size=None):
+                 blend: str = "linear", window_batch=None, net_size=None, crf=None):
         """evaluate.test_loop on network `index` of the pair: which="student" scores the trained weights, which="teacher" their
         exponential moving average (cfg.ema_decay), under cfg.amp_dtype.  `batches` yields (images, labels).  `fused`: resize, arg-max
         and confusion counts in one kernel (evaluate.test_loop's opt-in; the same numbers).  `visualize` (with fused): a callable
         (batch_index, viz_v1, viz_v2) that receives the test script's two uint8 sheets per batch (evaluate.test_loop).  `window`
-        (with fused; `stride`, `blend`, `window_batch`, `net_size`): tiled scoring, as predict.Predictor(window=...) predicts."""
+        (with fused; `stride`, `blend`, `window_batch`, `net_size`): tiled scoring, as predict.Predictor(window=...) predicts.  `crf`
+        (with fused; a utils.crf.DenseCRF or True): the dense-CRF refinement is scored, as predict.Predictor(crf=...) predicts."""
         model = self._networks(which)[index]
         return test_loop(model, batches, self.cfg.num_classes, device=self.device, amp_dtype=self.cfg.amp_dtype, fused=fused, visualize=visualize,
-                         window=window, stride=stride, blend=blend, window_batch=window_batch, net_size=net_size)
+                         window=window, stride=stride, blend=blend, window_batch=window_batch, net_size=net_size, crf=crf)
 
     @torch.no_grad()
     def example_image(self, l_input, l_target, ul_input, which: str = "student", index: int = 0, half: bool = True):
@@ -658,15 +659,17 @@ class CPSTrainer:
                                 resize_factor=0.5 if half else None)
 
     def predict(self, images, size=None, which: str = "student", index: int = 0, ensemble: bool = False, tta=("none",),
-                want_confidence: bool = False, window=None, stride=None, blend: str = "linear", window_batch=None, net_size=None) -> Prediction:
+                want_confidence: bool = False, window=None, stride=None, blend: str = "linear", window_batch=None, net_size=None,
+                crf=None) -> Prediction:
         """Class maps of `images` (N, 3, H, W) at `size` (None: their own): predict.Predictor on network `index` of the pair `which`
         names, or with `ensemble` on both of them (mean of the two networks' logits), times the flipped views of `tta`, under
         cfg.amp_dtype.  `window` (with `stride`, `blend`, `window_batch`, `net_size`): tiled prediction at the images' own size
-        (predict.Predictor).  -> Prediction(label (N, Ho, Wo) uint8, confidence (N, Ho, Wo) f32 | None)."""
+        (predict.Predictor).  `crf` (a utils.crf.DenseCRF or True; not with `window`): dense-CRF refinement of the prediction.
+        -> Prediction(label (N, Ho, Wo) uint8, confidence (N, Ho, Wo) f32 | None)."""
         nets = self._networks(which)
         return Predictor(list(nets) if ensemble else nets[index], self.cfg.num_classes, amp_dtype=self.cfg.amp_dtype, tta=tta,
                          device=self.device, window=window, stride=stride, blend=blend, window_batch=window_batch,
-                         net_size=net_size)(images, size=size, want_confidence=want_confidence)
+                         net_size=net_size, crf=crf)(images, size=size, want_confidence=want_confidence)
 
     def _weighted(self, pred, target, weight):
         """the configured criterion with this step's class weights: the module's own parameters (ignore index 255, the focal

@@ -142,15 +142,16 @@ def variant_of(case):
 
 
 def geometry(case):
-    return CASES[case][:11]
+    """the eleven geometry fields of a named case; a tuple (tests/layer_cases.py's census rows) is its own geometry"""
+    return tuple(case[:11]) if isinstance(case, tuple) else CASES[case][:11]
 
 
 def options(case):
-    return dict(CASES[case][11])
+    return {} if isinstance(case, tuple) else dict(CASES[case][11])
 
 
 def kind(case):
-    return CASES[case][0]
+    return geometry(case)[0]
 
 
 def out_size(case):

@@ -39,6 +39,7 @@ The bound for fp32 outputs, elementwise, with no term from the code under test:
   * accumulate = 1: y = prev + gradient in fp32 adds 2^-23 |prev + ref|.
 """
 import functools
+import zlib
 
 import torch
 import torch.nn.functional as F
@@ -107,34 +108,41 @@ VARIANTS = {
 }
 
 
+def _row(case):
+    """the twelve fields of a named case; a tuple (tests/layer_cases.py's census rows) is its own row"""
+    return case if isinstance(case, tuple) else CASES[case]
+
+
 def variant_of(case):
     (vid,) = [v for v, cs in VARIANTS.items() if case in cs]
     return vid
 
 
 def kind(case):
-    return CASES[case][0]
+    return _row(case)[0]
 
 
 def fast(case):
-    return case[0] in "GV"
+    return not isinstance(case, tuple) and case[0] in "GV"
 
 
 def out_size(case):
     """(ho, wo) of the forward layer"""
-    _kind, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    _kind, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
 
 
 def grad_grid(case):
     """(rows, columns, padding of the launched convolution) of a data-gradient case's output grid: the input grid of a stride-1
     zero-padded layer, else the PADDED input grid (reflect: folded afterwards; stride 2 with zero padding: cropped)"""
-    _kind, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    _kind, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     padded = reflect or stride == 2
     return (h + 2 * pad, w + 2 * pad, k - 1) if padded else (h, w, k - 1 - pad)
 
 
 def _seed(case):
+    if isinstance(case, tuple):
+        return 40000 + zlib.crc32(repr(case).encode()) % 50000
     return 7000 + 31 * sorted(CASES).index(case)
 
 
@@ -154,7 +162,7 @@ def full_mantissa(seed, shape):
 def operands(case):
     """fwd: (x [n, h, w, cin], w [cout, cin, k, k]); dgrad: (gy [n, ho, wo, cout], w); wgrad: (x, gy, prev [cout, cin, k, k] or None).
     fp32; the fast cases hold bf16 values only."""
-    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     cin = c1 + c2
     ho, wo = out_size(case)
     s = _seed(case)
@@ -178,7 +186,7 @@ def _unfold_rows(xp, k, stride):
 
 def patches(case, x):
     """the forward layer's im2col matrix [M, taps * cin] of x [n, h, w, cin] (any float dtype)"""
-    _kind, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    _kind, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     xp = x.permute(0, 3, 1, 2)
     if pad:
         xp = F.pad(xp, (pad,) * 4, mode="reflect" if reflect else "constant")
@@ -187,7 +195,7 @@ def patches(case, x):
 
 def grad_patches(case, gy):
     """the data-gradient launch's im2col matrix [grid pixels, taps * cout] of gy [n, ho, wo, cout]: zero-dilated for stride 2"""
-    _kind, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    _kind, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     g = gy.permute(0, 3, 1, 2)
     if stride == 2:
         d = torch.zeros(n, cout, 2 * g.shape[2] - 1, 2 * g.shape[3] - 1, dtype=gy.dtype)
@@ -200,7 +208,7 @@ def grad_patches(case, gy):
 
 def gemm(case):
     """(A [rows, K], B [K, columns]) in the operands' dtype (fp32)"""
-    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     ops = operands(case)
     if knd == "fwd":
         return patches(case, ops[0]), ops[1].permute(2, 3, 1, 0).reshape(-1, cout).contiguous()
@@ -225,7 +233,7 @@ def to_rows(case, gw):
 @functools.lru_cache(maxsize=None)
 def autograd_reference(case):
     """the same gradient from autograd in fp64 on the explicitly padded input, in the reference's layout (dgrad, wgrad)"""
-    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     cin = c1 + c2
     ops = operands(case)
     if knd == "dgrad":
@@ -243,7 +251,7 @@ def autograd_reference(case):
 
 def contraction(case):
     """K of the bound: an int, or for a 3x3 stride-2 data gradient a [rows, 1] tensor (taps of the pixel's parity class x channels)"""
-    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     if knd == "wgrad":
         ho, wo = out_size(case)
         m = n * ho * wo
@@ -286,7 +294,7 @@ def worst(y, ref, S, K, prev=None):
 
 def stages(case):
     """the K stages as (first column, one past the last): per tap 32-channel chunks, the last one short; weight gradient: 32 pixels"""
-    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     if knd == "wgrad":
         ho, wo = out_size(case)
         m = n * ho * wo
@@ -297,7 +305,7 @@ def stages(case):
 
 def second_source(case):
     """bool mask over (tap, channel) columns: the channels of the second concat source; None without a concat"""
-    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = CASES[case]
+    knd, n, h, w, c1, c2, cout, k, stride, pad, reflect, acc = _row(case)
     if not c2 or knd == "dgrad":
         return None
     return (torch.arange(c1 + c2) >= c1).repeat(k * k)

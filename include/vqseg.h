@@ -924,6 +924,52 @@ int vqseg_crf_step_f(const uint32_t* rgb, const float* unary, const float* norm_
                      int b, int c, int h, int w, double bi_w, double bi_xy_std, double bi_rgb_std, double pos_w, double pos_xy_std,
                      double truncate, int energies, void* stream);
 
+/* ---------------------------------------------------------------------------------- *
+ * SLIC superpixels and the mean over the segments of a label map (deprecated/train_slic.py:44-69,152-160; vq_seg_amd.nnf.slic,
+ * vq_seg_amd.nnf.segment_mean, vq_seg_amd.utils.superpixel, CPSConfig.superpixel_mean, predict.Predictor(superpixels=...)).  The
+ * algorithm is this project's own statement of SLIC in its gSLIC (gather) form; no parity with fast_slic or skimage is claimed.
+ * fp32 throughout, labels int32, one launch for the whole batch.
+ *
+ * Colour: image f32 logical (b, 3, h, w) in [0, 1] (not quantised), sRGB -> CIELAB per pixel:
+ *     lin(v) = ((v + 0.055) / 1.055)^2.4 above 0.04045, else v / 12.92
+ *     X = (0.412453 r + 0.357580 g + 0.180423 b) / 0.95047;  Y = 0.212671 r + 0.715160 g + 0.072169 b;
+ *     Z = (0.019334 r + 0.119193 g + 0.950227 b) / 1.08883;   f(t) = cbrt(t) above 0.008856, else 7.787 t + 16 / 116
+ *     L = 116 f(Y) - 16;  a = 500 (f(X) - f(Y));  b = 200 (f(Y) - f(Z))                          lab: planar f32 [b][3][h * w]
+ * Grid: gy x gx cells (1 <= gy <= h, 1 <= gx <= w; the caller derives them from the component count), cluster (i, j) has index
+ * i * gx + j; centers f32 [b][gy * gx][5] = (L, a, b, y, x).  A pixel's home cell is (y * gy / h, x * gx / w) in integers.
+ *
+ * vqseg_slic_lab_f: lab of every pixel, and the initial centre of every cluster: the Lab value and the coordinates of pixel
+ * (floor((i + 1/2) h / gy), floor((j + 1/2) w / gx)).  The image through batch / channel / pixel strides in ELEMENTS (planar or
+ * interleaved, rows dense).
+ * vqseg_slic_assign_f: labels[p] = the cluster of smallest D = |Lab_p - c_Lab|^2 + spatial_weight ((y - c_y)^2 + (x - c_x)^2) among the
+ * clusters of the 3 x 3 cells around p's home cell that exist; ties go to the lowest cluster index; a pixel whose distances are
+ * all NaN gets its home cell.  spatial_weight = (compactness / S)^2, S = sqrt(h w / num_components).  A gather, no atomics.
+ * vqseg_slic_update_f: centers[k] = the mean of (L, a, b, y, x) over the pixels labelled k among those of the 3 x 3 cells around
+ * cell k (where an assignment of this grid can put them); a cluster without pixels keeps its centre, bit for bit.  Summed in a fixed
+ * order, no atomics: two calls agree bit for bit.
+ *
+ * vqseg_segment_sums_f: sums f32 [b][k][c] and counts i32 [b][k] of x f32 logical (b, c, hw) over the pixels of each label, per image,
+ * for ANY label map; both tables are zeroed first.  A label outside [0, k) is not counted and never addressed.
+ * vqseg_segment_broadcast_f: y[b, :, p] = sums[b, l, :] / counts[b, l] with l = labels[b, p]; y = x where l lies outside [0, k).  x and
+ * y each through their own strides.  Applied to sums of x this is the segment mean, a symmetric projection: its adjoint is itself
+ * (the backward pass is the same two launches on the incoming gradient).  The sums use one float atomic per run of equal labels
+ * inside a wave, so their last bits can differ between calls; the output is exactly constant within a segment in every call.
+ *
+ * Errors (VQSEG_EINVAL before anything touches a device): null pointers, non-positive sizes, b > 65535 or a side above 4096 (slic),
+ * a grid outside 1..h x 1..w, a spatial_weight that is negative or not finite, c > 1024, a layout that is neither planar nor
+ * interleaved.
+ * ---------------------------------------------------------------------------------- */
+int vqseg_slic_lab_f(const float* image, int64_t image_stride_b, int64_t image_stride_c, int64_t image_stride_px, int b, int h, int w, int gy,
+                     int gx, float* lab, float* centers, void* stream);
+int vqseg_slic_assign_f(const float* lab, const float* centers, int b, int h, int w, int gy, int gx, float spatial_weight, int32_t* labels,
+                        void* stream);
+int vqseg_slic_update_f(const float* lab, const int32_t* labels, int b, int h, int w, int gy, int gx, float* centers, void* stream);
+int vqseg_segment_sums_f(const float* x, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_px, const int32_t* labels, int b, int c,
+                         int64_t hw, int k, float* sums, int32_t* counts, void* stream);
+int vqseg_segment_broadcast_f(const float* x, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_px, const int32_t* labels,
+                              const float* sums, const int32_t* counts, int b, int c, int64_t hw, int k, float* y, int64_t y_stride_b,
+                              int64_t y_stride_c, int64_t y_stride_px, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,12 @@ SYMBOLS = {
                                          c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqseg_crf_prepare_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p] + [c_int64] * 3 + [c_int] * 5 + [c_double] * 4 + [c_void_p] * 7),
     "vqseg_crf_step_f": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_double] * 6 + [c_int, c_void_p]),
+    "vqseg_slic_lab_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_int] * 5 + [c_void_p] * 3),
+    "vqseg_slic_assign_f": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_float] + [c_void_p] * 2),
+    "vqseg_slic_update_f": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 2),
+    "vqseg_segment_sums_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 3),
+    "vqseg_segment_broadcast_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p] * 3 + [c_int, c_int, c_int64, c_int, c_void_p] + [c_int64] * 3 +
+                                  [c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

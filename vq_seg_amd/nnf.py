@@ -2406,3 +2406,150 @@ def _crf_step(state, at, bi_w, bi_xy_std, bi_rgb_std, pos_w, pos_xy_std, trunc, 
     _launch("vqseg_crf_step_f", unary.device, _T(rgb, "colours", dtype=torch.int32, numel=b * n), _f32(unary, "unary", b * c * n),
             _f32(npos, "positional norm", n), _f32(nbi, "bilateral norm", b * n), _f32(q[at], "q in", b * c * n),
             _f32(q[1 - at], "q out", b * c * n), b, c, h, w, bi_w, bi_xy_std, bi_rgb_std, pos_w, pos_xy_std, trunc, int(bool(energies)))
+
+
+# ------------------------------------------------------------------------------------------------
+# SLIC superpixels and the mean over the segments of a label map (vqseg_slic_*_f, vqseg_segment_*_f; include/vqseg.h states the algorithm)
+# ------------------------------------------------------------------------------------------------
+SLIC_MAX_SIDE = 4096
+SEGMENT_MAX_CHANNELS = 1024
+
+
+def slic_grid(h: int, w: int, num_components: int):
+    """(gy, gx) of `num_components` superpixels on an h x w image: S = sqrt(h w / K), gy = max(1, round(h / S)), gx likewise
+    (Python's round; K_eff = gy * gx need not be K).  1 <= K <= h w, so a cell is at least one pixel."""
+    h, w = int(h), int(w)
+    if isinstance(num_components, bool) or int(num_components) != num_components or not 1 <= int(num_components) <= h * w:
+        raise ValueError(f"num_components must be an integer in 1..h * w = {h * w}, got {num_components!r}")
+    s = (h * w / int(num_components)) ** 0.5
+    return max(1, int(round(h / s))), max(1, int(round(w / s)))
+
+
+def slic_settings(h, w, num_components, compactness=10.0, iters=10, who="slic"):
+    """the checked settings of a slic call as (gy, gx, spatial weight (compactness / S)^2, iters)"""
+    gy, gx = slic_grid(h, w, num_components)
+    if isinstance(iters, bool) or int(iters) != iters or int(iters) < 0:
+        raise ValueError(f"{who}: iters must be an integer >= 0, got {iters!r}")
+    m = float(compactness)
+    if not 0.0 <= m <= 1e9:
+        raise ValueError(f"{who}: compactness must lie in [0, 1e9], got {compactness!r}")
+    return gy, gx, m * m * int(num_components) / (int(h) * int(w)), int(iters)
+
+
+def slic_supported(images) -> bool:
+    """what the kernels take: a float32 GPU tensor (B, 3, H, W), 1..65535 images, sides up to SLIC_MAX_SIDE"""
+    return (torch.is_tensor(images) and images.is_cuda and images.dim() == 4 and images.dtype == torch.float32 and images.shape[1] == 3
+            and 1 <= images.shape[0] <= 65535 and 1 <= images.shape[2] <= SLIC_MAX_SIDE and 1 <= images.shape[3] <= SLIC_MAX_SIDE)
+
+
+def _slic_lab(images, gy, gx):
+    """one vqseg_slic_lab_f launch -> (lab (B, 3, H, W) planar, the grid's initial centres (B, gy * gx, 5))"""
+    images, istr = _crf_dense(images)
+    b, _, h, w = images.shape
+    dev, n, k = images.device, h * w, gy * gx
+    ip = _strided_f32(images, "images", b * 3 * n)
+    if dev.type != "cuda":                       # before any buffer is asked for on a device that has no HIP path
+        _launch("vqseg_slic_lab_f", dev, ip, *istr, b, h, w, gy, gx, None, None)
+    lab = torch.empty((b, 3, h, w), dtype=torch.float32, device=dev)
+    centers = torch.empty((b, k, 5), dtype=torch.float32, device=dev)
+    _launch("vqseg_slic_lab_f", dev, ip, *istr, b, h, w, gy, gx, _f32(lab, "lab", b * 3 * n), _f32(centers, "centers", b * k * 5))
+    return lab, centers
+
+
+def _slic_assign(lab, centers, gy, gx, weight, labels=None):
+    """one vqseg_slic_assign_f launch -> labels (B, H, W) int32 (`labels`: written in place)"""
+    b, _, h, w = lab.shape
+    if labels is None:
+        labels = torch.empty((b, h, w), dtype=torch.int32, device=lab.device)
+    _launch("vqseg_slic_assign_f", lab.device, _f32(lab, "lab", b * 3 * h * w), _f32(centers, "centers", b * gy * gx * 5), b, h, w, gy, gx,
+            float(weight), _T(labels, "labels", dtype=torch.int32, numel=b * h * w))
+    return labels
+
+
+def _slic_update(lab, labels, centers, gy, gx):
+    """one vqseg_slic_update_f launch: `centers` (B, gy * gx, 5) become the means of their pixels, in place"""
+    b, _, h, w = lab.shape
+    _launch("vqseg_slic_update_f", lab.device, _f32(lab, "lab", b * 3 * h * w), _T(labels, "labels", dtype=torch.int32, numel=b * h * w),
+            b, h, w, gy, gx, _f32(centers, "centers", b * gy * gx * 5))
+    return centers
+
+
+def slic(images, num_components, compactness=10.0, iters=10):
+    """SLIC superpixels of `images` (B, 3, H, W) float32 in [0, 1] on the GPU, NCHW-contiguous or channels_last -> (labels int32
+    (B, H, W), centers float32 (B, K_eff, 5) = (L, a, b, y, x), (gy, gx)): the algorithm of include/vqseg.h -- CIELAB, a gy x gx
+    grid of slic_grid, `iters` times {assign among the 3 x 3 cells around the home cell; update}, one final assign, so the labels
+    are the assignment against the returned centres.  No connectivity enforcement.  One Lab launch, 2 iters + 1 others; bit-identical
+    from call to call.  No gradient flows.  There is no CPU form here (utils.superpixel.slic has one)."""
+    E = _hip.HipLibraryError
+    if not (torch.is_tensor(images) and images.dim() == 4 and images.shape[1] == 3):
+        raise E(f"slic: images must be a (B, 3, H, W) tensor, got {tuple(getattr(images, 'shape', ()))}")
+    b, _, h, w = images.shape
+    gy, gx, weight, iters = slic_settings(h, w, num_components, compactness, iters)
+    if min(b, h, w) < 1 or b > 65535 or max(h, w) > SLIC_MAX_SIDE:
+        raise E(f"slic: 1..65535 images with sides of 1..{SLIC_MAX_SIDE}, got {tuple(images.shape)}")
+    lab, centers = _slic_lab(images, gy, gx)
+    labels = None
+    for _ in range(iters):
+        labels = _slic_assign(lab, centers, gy, gx, weight, labels)
+        _slic_update(lab, labels, centers, gy, gx)
+    return _slic_assign(lab, centers, gy, gx, weight, labels), centers, (gy, gx)
+
+
+def segment_mean_supported(x, labels) -> bool:
+    """what the kernels take: x float32 (B, C, H, W) on the GPU with up to SEGMENT_MAX_CHANNELS channels, labels an integer tensor
+    (B, H, W) on the same device"""
+    return (torch.is_tensor(x) and torch.is_tensor(labels) and x.is_cuda and labels.device == x.device and x.dim() == 4 and labels.dim() == 3
+            and x.dtype == torch.float32 and labels.dtype in (torch.int32, torch.int64) and x.numel() > 0
+            and 1 <= x.shape[1] <= SEGMENT_MAX_CHANNELS and labels.shape[0] == x.shape[0] and labels.shape[1:] == x.shape[2:])
+
+
+def _segment_mean(x, labels, k):
+    """the two launches: sums and counts of x over the segments, then their quotient at every pixel, with x's strides"""
+    x, xs = _crf_dense(x)
+    b, c, h, w = x.shape
+    n, dev = h * w, x.device
+    xp, lp = _strided_f32(x, "x", b * c * n), _T(labels, "labels", dtype=torch.int32, numel=b * n)
+    if dev.type != "cuda":
+        _launch("vqseg_segment_sums_f", dev, xp, *xs, lp, b, c, n, k, None, None)
+    sums = torch.empty((b, k, c), dtype=torch.float32, device=dev)
+    counts = torch.empty((b, k), dtype=torch.int32, device=dev)
+    y = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev)
+    sp, cp = _f32(sums, "segment sums", b * k * c), _T(counts, "segment counts", dtype=torch.int32, numel=b * k)
+    _launch("vqseg_segment_sums_f", dev, xp, *xs, lp, b, c, n, k, sp, cp)
+    _launch("vqseg_segment_broadcast_f", dev, xp, *xs, lp, sp, cp, b, c, n, k, _strided_f32(y, "y", b * c * n), *xs)
+    return y
+
+
+class _SegmentMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, labels, k):
+        ctx.save_for_backward(labels)
+        ctx.k = k
+        return _segment_mean(x, labels, k)
+
+    @staticmethod
+    def backward(ctx, g):
+        (labels,) = ctx.saved_tensors
+        return _segment_mean(g.float(), labels, ctx.k), None, None       # a symmetric projection: its own adjoint
+
+
+def segment_mean(x, labels, num_segments):
+    """y[b, :, p] = the mean of x[b, :, q] over the pixels q of image b with labels[b, q] == labels[b, p], for ANY label map; a pixel
+    whose label lies outside [0, num_segments) passes through unchanged.  x float32 (B, C, H, W) on the GPU, NCHW-contiguous or
+    channels_last (y has x's strides), labels (B, H, W) int32 (int64 is converted).  Two launches (vqseg_segment_sums_f,
+    vqseg_segment_broadcast_f); the backward pass is the same two on the incoming gradient.  Within a segment y is exactly constant."""
+    E = _hip.HipLibraryError
+    if not (torch.is_tensor(x) and torch.is_tensor(labels) and x.dim() == 4 and labels.dim() == 3):
+        raise E("segment_mean: x must be a (B, C, H, W) tensor and labels a (B, H, W) tensor")
+    if labels.shape[0] != x.shape[0] or labels.shape[1:] != x.shape[2:]:
+        raise E(f"segment_mean: labels must be (B, H, W) of x's batch and size, got {tuple(labels.shape)} and {tuple(x.shape)}")
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise E(f"segment_mean: labels must be int32 (or int64), got {labels.dtype}")
+    if isinstance(num_segments, bool) or int(num_segments) != num_segments or int(num_segments) < 1:
+        raise ValueError(f"segment_mean: num_segments must be a positive integer, got {num_segments!r}")
+    if x.numel() == 0 or x.shape[1] > SEGMENT_MAX_CHANNELS:
+        raise E(f"segment_mean: a non-empty x with at most {SEGMENT_MAX_CHANNELS} channels, got {tuple(x.shape)}")
+    if labels.device != x.device:
+        raise E(f"segment_mean: x and labels must be on one device, got {x.device} and {labels.device}")
+    labels = labels.detach().to(torch.int32).contiguous()
+    return _SegmentMean.apply(x, labels, int(num_segments))

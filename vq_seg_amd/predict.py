@@ -55,6 +55,24 @@ def _as_crf(crf):
     return crf
 
 
+def _as_superpixels(superpixels):
+    """None, a component count, or dict(num_components=, compactness=, iters=) -> None or the full dict"""
+    if superpixels is None:
+        return None
+    given = dict(superpixels) if isinstance(superpixels, dict) else dict(num_components=superpixels)
+    unknown = sorted(set(given) - {"num_components", "compactness", "iters"})
+    if unknown or "num_components" not in given:
+        raise ValueError(f"superpixels is a component count or dict(num_components=, compactness=, iters=), got {superpixels!r}")
+    k, m, iters = given["num_components"], given.get("compactness", 10.0), given.get("iters", 10)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"superpixels: num_components must be a positive integer, got {k!r}")
+    if not 0.0 <= float(m) <= 1e9:
+        raise ValueError(f"superpixels: compactness must lie in [0, 1e9], got {m!r}")
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise ValueError(f"superpixels: iters must be an integer >= 0, got {iters!r}")
+    return dict(num_components=k, compactness=float(m), iters=iters)
+
+
 def _resize(x: torch.Tensor, size) -> torch.Tensor:
     """bilinear, align_corners=False: the HIP resize kernel on the GPU, F.interpolate elsewhere"""
     if x.is_cuda:
@@ -71,10 +89,15 @@ class Predictor:
     window, if not the window itself: the windows are resized bilinearly on the way in and their logits on the way out) and
     `window_batch` (how many windows go through one forward, default all of a view: it bounds the forward's activations).  The
     logits of ALL windows are held until the merge: B * T * C * lh * lw * 4 bytes per view (B images, T windows each, C classes,
-    lh x lw logits per window).  `crf`: a utils.crf.DenseCRF, or True for its defaults, refines the prediction (untiled mode)."""
+    lh x lw logits per window).  `crf`: a utils.crf.DenseCRF, or True for its defaults, refines the prediction (untiled mode).
+    `superpixels`: a component count K or dict(num_components=, compactness=, iters=) -- object-based smoothing, the cheap alternative
+    to the CRF (the reference's users write pred[assignment]): the view-averaged class probabilities are averaged over SLIC
+    superpixels of the images (utils.superpixel) at the network's size, between the softmax and the arg-max.  Inference only; not
+    with `window` or `crf`."""
 
     def __init__(self, models: Union[nn.Module, Sequence[nn.Module]], num_classes: int, amp_dtype=None, tta: Sequence[str] = ("none",),
-                 device=None, window=None, stride=None, blend: str = "linear", window_batch: Optional[int] = None, net_size=None, crf=None):
+                 device=None, window=None, stride=None, blend: str = "linear", window_batch: Optional[int] = None, net_size=None, crf=None,
+                 superpixels=None):
         self.models: List[nn.Module] = [models] if isinstance(models, nn.Module) else list(models)
         self.tta: Tuple[str, ...] = (tta,) if isinstance(tta, str) else tuple(tta)
         unknown = [t for t in self.tta if t not in TTA_FLIPS]
@@ -100,6 +123,11 @@ class Predictor:
         self.crf = _as_crf(crf)
         if self.crf is not None and window is not None:
             raise ValueError("crf together with window: the CRF under tiled prediction is not built")
+        self.superpixels = _as_superpixels(superpixels)
+        if self.superpixels is not None and window is not None:
+            raise ValueError("superpixels together with window: superpixels under tiled prediction are not built")
+        if self.superpixels is not None and self.crf is not None:
+            raise ValueError("superpixels together with crf: one refinement of the probabilities at a time")
 
     def _forward(self, model: nn.Module, x: torch.Tensor) -> torch.Tensor:
         """fp32 logits of one forward, under autocast on the GPU if asked for"""
@@ -178,6 +206,34 @@ class Predictor:
             x = _resize(x, size)
         return self.crf.batch(x, torch.softmax(acc, dim=1), out="logits")
 
+    def probabilities(self, images: torch.Tensor) -> torch.Tensor:
+        """-> the class probabilities (N, C, h, w) fp32 at the network's size: softmax of the mean of the views' logits (each view
+        un-flipped).  The models' modes are the caller's business."""
+        logits, flips = self.views(images)
+        acc = None
+        for v, code in zip(logits, flips):
+            r = v.flip(nnf.FLIP_DIMS[code]) if code else v
+            acc = r if acc is None else acc + r
+        if len(logits) > 1:
+            acc = acc * (1.0 / len(logits))
+        return torch.softmax(acc, dim=1)
+
+    def pooled(self, images: torch.Tensor) -> torch.Tensor:
+        """superpixels mode -> log of the pooled probabilities (N, C, h, w) fp32 at the network's size (softmax of it IS the pooled
+        probabilities, so resize_argmax takes labels and top probability from it): `probabilities`, averaged over the SLIC superpixels
+        of the images at that size."""
+        from .utils.superpixel import slic, superpixel_mean
+        if self.superpixels is None:
+            raise ValueError("pooled: this Predictor has no superpixels")
+        if self.device is not None:
+            images = images.to(self.device)
+        prob = self.probabilities(images)
+        x = images.to(prob.device).float()
+        if tuple(x.shape[-2:]) != tuple(prob.shape[-2:]):
+            x = _resize(x, prob.shape[-2:])
+        labels, _centers, (gy, gx) = slic(x, return_centers=True, **self.superpixels)
+        return superpixel_mean(prob, labels, gy * gx).clamp_min(1e-30).log()
+
     @torch.no_grad()
     def __call__(self, images: torch.Tensor, size: Optional[Sequence[int]] = None, want_confidence: bool = False) -> Prediction:
         """images (N, 3, H, W) -> Prediction(label (N, Ho, Wo) uint8, confidence (N, Ho, Wo) f32 | None); size None: (H, W).
@@ -193,6 +249,8 @@ class Predictor:
                 label, top, _ = nnf.merge_argmax(logits, grid, flips=flips, blend=self.blend, want_top=want_confidence)
             elif self.crf is not None:
                 label, top, _ = nnf.resize_argmax(self.refined(images, size), size, want_top=want_confidence)
+            elif self.superpixels is not None:
+                label, top, _ = nnf.resize_argmax(self.pooled(images), size, want_top=want_confidence)
             else:
                 logits, flips = self.views(images)
                 label, top, _ = nnf.resize_argmax(logits, size, flips=flips, want_top=want_confidence)
@@ -209,7 +267,7 @@ class Predictor:
         launch (utils.visualize.render_sheet; vqseg_render_sheet_u8 on the GPU) from the labels, `targets` (N, Ht, Wt) at any size
         and the images themselves.  `panels` default: image | target | pred | 20 px white | mix_pred (without `targets`: no target
         panel); size None: (H, W).  Tiled mode: the merged labels of __call__ are what the sheet shows (`size`: None or the
-        images' own).  crf mode: likewise the refined labels of __call__."""
+        images' own).  crf and superpixels mode: likewise the refined labels of __call__."""
         from .utils.visualize import GAP, render_sheet
         size = self._own_size(images, size) if self.window is not None else \
             tuple(images.shape[-2:]) if size is None else (int(size[0]), int(size[1]))
@@ -222,8 +280,8 @@ class Predictor:
             if self.window is not None:
                 logits, flips, grid = self.tiled_views(images)
                 label = nnf.merge_argmax(logits, grid, flips=flips, blend=self.blend)[0]
-            elif self.crf is not None:
-                logits = [self.refined(images, size)]
+            elif self.crf is not None or self.superpixels is not None:
+                logits = [self.refined(images, size) if self.crf is not None else self.pooled(images)]
                 label = nnf.resize_argmax(logits, size)[0]
             else:
                 logits, flips = self.views(images)
@@ -231,7 +289,7 @@ class Predictor:
             for m, was_training in zip(self.models, modes):
                 m.train(was_training)
         dev = logits[0].device
-        if self.window is not None or self.crf is not None:
+        if self.window is not None or self.crf is not None or self.superpixels is not None:
             return render_sheet(panels, images.to(dev), label, None if targets is None else targets.to(dev), size=size, palette=palette,
                                 alpha=alpha, half=half, num_classes=self.num_classes)
         return render_sheet(panels, images.to(dev), logits, None if targets is None else targets.to(dev), size=size, palette=palette, alpha=alpha,

@@ -33,6 +33,7 @@ from . import nnf
 from .averaging import AveragedNetwork
 from .evaluate import test_loop
 from .utils.visualize import default_palette
+from .utils import superpixel
 from .models import init_weight
 from .models.networks import make_model
 from .optim import HipAdam
@@ -104,6 +105,14 @@ class CPSConfig:
     conf_ce_temperature: float = 1.0
     conf_ce_unreliable_weight: bool = True    # uw = loss.unreliable_weight(the target-side logits, 100 - unsup_loss_drop_percent * (1 - epoch_frac)); False: 1
     conf_ce_detach_targets: bool = False      # True: no gradient to the network that made the targets (not the reference's)
+    superpixel_mean: Optional[int] = None     # the component count (the reference's: 1600).  deprecated/train_slic.py:44-69,152-160: each network's fp32
+                                              # TRAINING logits are averaged over SLIC superpixels of the images they were computed from (utils.superpixel)
+                                              # before the losses and the pseudo labels are taken -- both criteria, the masks handed to the other network,
+                                              # the metrics and conf-CE see pooled logits.  One label map per batch and step, made on the device on the
+                                              # caller's stream (the unlabelled one after CutMix) and shared by both networks; the two no-grad pseudo-label
+                                              # forwards are not pooled.  None = today's step: nothing of it is entered
+    superpixel_compactness: float = 10.0      # slic(compactness, iters): the reference's fast_slic call uses compactness 10 and its default 10 iterations
+    superpixel_iters: int = 10
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -131,6 +140,13 @@ class CPSConfig:
                 raise ValueError(f"conf_ce_temperature must be positive, got {self.conf_ce_temperature!r}")
             if not float(self.conf_ce_threshold_neg) >= 0.0:
                 raise ValueError(f"conf_ce_threshold_neg must be >= 0, got {self.conf_ce_threshold_neg!r}")
+        if self.superpixel_mean is not None and (isinstance(self.superpixel_mean, bool) or int(self.superpixel_mean) != self.superpixel_mean
+                                                 or int(self.superpixel_mean) < 1):
+            raise ValueError(f"superpixel_mean must be None or a positive component count, got {self.superpixel_mean!r}")
+        if not 0.0 <= float(self.superpixel_compactness) <= 1e9:
+            raise ValueError(f"superpixel_compactness must lie in [0, 1e9], got {self.superpixel_compactness!r}")
+        if isinstance(self.superpixel_iters, bool) or int(self.superpixel_iters) != self.superpixel_iters or int(self.superpixel_iters) < 0:
+            raise ValueError(f"superpixel_iters must be an integer >= 0, got {self.superpixel_iters!r}")
         if self.recipe != "v1" and (self.criterion != "dice_loss" or self.class_weight is not None):
             raise ValueError("criterion / class_weight apply to recipe 'v1', the single-criterion recipe; the reference has no weighted or "
                              "focal form of recipe 'v2' (CE + Dice)")
@@ -321,8 +337,9 @@ class CPSTrainer:
         score_1, score_2 = self._pseudo_scores(ul_input)
         ul_train, score_1, score_2 = self._cutmix(ul_input, score_1, score_2)
         gt_ul_1, gt_ul_2, kw = self._targets(score_1, score_2, epoch_frac)
+        segments = self._superpixels(l_input, ul_train)
         sup, unsup, sup_con = self._train_forwards(l_input, l_target, ul_train, gt_ul_1, gt_ul_2, kw)
-        fused, ps1, sup_terms, cps_terms = self._terms(l_target, sup, unsup, score_1, score_2, kw)
+        fused, ps1, sup_terms, cps_terms = self._terms(l_target, sup, unsup, score_1, score_2, kw, segments)
         lr = self.sched.get_lr(self.iter)
         for o in self.opts:
             o.param_groups[0]["lr"] = lr
@@ -400,6 +417,25 @@ class CPSTrainer:
             self.aux.update(ul_mixed=ul_train, score_1_mixed=mixed_1, score_2_mixed=mixed_2, boxes=list(boxes))
         return ul_train, mixed_1, mixed_2
 
+    @torch.no_grad()
+    def _superpixels(self, l_input, ul_train):
+        """cfg.superpixel_mean -> (labelled label maps, unlabelled label maps, K_eff): SLIC of the two batches as the training forwards
+        receive them, once each, on the caller's stream, for both networks' lanes; else None, and nothing is entered."""
+        cfg, g = self.cfg, self._glue
+        if cfg.superpixel_mean is None:
+            return None
+        maps = []
+        for images in (l_input, ul_train):
+            labels, _centers, (gy, gx) = superpixel.slic(images.float(), cfg.superpixel_mean, cfg.superpixel_compactness, cfg.superpixel_iters,
+                                                         return_centers=True)
+            maps.append(labels)
+        g.fork()                                                        # the lanes wait for the maps
+        for labels in maps:
+            g.share(labels)
+        if cfg.keep_aux:
+            self.aux.update(superpixels_l=maps[0], superpixels_ul=maps[1])
+        return maps[0], maps[1], gy * gx
+
     def _targets(self, score_1, score_2, epoch_frac):
         """-> gt_ul_1, gt_ul_2 (each network's unlabelled target comes from the OTHER network's scores, made on that network's
         stream) and the recipe's keyword of the training forwards"""
@@ -449,15 +485,18 @@ class CPSTrainer:
             return (lambda p, t: sums(p, t, crt.ignore_index)), True
         return (crt if cfg.recipe == "v1" else self._ce_dice), False
 
-    def _own_mask(self, ps, pu, kw):
-        """a network's fp32 predictions (labelled, unlabelled, both) and the pseudo-label mask it hands to the other network"""
+    def _own_mask(self, ps, pu, kw, segments=None):
+        """a network's fp32 predictions (labelled, unlabelled, both) and the pseudo-label mask it hands to the other network.
+        `segments` (cfg.superpixel_mean): both predictions are first averaged over their batch's superpixels, on this network's stream"""
         ps, pu = ps.float(), pu.float()
+        if segments is not None:
+            ps, pu = superpixel.superpixel_mean(ps, segments[0], segments[2]), superpixel.superpixel_mean(pu, segments[1], segments[2])
         pred = torch.cat([ps, pu], dim=0)
         if self.cfg.recipe == "v1":
             return ps, pu, pred, regularized_pseudo_label(pred, kw["percent"])
         return ps, pu, pred, score_mask(pred, _argmax_classes(pred), kw["th"])
 
-    def _terms(self, l_target, sup, unsup, score_1, score_2, kw):
+    def _terms(self, l_target, sup, unsup, score_1, score_2, kw, segments=None):
         """Each network's own mask and its two criterion terms (supervised; CPS against the other's mask) on its stream ->
         fused, pred_sup_1, (sup_1, sup_2), (cps_1, cps_2).  Ends the glue: the caller's stream joins the lanes."""
         cfg, g = self.cfg, self._glue
@@ -469,9 +508,9 @@ class CPSTrainer:
             g.fork()
             g.share(cls_weight)
         with g.on(0):
-            ps1, pu1, pred_1, mask_1 = self._own_mask(sup[0][0], unsup[0][0], kw)
+            ps1, pu1, pred_1, mask_1 = self._own_mask(sup[0][0], unsup[0][0], kw, segments)
         with g.on(1):
-            ps2, pu2, pred_2, mask_2 = self._own_mask(sup[1][0], unsup[1][0], kw)
+            ps2, pu2, pred_2, mask_2 = self._own_mask(sup[1][0], unsup[1][0], kw, segments)
         g.exchange(mask_1, mask_2)
         crit, fused = self._criterion(cls_weight, pred_1)
         soft = cfg.unsup_criterion is not None                          # the unlabelled half of the CPS terms is _soft_cps's
@@ -487,6 +526,10 @@ class CPSTrainer:
             cps_1, cps_2 = self._soft_cps(cps_1, cps_2, ps1, ps2, pu1, pu2, kw)
         if cfg.keep_aux:
             self.aux.update(mask_1=mask_1, mask_2=mask_2, pred_sup_1=ps1.detach(), pred_ul_2=pu2.detach())
+            if segments is not None:                                    # the unpooled logits of network 1, and what the terms are restated from
+                raw_s, raw_u = sup[0][0].detach().float(), unsup[0][0].detach().float()
+                self.aux.update(pred_sup_1_unpooled=raw_s, pred_ul_1_unpooled=raw_u, pred_1=pred_1.detach(), pred_2=pred_2.detach())
+                g.to_caller(raw_s, raw_u, pred_1, pred_2)
             if cls_weight is not None or not isinstance(self.criterion, DiceLoss):     # what the criterion arms' terms are restated from
                 self.aux.update(pred_1=pred_1.detach(), pred_2=pred_2.detach(), class_weight=cls_weight)
                 g.to_caller(pred_1, pred_2)
@@ -660,16 +703,18 @@ class CPSTrainer:
 
     def predict(self, images, size=None, which: str = "student", index: int = 0, ensemble: bool = False, tta=("none",),
                 want_confidence: bool = False, window=None, stride=None, blend: str = "linear", window_batch=None, net_size=None,
-                crf=None) -> Prediction:
+                crf=None, superpixels=None) -> Prediction:
         """Class maps of `images` (N, 3, H, W) at `size` (None: their own): predict.Predictor on network `index` of the pair `which`
         names, or with `ensemble` on both of them (mean of the two networks' logits), times the flipped views of `tta`, under
         cfg.amp_dtype.  `window` (with `stride`, `blend`, `window_batch`, `net_size`): tiled prediction at the images' own size
         (predict.Predictor).  `crf` (a utils.crf.DenseCRF or True; not with `window`): dense-CRF refinement of the prediction.
+        `superpixels` (a component count or dict(num_components=, compactness=, iters=); not with `window` or `crf`): the class
+        probabilities are averaged over SLIC superpixels of the images before the arg-max.
         -> Prediction(label (N, Ho, Wo) uint8, confidence (N, Ho, Wo) f32 | None)."""
         nets = self._networks(which)
         return Predictor(list(nets) if ensemble else nets[index], self.cfg.num_classes, amp_dtype=self.cfg.amp_dtype, tta=tta,
                          device=self.device, window=window, stride=stride, blend=blend, window_batch=window_batch,
-                         net_size=net_size, crf=crf)(images, size=size, want_confidence=want_confidence)
+                         net_size=net_size, crf=crf, superpixels=superpixels)(images, size=size, want_confidence=want_confidence)
 
     def _weighted(self, pred, target, weight):
         """the configured criterion with this step's class weights: the module's own parameters (ignore index 255, the focal

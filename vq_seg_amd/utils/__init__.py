@@ -4,3 +4,4 @@ from .seg_tools import img_to_label, onehot_1d, label_to_onehot  # noqa: F401
 from .seed import seed_everything  # noqa: F401
 from .device import device_setting  # noqa: F401
 from .ckpoints import save_ckpoints, load_ckpoints  # noqa: F401
+from .superpixel import slic, superpixel_mean, superpixel_grid  # noqa: F401

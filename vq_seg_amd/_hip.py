@@ -167,6 +167,13 @@ SYMBOLS = {
     "vqseg_segment_sums_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 3),
     "vqseg_segment_broadcast_f": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p] * 3 + [c_int, c_int, c_int64, c_int, c_void_p] + [c_int64] * 3 +
                                   [c_void_p]),
+    "vqseg_region_graph_f": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 3),
+    "vqseg_rbd_weights_f": (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 2),
+    "vqseg_rbd_geodesic_f": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "vqseg_rbd_background_f": (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_float] * 2 + [c_void_p] * 2),
+    "vqseg_rbd_contrast_f": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] + [c_void_p] * 2),
+    "vqseg_rbd_solve_f": (c_int, [c_void_p] * 5 + [c_int] * 2 + [c_float] * 2 + [c_void_p] * 5),
+    "vqseg_rbd_paint_f": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 2),
 }
 
 _lib: Optional[ctypes.CDLL] = None

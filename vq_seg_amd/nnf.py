@@ -2474,6 +2474,15 @@ def _slic_update(lab, labels, centers, gy, gx):
     return centers
 
 
+def _slic_loop(lab, centers, gy, gx, weight, iters):
+    """`iters` times {assign; update} on `centers` (in place), then the final assign -> labels (slic and saliency_rbd share it)"""
+    labels = None
+    for _ in range(iters):
+        labels = _slic_assign(lab, centers, gy, gx, weight, labels)
+        _slic_update(lab, labels, centers, gy, gx)
+    return _slic_assign(lab, centers, gy, gx, weight, labels)
+
+
 def slic(images, num_components, compactness=10.0, iters=10):
     """SLIC superpixels of `images` (B, 3, H, W) float32 in [0, 1] on the GPU, NCHW-contiguous or channels_last -> (labels int32
     (B, H, W), centers float32 (B, K_eff, 5) = (L, a, b, y, x), (gy, gx)): the algorithm of include/vqseg.h -- CIELAB, a gy x gx
@@ -2488,11 +2497,7 @@ def slic(images, num_components, compactness=10.0, iters=10):
     if min(b, h, w) < 1 or b > 65535 or max(h, w) > SLIC_MAX_SIDE:
         raise E(f"slic: 1..65535 images with sides of 1..{SLIC_MAX_SIDE}, got {tuple(images.shape)}")
     lab, centers = _slic_lab(images, gy, gx)
-    labels = None
-    for _ in range(iters):
-        labels = _slic_assign(lab, centers, gy, gx, weight, labels)
-        _slic_update(lab, labels, centers, gy, gx)
-    return _slic_assign(lab, centers, gy, gx, weight, labels), centers, (gy, gx)
+    return _slic_loop(lab, centers, gy, gx, weight, iters), centers, (gy, gx)
 
 
 def segment_mean_supported(x, labels) -> bool:
@@ -2553,3 +2558,199 @@ def segment_mean(x, labels, num_segments):
         raise E(f"segment_mean: x and labels must be on one device, got {x.device} and {labels.device}")
     labels = labels.detach().to(torch.int32).contiguous()
     return _SegmentMean.apply(x, labels, int(num_segments))
+
+
+# ------------------------------------------------------------------------------------------------
+# RBD saliency over SLIC superpixels (vqseg_region_graph_f, vqseg_rbd_*_f; include/vqseg.h states the definition)
+# ------------------------------------------------------------------------------------------------
+RBD_MAX_SEGMENTS = 1024
+
+
+def rbd_settings(sigma_clr=10.0, sigma_bndcon=1.0, sigma_spa=0.25, mu=0.1, who="saliency_rbd"):
+    """the checked parameters of an RBD call as floats"""
+    out = []
+    for name, v in (("sigma_clr", sigma_clr), ("sigma_bndcon", sigma_bndcon), ("sigma_spa", sigma_spa)):
+        v = float(v)
+        if not 0.0 < v <= 1e18:
+            raise ValueError(f"{who}: {name} must lie in (0, 1e18], got {v!r}")
+        out.append(v)
+    mu = float(mu)
+    if not 0.0 <= mu <= 1e18:
+        raise ValueError(f"{who}: mu must lie in [0, 1e18], got {mu!r}")
+    return (*out, mu)
+
+
+def rbd_supported(images, n_segments=250) -> bool:
+    """what the kernels take: what slic takes, with a grid of at most RBD_MAX_SEGMENTS cells"""
+    if not slic_supported(images):
+        return False
+    try:
+        gy, gx = slic_grid(images.shape[2], images.shape[3], n_segments)
+    except (ValueError, TypeError):
+        return False
+    return gy * gx <= RBD_MAX_SEGMENTS
+
+
+def _rbd_check(who, b, h, w, gy, gx):
+    E = _hip.HipLibraryError
+    if min(b, h, w) < 1 or b > 65535 or max(h, w) > SLIC_MAX_SIDE:
+        raise E(f"{who}: 1..65535 images with sides of 1..{SLIC_MAX_SIDE}, got {b} of {h} x {w}")
+    if not (1 <= gy <= h and 1 <= gx <= w):
+        raise E(f"{who}: the grid must have 1..h rows and 1..w columns of cells, got {gy} x {gx} on {h} x {w}")
+    if gy * gx > RBD_MAX_SEGMENTS:
+        raise E(f"{who}: at most {RBD_MAX_SEGMENTS} superpixels, got a {gy} x {gx} grid ({gy * gx})")
+
+
+def _rbd_region_graph(lab, labels, gy, gx):
+    """one vqseg_region_graph_f launch -> (stats (B, K, 8) = (L, a, b, y, x, n, bnd, 0), adj uint8 (B, K, K))"""
+    b, _, h, w = lab.shape
+    k, dev = gy * gx, lab.device
+    _rbd_check("region_graph", b, h, w, gy, gx)
+    lp, bp = _f32(lab, "lab", b * 3 * h * w), _T(labels, "labels", dtype=torch.int32, numel=b * h * w)
+    if dev.type != "cuda":
+        _launch("vqseg_region_graph_f", dev, lp, bp, b, h, w, gy, gx, None, None)
+    stats = torch.empty((b, k, 8), dtype=torch.float32, device=dev)
+    adj = torch.empty((b, k, k), dtype=torch.uint8, device=dev)
+    _launch("vqseg_region_graph_f", dev, lp, bp, b, h, w, gy, gx, _f32(stats, "stats", b * k * 8), _T(adj, "adj", dtype=torch.uint8, numel=b * k * k))
+    return stats, adj
+
+
+def _rbd_tables(who, stats, *tables):
+    """(b, k) of stats (B, K, 8), after checking that every table is (B, K, K) or (B, K) of it"""
+    E = _hip.HipLibraryError
+    if not (torch.is_tensor(stats) and stats.dim() == 3 and stats.shape[2] == 8 and 1 <= stats.shape[1] <= RBD_MAX_SEGMENTS
+            and 1 <= stats.shape[0] <= 65535):
+        raise E(f"{who}: stats must be (B, K, 8) with 1..65535 images and K <= {RBD_MAX_SEGMENTS}, got {tuple(getattr(stats, 'shape', ()))}")
+    b, k = stats.shape[:2]
+    for t in tables:
+        if not (torch.is_tensor(t) and tuple(t.shape) in ((b, k, k), (b, k))):
+            raise E(f"{who}: a table of shape {tuple(getattr(t, 'shape', ()))} beside stats {tuple(stats.shape)}")
+    return b, k
+
+
+def _rbd_weights(stats, adj):
+    """one vqseg_rbd_weights_f launch -> W (B, K, K): the colour distance along an edge, 0 on the diagonal, +inf elsewhere"""
+    b, k = _rbd_tables("rbd_weights", stats, adj)
+    sp, ap = _f32(stats, "stats", b * k * 8), _T(adj, "adj", dtype=torch.uint8, numel=b * k * k)
+    if stats.device.type != "cuda":
+        _launch("vqseg_rbd_weights_f", stats.device, sp, ap, b, k, None)
+    wgt = torch.empty((b, k, k), dtype=torch.float32, device=stats.device)
+    _launch("vqseg_rbd_weights_f", stats.device, sp, ap, b, k, _f32(wgt, "weights", b * k * k))
+    return wgt
+
+
+def _rbd_geodesic(wgt, inplace=False):
+    """vqseg_rbd_geodesic_f: all-pairs shortest path lengths over W (B, K, K) (a copy unless `inplace`)"""
+    E = _hip.HipLibraryError
+    if not (torch.is_tensor(wgt) and wgt.dim() == 3 and wgt.shape[1] == wgt.shape[2] and 1 <= wgt.shape[1] <= RBD_MAX_SEGMENTS
+            and 1 <= wgt.shape[0] <= 65535):
+        raise E(f"rbd_geodesic: W must be (B, K, K) with 1..65535 images and K <= {RBD_MAX_SEGMENTS}, got {tuple(getattr(wgt, 'shape', ()))}")
+    b, k = wgt.shape[:2]
+    wp = _f32(wgt, "weights", b * k * k)
+    if wgt.device.type != "cuda":
+        _launch("vqseg_rbd_geodesic_f", wgt.device, wp, b, k)
+    g = wgt if inplace else wgt.clone()
+    _launch("vqseg_rbd_geodesic_f", g.device, _f32(g, "geodesic", b * k * k), b, k)
+    return g
+
+
+def _rbd_background(g, stats, sigma_clr=10.0, sigma_bndcon=1.0):
+    """one vqseg_rbd_background_f launch -> w_bg (B, K)"""
+    b, k = _rbd_tables("rbd_background", stats, g)
+    gp, sp = _f32(g, "geodesic", b * k * k), _f32(stats, "stats", b * k * 8)
+    if g.device.type != "cuda":
+        _launch("vqseg_rbd_background_f", g.device, gp, sp, b, k, float(sigma_clr), float(sigma_bndcon), None)
+    w_bg = torch.empty((b, k), dtype=torch.float32, device=g.device)
+    _launch("vqseg_rbd_background_f", g.device, gp, sp, b, k, float(sigma_clr), float(sigma_bndcon), _f32(w_bg, "w_bg", b * k))
+    return w_bg
+
+
+def _rbd_contrast(g, stats, w_bg, h, w, sigma_spa=0.25):
+    """one vqseg_rbd_contrast_f launch -> wCtr (B, K), not yet normalised"""
+    b, k = _rbd_tables("rbd_contrast", stats, g, w_bg)
+    gp, sp, wp = _f32(g, "geodesic", b * k * k), _f32(stats, "stats", b * k * 8), _f32(w_bg, "w_bg", b * k)
+    if g.device.type != "cuda":
+        _launch("vqseg_rbd_contrast_f", g.device, gp, sp, wp, b, k, int(h), int(w), float(sigma_spa), None)
+    wctr = torch.empty((b, k), dtype=torch.float32, device=g.device)
+    _launch("vqseg_rbd_contrast_f", g.device, gp, sp, wp, b, k, int(h), int(w), float(sigma_spa), _f32(wctr, "wctr", b * k))
+    return wctr
+
+
+def _rbd_solve(g, stats, adj, w_bg, wctr, sigma_clr=10.0, mu=0.1):
+    """one vqseg_rbd_solve_f launch -> (wCtr normalised, x, x normalised), each (B, K)"""
+    b, k = _rbd_tables("rbd_solve", stats, g, adj, w_bg, wctr)
+    dev = g.device
+    ins = (_f32(g, "geodesic", b * k * k), _f32(stats, "stats", b * k * 8), _T(adj, "adj", dtype=torch.uint8, numel=b * k * k),
+           _f32(w_bg, "w_bg", b * k), _f32(wctr, "wctr", b * k))
+    if dev.type != "cuda":
+        _launch("vqseg_rbd_solve_f", dev, *ins, b, k, float(sigma_clr), float(mu), None, None, None, None)
+    work = torch.empty((b, k, k), dtype=torch.float32, device=dev)
+    outs = torch.empty((3, b, k), dtype=torch.float32, device=dev)
+    _launch("vqseg_rbd_solve_f", dev, *ins, b, k, float(sigma_clr), float(mu), _f32(work, "workspace", b * k * k),
+            *(_f32(o, "solve output", b * k) for o in outs))
+    return outs[0], outs[1], outs[2]
+
+
+def _rbd_paint(xnorm, labels, gy, gx):
+    """one vqseg_rbd_paint_f launch -> sal (B, H, W) = xnorm[b, label]"""
+    b, h, w = labels.shape
+    _rbd_check("rbd_paint", b, h, w, gy, gx)
+    k = gy * gx
+    xp, lp = _f32(xnorm, "xnorm", b * k), _T(labels, "labels", dtype=torch.int32, numel=b * h * w)
+    if labels.device.type != "cuda":
+        _launch("vqseg_rbd_paint_f", labels.device, xp, lp, b, h, w, gy, gx, None)
+    sal = torch.empty((b, h, w), dtype=torch.float32, device=labels.device)
+    _launch("vqseg_rbd_paint_f", labels.device, xp, lp, b, h, w, gy, gx, _f32(sal, "saliency", b * h * w))
+    return sal
+
+
+def rbd_from_labels(lab, labels, grid, sigma_clr=10.0, sigma_bndcon=1.0, sigma_spa=0.25, mu=0.1, return_parts=False):
+    """RBD saliency (include/vqseg.h) of planar Lab images (B, 3, H, W) float32 under a SLIC label map (B, H, W) int32 of the grid
+    (gy, gx), both on the GPU -> (B, H, W) float32 in [0, 1], exactly constant within a superpixel.  6 + 3 ceil(K / 64) launches,
+    bit-identical from call to call and independent of the batch.  `return_parts`: (map, dict of every stage's output)."""
+    E = _hip.HipLibraryError
+    if not (torch.is_tensor(lab) and torch.is_tensor(labels) and lab.dim() == 4 and lab.shape[1] == 3 and labels.dim() == 3
+            and labels.shape[0] == lab.shape[0] and labels.shape[1:] == lab.shape[2:]):
+        raise E(f"saliency_rbd: lab must be (B, 3, H, W) and labels (B, H, W) of one batch and size, got "
+                f"{tuple(getattr(lab, 'shape', ()))} and {tuple(getattr(labels, 'shape', ()))}")
+    if lab.dtype != torch.float32 or labels.dtype != torch.int32:
+        raise E(f"saliency_rbd: lab must be float32 and labels int32, got {lab.dtype} and {labels.dtype}")
+    if labels.device != lab.device:
+        raise E(f"saliency_rbd: lab and labels must be on one device, got {lab.device} and {labels.device}")
+    gy, gx = int(grid[0]), int(grid[1])
+    sigma_clr, sigma_bndcon, sigma_spa, mu = rbd_settings(sigma_clr, sigma_bndcon, sigma_spa, mu)
+    b, _, h, w = lab.shape
+    _rbd_check("saliency_rbd", b, h, w, gy, gx)
+    lab, labels = lab.detach().contiguous(), labels.detach().contiguous()
+    stats, adj = _rbd_region_graph(lab, labels, gy, gx)
+    g = _rbd_geodesic(_rbd_weights(stats, adj), inplace=True)
+    w_bg = _rbd_background(g, stats, sigma_clr, sigma_bndcon)
+    wctr = _rbd_contrast(g, stats, w_bg, h, w, sigma_spa)
+    wctr_norm, x, xnorm = _rbd_solve(g, stats, adj, w_bg, wctr, sigma_clr, mu)
+    sal = _rbd_paint(xnorm, labels, gy, gx)
+    if return_parts:
+        return sal, dict(stats=stats, adj=adj, geodesic=g, w_bg=w_bg, wctr=wctr, wctr_norm=wctr_norm, x=x, xnorm=xnorm)
+    return sal
+
+
+def saliency_rbd(images, n_segments=250, compactness=10.0, iters=10, sigma_clr=10.0, sigma_bndcon=1.0, sigma_spa=0.25, mu=0.1,
+                 return_parts=False):
+    """RBD saliency maps of `images` (B, 3, H, W) float32 in [0, 1] on the GPU, NCHW-contiguous or channels_last -> (B, H, W) float32
+    in [0, 1]: slic's superpixels (ONE Lab launch serves the assign / update loop and the region pass), then rbd_from_labels.  The
+    labels are nnf.slic's, bit for bit.  No gradient flows.  `return_parts`: (map, dict with labels, centers, grid and every stage).
+    There is no CPU form here (utils.saliency.saliency_rbd has one)."""
+    E = _hip.HipLibraryError
+    if not (torch.is_tensor(images) and images.dim() == 4 and images.shape[1] == 3):
+        raise E(f"saliency_rbd: images must be a (B, 3, H, W) tensor, got {tuple(getattr(images, 'shape', ()))}")
+    b, _, h, w = images.shape
+    gy, gx, weight, iters = slic_settings(h, w, n_segments, compactness, iters, who="saliency_rbd")
+    rbd_settings(sigma_clr, sigma_bndcon, sigma_spa, mu)
+    _rbd_check("saliency_rbd", b, h, w, gy, gx)
+    if images.dtype != torch.float32:
+        raise E(f"saliency_rbd: images must be float32, got {images.dtype}")
+    lab, centers = _slic_lab(images, gy, gx)
+    labels = _slic_loop(lab, centers, gy, gx, weight, iters)
+    out = rbd_from_labels(lab, labels, (gy, gx), sigma_clr, sigma_bndcon, sigma_spa, mu, return_parts)
+    if return_parts:
+        out[1].update(labels=labels, centers=centers, grid=(gy, gx), lab=lab)
+    return out

@@ -33,7 +33,7 @@ from . import nnf
 from .averaging import AveragedNetwork
 from .evaluate import test_loop
 from .utils.visualize import default_palette
-from .utils import superpixel
+from .utils import saliency, superpixel
 from .models import init_weight
 from .models.networks import make_model
 from .optim import HipAdam
@@ -113,6 +113,15 @@ class CPSConfig:
                                               # forwards are not pooled.  None = today's step: nothing of it is entered
     superpixel_compactness: float = 10.0      # slic(compactness, iters): the reference's fast_slic call uses compactness 10 and its default 10 iterations
     superpixel_iters: int = 10
+    salient_mask: Optional[float] = None      # the threshold (the reference's: 0.1).  deprecated/train_salient.py:29-34,122-126: where the RBD saliency map
+                                              # (utils.saliency) of the image is <= the threshold, each network's fp32 TRAINING scores of every class >= 1
+                                              # are multiplied by 0 (after the superpixel pooling, when that is on) -- the losses, the masks handed to the
+                                              # other network, the metrics and conf-CE see masked scores.  One map per batch and step, made on the device on
+                                              # the caller's stream from the images the training forwards receive (the unlabelled ones after CutMix); the
+                                              # reference can only read the map of the un-augmented file from disk.  The two no-grad pseudo-label forwards
+                                              # are not masked.  None = today's step: nothing of it is entered
+    salient_segments: int = 250               # saliency_rbd(n_segments): the reference's get_saliency_rbd default; SLIC with superpixel_compactness / _iters.
+                                              # Equal to superpixel_mean: one SLIC run per batch serves both options
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -147,6 +156,11 @@ class CPSConfig:
             raise ValueError(f"superpixel_compactness must lie in [0, 1e9], got {self.superpixel_compactness!r}")
         if isinstance(self.superpixel_iters, bool) or int(self.superpixel_iters) != self.superpixel_iters or int(self.superpixel_iters) < 0:
             raise ValueError(f"superpixel_iters must be an integer >= 0, got {self.superpixel_iters!r}")
+        if self.salient_mask is not None and (isinstance(self.salient_mask, bool) or not 0.0 <= float(self.salient_mask) < 1.0):
+            raise ValueError(f"salient_mask must be None or a threshold in [0, 1), got {self.salient_mask!r}")
+        if (isinstance(self.salient_segments, bool) or int(self.salient_segments) != self.salient_segments
+                or not 1 <= int(self.salient_segments) <= nnf.RBD_MAX_SEGMENTS):
+            raise ValueError(f"salient_segments must be an integer in 1..{nnf.RBD_MAX_SEGMENTS}, got {self.salient_segments!r}")
         if self.recipe != "v1" and (self.criterion != "dice_loss" or self.class_weight is not None):
             raise ValueError("criterion / class_weight apply to recipe 'v1', the single-criterion recipe; the reference has no weighted or "
                              "focal form of recipe 'v2' (CE + Dice)")
@@ -338,8 +352,9 @@ class CPSTrainer:
         ul_train, score_1, score_2 = self._cutmix(ul_input, score_1, score_2)
         gt_ul_1, gt_ul_2, kw = self._targets(score_1, score_2, epoch_frac)
         segments = self._superpixels(l_input, ul_train)
+        salient = self._saliency(l_input, ul_train, segments)
         sup, unsup, sup_con = self._train_forwards(l_input, l_target, ul_train, gt_ul_1, gt_ul_2, kw)
-        fused, ps1, sup_terms, cps_terms = self._terms(l_target, sup, unsup, score_1, score_2, kw, segments)
+        fused, ps1, sup_terms, cps_terms = self._terms(l_target, sup, unsup, score_1, score_2, kw, segments, salient)
         lr = self.sched.get_lr(self.iter)
         for o in self.opts:
             o.param_groups[0]["lr"] = lr
@@ -429,12 +444,35 @@ class CPSTrainer:
             labels, _centers, (gy, gx) = superpixel.slic(images.float(), cfg.superpixel_mean, cfg.superpixel_compactness, cfg.superpixel_iters,
                                                          return_centers=True)
             maps.append(labels)
+        self._slic_grid = (gy, gx)                                      # for _saliency, when it can use these maps
         g.fork()                                                        # the lanes wait for the maps
         for labels in maps:
             g.share(labels)
         if cfg.keep_aux:
             self.aux.update(superpixels_l=maps[0], superpixels_ul=maps[1])
         return maps[0], maps[1], gy * gx
+
+    @torch.no_grad()
+    def _saliency(self, l_input, ul_train, segments=None):
+        """cfg.salient_mask -> (labelled maps, unlabelled maps): RBD saliency of the two batches as the training forwards receive them,
+        once each, on the caller's stream, for both networks' lanes; else None, and nothing is entered.  SLIC with cfg.salient_segments
+        components and cfg.superpixel_compactness / superpixel_iters (10 and 10: the reference's); where cfg.superpixel_mean asks for the
+        same component count, `segments`' label maps serve both and SLIC runs once per batch, else each option runs its own."""
+        cfg, g = self.cfg, self._glue
+        if cfg.salient_mask is None:
+            return None
+        if segments is not None and cfg.superpixel_mean == cfg.salient_segments:
+            maps = [saliency.saliency_rbd_from_slic(images.float(), labels, self._slic_grid)
+                    for images, labels in ((l_input, segments[0]), (ul_train, segments[1]))]
+        else:
+            maps = [saliency.saliency_rbd(images.float(), cfg.salient_segments, cfg.superpixel_compactness, cfg.superpixel_iters)
+                    for images in (l_input, ul_train)]
+        g.fork()                                                        # the lanes wait for the maps
+        for m in maps:
+            g.share(m)
+        if cfg.keep_aux:
+            self.aux.update(saliency_l=maps[0], saliency_ul=maps[1])
+        return maps[0], maps[1]
 
     def _targets(self, score_1, score_2, epoch_frac):
         """-> gt_ul_1, gt_ul_2 (each network's unlabelled target comes from the OTHER network's scores, made on that network's
@@ -485,18 +523,22 @@ class CPSTrainer:
             return (lambda p, t: sums(p, t, crt.ignore_index)), True
         return (crt if cfg.recipe == "v1" else self._ce_dice), False
 
-    def _own_mask(self, ps, pu, kw, segments=None):
+    def _own_mask(self, ps, pu, kw, segments=None, salient=None):
         """a network's fp32 predictions (labelled, unlabelled, both) and the pseudo-label mask it hands to the other network.
-        `segments` (cfg.superpixel_mean): both predictions are first averaged over their batch's superpixels, on this network's stream"""
+        `segments` (cfg.superpixel_mean): both predictions are first averaged over their batch's superpixels, on this network's stream.
+        `salient` (cfg.salient_mask): then the scores of the classes >= 1 are zeroed where the batch's saliency map is <= the threshold"""
         ps, pu = ps.float(), pu.float()
         if segments is not None:
             ps, pu = superpixel.superpixel_mean(ps, segments[0], segments[2]), superpixel.superpixel_mean(pu, segments[1], segments[2])
+        if salient is not None:
+            ps, pu = (saliency.salient_masking(ps, salient[0], self.cfg.salient_mask),
+                      saliency.salient_masking(pu, salient[1], self.cfg.salient_mask))
         pred = torch.cat([ps, pu], dim=0)
         if self.cfg.recipe == "v1":
             return ps, pu, pred, regularized_pseudo_label(pred, kw["percent"])
         return ps, pu, pred, score_mask(pred, _argmax_classes(pred), kw["th"])
 
-    def _terms(self, l_target, sup, unsup, score_1, score_2, kw, segments=None):
+    def _terms(self, l_target, sup, unsup, score_1, score_2, kw, segments=None, salient=None):
         """Each network's own mask and its two criterion terms (supervised; CPS against the other's mask) on its stream ->
         fused, pred_sup_1, (sup_1, sup_2), (cps_1, cps_2).  Ends the glue: the caller's stream joins the lanes."""
         cfg, g = self.cfg, self._glue
@@ -508,9 +550,9 @@ class CPSTrainer:
             g.fork()
             g.share(cls_weight)
         with g.on(0):
-            ps1, pu1, pred_1, mask_1 = self._own_mask(sup[0][0], unsup[0][0], kw, segments)
+            ps1, pu1, pred_1, mask_1 = self._own_mask(sup[0][0], unsup[0][0], kw, segments, salient)
         with g.on(1):
-            ps2, pu2, pred_2, mask_2 = self._own_mask(sup[1][0], unsup[1][0], kw, segments)
+            ps2, pu2, pred_2, mask_2 = self._own_mask(sup[1][0], unsup[1][0], kw, segments, salient)
         g.exchange(mask_1, mask_2)
         crit, fused = self._criterion(cls_weight, pred_1)
         soft = cfg.unsup_criterion is not None                          # the unlabelled half of the CPS terms is _soft_cps's
@@ -529,6 +571,10 @@ class CPSTrainer:
             if segments is not None:                                    # the unpooled logits of network 1, and what the terms are restated from
                 raw_s, raw_u = sup[0][0].detach().float(), unsup[0][0].detach().float()
                 self.aux.update(pred_sup_1_unpooled=raw_s, pred_ul_1_unpooled=raw_u, pred_1=pred_1.detach(), pred_2=pred_2.detach())
+                g.to_caller(raw_s, raw_u, pred_1, pred_2)
+            if salient is not None:                                     # the unmasked logits of network 1, and what the terms are restated from
+                raw_s, raw_u = sup[0][0].detach().float(), unsup[0][0].detach().float()
+                self.aux.update(pred_sup_1_unmasked=raw_s, pred_ul_1_unmasked=raw_u, pred_1=pred_1.detach(), pred_2=pred_2.detach())
                 g.to_caller(raw_s, raw_u, pred_1, pred_2)
             if cls_weight is not None or not isinstance(self.criterion, DiceLoss):     # what the criterion arms' terms are restated from
                 self.aux.update(pred_1=pred_1.detach(), pred_2=pred_2.detach(), class_weight=cls_weight)

@@ -5,3 +5,4 @@ from .seed import seed_everything  # noqa: F401
 from .device import device_setting  # noqa: F401
 from .ckpoints import save_ckpoints, load_ckpoints  # noqa: F401
 from .superpixel import slic, superpixel_mean, superpixel_grid  # noqa: F401
+from .saliency import saliency_rbd, saliency_rbd_from_labels, salient_masking  # noqa: F401

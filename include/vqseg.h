@@ -1022,6 +1022,50 @@ int vqseg_rbd_solve_f(const float* g, const float* stats, const uint8_t* adj, co
                       float sigma_clr, float mu, float* work, float* wctr_norm, float* x, float* xnorm, void* stream);
 int vqseg_rbd_paint_f(const float* xnorm, const int32_t* labels, int b, int h, int w, int gy, int gx, float* sal, void* stream);
 
+/* ---------------------------------------------------------------------------------- *
+ * Photometric strong augmentation: colour jitter, grayscale and Gaussian blur of an RGB batch, one parameter row per sample
+ * (vq_seg_amd.data.augmentations.photometric / StrongPhotometric; CPSConfig.hard_aug = "photometric").  No reference counterpart (its
+ * hard augmentation stops at CutMix) and no parity with torchvision or PIL is claimed: THIS is the definition, restated in float64 by
+ * tests/photometric_cases.py.
+ *
+ * x: (n, 3, h, w) f32, RGB planes, values meant to lie in [0, 1]; NaN is unspecified.  Sample s has the row (b, c, sat, hue, gray,
+ * sigma).  The ops run in this order, all arithmetic in f32.  An op whose parameter has its identity value is SKIPPED, not evaluated,
+ * and a sample whose six parameters are all identity is copied bit for bit (no clamp).  g(p) = 0.299 r + 0.587 g + 0.114 b.
+ *   1 brightness (identity b = 1)     p = clamp(b p, 0, 1)
+ *   2 contrast   (identity c = 1)     p = clamp(c p + (1 - c) m, 0, 1),  m = the mean of g over all h w pixels of the sample after step 1
+ *   3 saturation (identity sat = 1)   p = clamp(sat p + (1 - sat) g(p), 0, 1)
+ *   4 hue        (identity hue = 0; |hue| <= 0.5)   RGB -> HSV, h = (h + hue) mod 1, HSV -> RGB by the hexcone formulas:
+ *         v = max, cr = max - min, s = cr / max (0 when cr == 0); rc = (max - r) / cr, gc, bc likewise (divisor 1 when cr == 0);
+ *         h6 = bc - gc if max == r, else 2 + rc - bc if max == g, else 4 + gc - rc;  h = (h6 / 6 + 1) mod 1
+ *         back: i = floor(6 h), f = 6 h - i, i mod 6;  p_ = clamp(v (1 - s)), q = clamp(v (1 - f s)), t = clamp(v (1 - (1 - f) s));
+ *         (r, g, b) = (v, t, p_), (q, v, p_), (p_, v, t), (p_, q, v), (t, p_, v), (v, p_, q) for i = 0..5
+ *   5 grayscale  (identity gray = 0)  r = g = b = g(p)
+ *   6 blur       (identity sigma = 0) R = ceil(3 sigma), 1 <= R <= 8; taps w_i = exp(-i^2 / 2 sigma^2) / sum_j exp(-j^2 / 2 sigma^2), i in
+ *         [-R, R], computed on the HOST in float64 and rounded to f32; rows first, then columns, each plane on its own; reflect-101
+ *         borders (index -i -> i, n - 1 + i -> n - 1 - i), which needs R <= min(h, w) - 1
+ *
+ *   src, out              out of place, the same layout and sample stride; src is never written
+ *   stride_s/_p/_px       sample, plane and pixel strides in ELEMENTS, rows dense: planar (pixel stride 1, plane stride h * w) or interleaved
+ *                         (plane stride 1, pixel stride 3: channels_last); anything else is VQSEG_EINVAL
+ *   params_host [n][6]    HOST rows (b, c, sat, hue, gray, sigma): finite; b, c, sat, sigma >= 0; gray 0 or 1
+ *   radii_host  [n]       HOST R per sample: 0 exactly where sigma is 0
+ *   taps_host   [n][9]    HOST w_0 .. w_8 per sample (w_-i = w_i), 0 beyond R
+ *   partials              device workspace of n * vqseg_photometric_mean_blocks(h w) floats; required when some c != 1, else may be null
+ *   means                 null, or n device floats: means[s] = m of every sample with c != 1 (the others are not written)
+ * Parameters and taps travel as kernel arguments, 32 samples per launch: no device allocation, no host-to-device copy, no
+ * synchronisation.  Per launch: a mean pass when one of its samples has c != 1 (per-(sample, workgroup) partial sums in a fixed order,
+ * folded by the main pass in a fixed order; NO atomics: two calls agree bit for bit, and a sample's result does not depend on the batch
+ * it travels in, nor on the layout), then the main pass: a workgroup owns a 16 x 64 tile of output pixels, evaluates steps 1-5 for the
+ * tile plus an R-wide reflected halo into LDS and runs the row and the column pass from there; sigma = 0 takes no halo and no stencil,
+ * an all-identity row a copy.  The blur adds the two taps of equal weight first and accumulates from the outermost pair inwards.
+ * vqseg_photometric_mean_blocks: the workgroups P (1..64) that share a sample's reduction, a function of the pixel count alone; pixel
+ * q goes to thread q % (256 P), so a thread adds ceil(h w / (256 P)) values in sequence and the folds add 6 + 2 + 6 levels.
+ * ---------------------------------------------------------------------------------- */
+int vqseg_photometric_mean_blocks(int64_t pixels);
+int vqseg_photometric_f(const float* src, float* out, int n, int h, int w, int64_t stride_s, int64_t stride_p, int64_t stride_px,
+                        const float* params_host, const int32_t* radii_host, const float* taps_host, float* partials, float* means,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

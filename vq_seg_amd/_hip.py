@@ -11,6 +11,8 @@ nothing is kept between the two.
 from __future__ import annotations
 
 import ctypes
+import functools
+import math
 import os
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 from typing import Optional, Tuple
@@ -174,6 +176,8 @@ SYMBOLS = {
     "vqseg_rbd_contrast_f": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] + [c_void_p] * 2),
     "vqseg_rbd_solve_f": (c_int, [c_void_p] * 5 + [c_int] * 2 + [c_float] * 2 + [c_void_p] * 5),
     "vqseg_rbd_paint_f": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 2),
+    "vqseg_photometric_mean_blocks": (c_int, [c_int64]),
+    "vqseg_photometric_f": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_int64] * 3 + [c_void_p] * 6),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -701,6 +705,120 @@ def affine_warp(src: torch.Tensor, matrices, mode: str = "bilinear", fill=0, out
            *inner, mats.ctypes.data, bits)
     AFFINE_WARP_CALLS += 1
     return out
+
+
+PHOTOMETRIC_CALLS = 0         # calls of photometric that reached the library (as BOX_MIX_CALLS: for tests, never read by the product)
+PHOTOMETRIC_MAX_RADIUS = 8    # include/vqseg.h: R = ceil(3 sigma) <= 8
+PHOTOMETRIC_ARG_SAMPLES = 32  # parameter rows per launch (csrc/photometric_kernels.hip: PHOTO_ARG_SAMPLES)
+PHOTOMETRIC_MEAN_THREADS = 256        # the mean pass: pixel q of a sample goes to thread q % (256 P), P = photometric_mean_blocks(h w)
+PHOTOMETRIC_MEAN_FOLD_LEVELS = 6 + 2 + 6      # wave shuffle tree, the workgroup's four wave sums pairwise, the main pass's tree over the P partials
+
+
+def photometric_mean_blocks(pixels: int) -> int:
+    """vqseg_photometric_mean_blocks: the workgroups (1..64) that share one sample's mean reduction, a function of h * w alone"""
+    p = lib().vqseg_photometric_mean_blocks(int(pixels))
+    if p <= 0:
+        raise _failed(lib(), "vqseg_photometric_mean_blocks", p)
+    return p
+
+
+def photometric_mean_run(pixels: int) -> int:
+    """the longest run of values one thread of the mean pass adds in sequence"""
+    per = PHOTOMETRIC_MEAN_THREADS * photometric_mean_blocks(pixels)
+    return (int(pixels) + per - 1) // per
+
+
+def photometric_radius(sigma: float) -> int:
+    """R = ceil(3 sigma) in float64 (0 for sigma = 0)"""
+    return int(math.ceil(3.0 * float(sigma)))
+
+
+@functools.lru_cache(maxsize=4096)
+def _half_taps(sigma: float):
+    """(R, [w_0 .. w_R]) in float64: exp(-i^2 / 2 sigma^2) over the exactly rounded sum of all 2R + 1 of them (math.fsum: no order of
+    addition to state).  Plain Python floats: a step draws one sigma per sample, and this runs on the host inside the step."""
+    if not (math.isfinite(sigma) and sigma >= 0.0):
+        raise ValueError(f"photometric_taps: sigma must be finite and >= 0, got {sigma!r}")
+    r = photometric_radius(sigma)
+    if r > PHOTOMETRIC_MAX_RADIUS:
+        raise ValueError(f"photometric_taps: sigma {sigma} gives the radius ceil(3 sigma) = {r}, above {PHOTOMETRIC_MAX_RADIUS}")
+    if r == 0:
+        return 0, (1.0,)
+    e = [math.exp(-(i * i) / (2.0 * sigma * sigma)) for i in range(r + 1)]
+    total = math.fsum(e + e[1:])
+    return r, tuple(v / total for v in e)
+
+
+def photometric_taps(sigma: float) -> np.ndarray:
+    """the 2R + 1 float32 taps of the blur, R = ceil(3 sigma): exp(-i^2 / 2 sigma^2) normalised, computed in float64 and rounded once;
+    symmetric by construction.  sigma = 0: the single tap 1."""
+    r, half = _half_taps(float(sigma))
+    return np.asarray(half[:0:-1] + half, dtype=np.float32)
+
+
+def photometric_rows(params, n: int, h: int, w: int):
+    """-> (params float32 (n, 6), radii int32 (n,), taps float32 (n, 9)) of n host rows (b, c, sat, hue, gray, sigma), checked: what
+    both the kernel and the torch-op form of the definition are handed.  The rows are rounded to float32 FIRST: a sample's taps are
+    those of its float32 sigma.  ValueError for what the definition excludes."""
+    try:
+        rows = np.ascontiguousarray(params, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("photometric: params must be n rows of six numbers (b, c, sat, hue, gray, sigma)") from None
+    if rows.shape != (n, 6):
+        raise ValueError(f"photometric: one (b, c, sat, hue, gray, sigma) row per sample required: {n} samples, params of shape {rows.shape}")
+    if not np.isfinite(rows).all():
+        raise ValueError("photometric: a parameter is not finite")
+    if (rows[:, (0, 1, 2, 5)] < 0).any():
+        raise ValueError("photometric: brightness, contrast, saturation and sigma must be >= 0")
+    if (np.abs(rows[:, 3]) > 0.5).any():
+        raise ValueError("photometric: |hue| must be <= 0.5")
+    if not np.isin(rows[:, 4], (0.0, 1.0)).all():
+        raise ValueError("photometric: gray must be 0 or 1")
+    radii, taps, pad = [], [], (0.0,) * PHOTOMETRIC_MAX_RADIUS
+    for sigma in rows[:, 5].tolist():
+        r, half = _half_taps(sigma) if sigma else (0, (1.0,))                # ValueError for R > 8
+        if r > min(h, w) - 1:
+            raise ValueError(f"photometric: sigma {sigma} gives the radius {r}, above min(h, w) - 1 = {min(h, w) - 1} (reflect-101 borders)")
+        radii.append(r)
+        taps.append((half + pad)[:PHOTOMETRIC_MAX_RADIUS + 1])
+    return rows, np.asarray(radii, dtype=np.int32), np.asarray(taps, dtype=np.float32).reshape(n, PHOTOMETRIC_MAX_RADIUS + 1)
+
+
+def photometric(src: torch.Tensor, params, out: Optional[torch.Tensor] = None, return_means: bool = False):
+    """The photometric strong augmentation of a batch (include/vqseg.h: vqseg_photometric_f): src (n, 3, h, w) float32, NCHW-contiguous or
+    channels_last; `params`: n host rows (b, c, sat, hue, gray, sigma).  Out of place: returns `out` (default: a new tensor of src's
+    layout); src is not written.  `return_means`: -> (out, means), means (n,) float32 holding the contrast op's per-sample mean for the
+    rows with c != 1 and 0 elsewhere."""
+    global PHOTOMETRIC_CALLS
+    if not isinstance(src, torch.Tensor) or src.dim() != 4 or src.shape[1] != 3:
+        raise ValueError("photometric: src must be a (n, 3, h, w) tensor of RGB planes")
+    if src.dtype != torch.float32:
+        raise ValueError(f"photometric: src must be float32, got {src.dtype}")
+    n, _c, h, w = src.shape
+    rows, radii, taps = photometric_rows(params, n, h, w)
+    numel = n * 3 * h * w
+    sp = tptr(src, "src", dtype=torch.float32, numel=numel)
+    if numel == 0:
+        raise HipLibraryError("photometric: empty tensor")
+    if out is None:
+        out = torch.empty_like(src)                          # dense src: the same strides
+    elif not isinstance(out, torch.Tensor) or out.shape != src.shape or out.stride() != src.stride():
+        raise HipLibraryError("photometric: out must have src's shape and layout")
+    op = tptr(out, "out", dtype=torch.float32, numel=numel)
+    if type(sp) is int and type(op) is int and sp == op:
+        raise HipLibraryError("photometric: out of place only")
+    strides = (3 * h * w, h * w, 1) if src.is_contiguous() else (3 * h * w, 1, 3)
+    need_mean = bool((rows[:, 1] != 1.0).any())
+    partials = means = None
+    if src.is_cuda and (need_mean or return_means):
+        if need_mean:
+            partials = torch.empty(n * photometric_mean_blocks(h * w), dtype=torch.float32, device=src.device)
+        if return_means:
+            means = torch.zeros(n, dtype=torch.float32, device=src.device)
+    launch("vqseg_photometric_f", src.device, sp, op, n, h, w, *strides, rows.ctypes.data, radii.ctypes.data, taps.ctypes.data,
+           partials.data_ptr() if partials is not None else None, means.data_ptr() if means is not None else None)
+    PHOTOMETRIC_CALLS += 1
+    return (out, means) if return_means else out
 
 
 RENDER_KINDS = {"image": 0, "target": 1, "pred": 2, "detail": 3, "mix_pred": 4, "mix_detail": 5, "fill": 6}     # include/vqseg.h: vqseg_render_sheet_u8

@@ -23,6 +23,19 @@ tensors -- grid_sample, align_corners=False, zero fill, positive = counter-clock
 interpolates integer class maps bilinearly, which invents classes between two labels; integer and bool tensors here take the NEAREST
 source pixel (and `fill` outside the image).  Flips, quarter turns on square images and the identity pass every bit pattern through,
 on either device.
+
+Photometric strong augmentation (no reference counterpart: its hard augmentation stops at CutMix; this is the colour half of the
+FixMatch / UniMatch strong view that deprecated/train_vqpt_easyhard_aug.py and deprecated/train_UNIMatch.py belong to).  What is
+defined HERE, once, in include/vqseg.h (vqseg_photometric_f) and restated in float64 by tests/photometric_cases.py: six ops per sample
+in a fixed order -- brightness, contrast (about the sample's mean gray), saturation, hue (hexcone RGB <-> HSV), grayscale, Gaussian
+blur (radius ceil(3 sigma) <= 8, reflect-101 borders, float32 taps made in float64 on the host) -- all in float32, an op at its
+identity value skipped, an all-identity row a copy of the bits.  Why fixed: a step's view must be a pure function of (seed, rank,
+iteration), and one order of ops is one kernel; the draws (`draw_photometric`, `step_photometric`) take exactly eight uniforms per
+sample under a generator key of their own, so neither the CutMix boxes nor the similarity transforms of a step move.  What is NOT
+torchvision's or PIL's, and is not claimed to be: torchvision's ColorJitter applies its four ops in a random order and blends
+contrast about the mean of ITS grayscale after ITS rounding, PIL's GaussianBlur is a box approximation; neither is a dependency, and
+the yardstick is the float64 restatement.  GPU tensors take the photometric kernel (`_hip.photometric`), CPU tensors the same
+definition with float32 torch ops (`photometric`); the two agree within float32 rounding, and exactly on identity rows.
 """
 from __future__ import annotations
 
@@ -282,6 +295,165 @@ def step_transforms(n: int, seed: int, rank: int, it: int, per: str = "batch", c
 
     pairs = [draw()] * int(n) if per == "batch" else [draw() for _ in range(int(n))]
     return [c for c, _a in pairs], [a for _c, a in pairs]
+
+
+# ---- photometric strong augmentation (colour jitter, grayscale, blur): the hard augmentation's colour half --------------------------
+
+PhotometricRow = Tuple[float, float, float, float, float, float]       # (b, c, sat, hue, gray, sigma)
+IDENTITY_PHOTOMETRIC: PhotometricRow = (1.0, 1.0, 1.0, 0.0, 0.0, 0.0)
+PHOTOMETRIC_DEFAULTS = dict(jitter=(0.5, 0.5, 0.5, 0.25), jitter_p=0.8, gray_p=0.2, blur_p=0.5, sigma=(0.1, 2.0))     # the FixMatch / UniMatch strong view
+
+photometric_taps = _hip.photometric_taps                    # the 2R + 1 float32 taps of a sigma (float64 on the host, rounded once)
+
+
+def check_photometric_ranges(jitter, jitter_p, gray_p, blur_p, sigma) -> None:
+    """ValueError unless the draw ranges can only give rows the definition admits: jitter = (B, C, S, Hh) with B, C, S in [0, 1] (factors
+    1 +- X stay >= 0) and Hh in [0, 0.5]; probabilities in [0, 1]; sigma = (lo, hi) with 0 <= lo <= hi <= 8 / 3 (R = ceil(3 sigma) <= 8)"""
+    try:
+        jit, sig = tuple(float(v) for v in jitter), tuple(float(v) for v in sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"photometric: jitter must be four numbers and sigma two, got {jitter!r} and {sigma!r}") from None
+    if len(jit) != 4 or not all(0.0 <= v <= 1.0 for v in jit[:3]) or not 0.0 <= jit[3] <= 0.5:
+        raise ValueError(f"photometric: jitter must be (B, C, S, Hh) with B, C, S in [0, 1] and Hh in [0, 0.5], got {jitter!r}")
+    for name, p in (("jitter_p", jitter_p), ("gray_p", gray_p), ("blur_p", blur_p)):
+        if isinstance(p, bool) or not 0.0 <= float(p) <= 1.0:
+            raise ValueError(f"photometric: {name} must be a probability, got {p!r}")
+    if len(sig) != 2 or not 0.0 <= sig[0] <= sig[1] <= _hip.PHOTOMETRIC_MAX_RADIUS / 3.0:
+        raise ValueError(f"photometric: sigma must be (lo, hi) with 0 <= lo <= hi <= {_hip.PHOTOMETRIC_MAX_RADIUS} / 3, got {sigma!r}")
+
+
+def draw_photometric(rng, jitter=(0.5, 0.5, 0.5, 0.25), jitter_p: float = 0.8, gray_p: float = 0.2, blur_p: float = 0.5,
+                     sigma=(0.1, 2.0)) -> PhotometricRow:
+    """one parameter row from EXACTLY eight uniforms u = rng.random(8) of a np.random.Generator, whatever the outcome: jitter on iff
+    u0 < jitter_p, then b = 1 + (2 u1 - 1) B, c = 1 + (2 u2 - 1) C, sat = 1 + (2 u3 - 1) S, hue = (2 u4 - 1) Hh (else their identity
+    values); gray = u5 < gray_p; blur on iff u6 < blur_p, with sigma = lo + u7 (hi - lo)"""
+    u = [float(v) for v in rng.random(8)]
+    (B, C, S, Hh), (lo, hi) = (float(v) for v in jitter), (float(v) for v in sigma)
+    b, c, sat, hue = IDENTITY_PHOTOMETRIC[:4]
+    if u[0] < jitter_p:
+        b, c, sat, hue = 1.0 + (2.0 * u[1] - 1.0) * B, 1.0 + (2.0 * u[2] - 1.0) * C, 1.0 + (2.0 * u[3] - 1.0) * S, (2.0 * u[4] - 1.0) * Hh
+    return b, c, sat, hue, 1.0 if u[5] < gray_p else 0.0, lo + u[7] * (hi - lo) if u[6] < blur_p else 0.0
+
+
+def step_photometric(n: int, seed: int, rank: int, it: int, per: str = "sample", jitter=(0.5, 0.5, 0.5, 0.25), jitter_p: float = 0.8,
+                     gray_p: float = 0.2, blur_p: float = 0.5, sigma=(0.1, 2.0)) -> List[PhotometricRow]:
+    """the n parameter rows of one training step as a pure function of (seed, rank, iteration): `per` "sample" = one draw per sample in
+    sample order, "batch" = one draw for all samples.  The generator is np.random.default_rng([seed, rank, it, 2]): a key neither
+    `step_generators` (three elements) nor `step_transforms` (key 1) uses, so a step's boxes and transforms do not depend on this
+    option; eight uniforms per draw (`draw_photometric`), so one sample's outcome never shifts another's."""
+    if per not in ("batch", "sample"):
+        raise ValueError(f"hard_aug_per must be 'batch' or 'sample', got {per!r}")
+    check_photometric_ranges(jitter, jitter_p, gray_p, blur_p, sigma)
+    rng = np.random.default_rng([int(seed), int(rank), int(it), 2])
+    if per == "batch":
+        return [draw_photometric(rng, jitter, jitter_p, gray_p, blur_p, sigma)] * int(n)
+    return [draw_photometric(rng, jitter, jitter_p, gray_p, blur_p, sigma) for _ in range(int(n))]
+
+
+def _gray(r, g, b):
+    return 0.299 * r + 0.587 * g + 0.114 * b
+
+
+def _hue_torch(r, g, b, hue: float):
+    """step 4 of the definition on float32 planes"""
+    mx, mn = torch.maximum(r, torch.maximum(g, b)), torch.minimum(r, torch.minimum(g, b))
+    v, cr = mx, mx - mn
+    flat = cr == 0
+    s = torch.where(flat, torch.zeros_like(cr), cr / torch.where(flat, torch.ones_like(mx), mx))
+    d = torch.where(flat, torch.ones_like(cr), cr)
+    rc, gc, bc = (mx - r) / d, (mx - g) / d, (mx - b) / d
+    h6 = torch.where(mx == r, bc - gc, torch.where(mx == g, 2.0 + rc - bc, 4.0 + gc - rc))
+    h = h6 / 6.0 + 1.0
+    h = h - torch.floor(h)
+    h = h + hue
+    h = h - torch.floor(h)
+    fi = torch.floor(6.0 * h)
+    f = 6.0 * h - fi
+    i = fi.long() % 6
+    p_, q, t = (v * (1.0 - s)).clamp(0.0, 1.0), (v * (1.0 - f * s)).clamp(0.0, 1.0), (v * (1.0 - (1.0 - f) * s)).clamp(0.0, 1.0)
+    pick = lambda opts: torch.stack(opts).gather(0, i[None])[0]
+    return pick([v, q, p_, p_, t, v]), pick([t, v, v, q, p_, p_]), pick([p_, p_, t, v, v, q])
+
+
+def _blur_torch(x: torch.Tensor, taps: np.ndarray, r: int) -> torch.Tensor:
+    """step 6 on (3, h, w) float32 planes: rows, then columns, reflect-101; the kernel's order of addition (pairs, outermost first)"""
+    pad = torch.nn.functional.pad
+    for dim in (2, 1):
+        padded = pad(x[None], (r, r, 0, 0) if dim == 2 else (0, 0, r, r), mode="reflect")[0]
+        n = x.shape[dim]
+        acc = torch.zeros_like(x)
+        for k in range(r, 0, -1):
+            acc = acc + float(taps[k]) * (padded.narrow(dim, r - k, n) + padded.narrow(dim, r + k, n))
+        x = acc + float(taps[0]) * padded.narrow(dim, r, n)
+    return x
+
+
+def _photometric_torch(t: torch.Tensor, rows: np.ndarray, radii: np.ndarray, taps: np.ndarray) -> torch.Tensor:
+    """the definition (include/vqseg.h: vqseg_photometric_f) with float32 torch ops, sample by sample: CPU tensors"""
+    out = torch.empty_like(t)
+    one = np.float32(1.0)
+    for s in range(t.shape[0]):
+        b, c, sat, hue, gray, _sigma = rows[s]              # float32 scalars: (1 - c) below is a float32 difference
+        r_ = int(radii[s])
+        if (b, c, sat, hue, gray, r_) == (1.0, 1.0, 1.0, 0.0, 0.0, 0):
+            out[s] = t[s]                                    # by bits
+            continue
+        r, g, bl = t[s, 0], t[s, 1], t[s, 2]
+        if b != 1.0:
+            r, g, bl = ((float(b) * p).clamp(0.0, 1.0) for p in (r, g, bl))
+        if c != 1.0:
+            o = float(one - c) * _gray(r, g, bl).mean()
+            r, g, bl = ((float(c) * p + o).clamp(0.0, 1.0) for p in (r, g, bl))
+        if sat != 1.0:
+            o = float(one - sat) * _gray(r, g, bl)
+            r, g, bl = ((float(sat) * p + o).clamp(0.0, 1.0) for p in (r, g, bl))
+        if hue != 0.0:
+            r, g, bl = _hue_torch(r, g, bl, float(hue))
+        if gray != 0.0:
+            r = g = bl = _gray(r, g, bl)
+        x = torch.stack([r, g, bl])
+        out[s] = _blur_torch(x, taps[s], r_) if r_ else x
+    return out
+
+
+def photometric(t: torch.Tensor, params) -> torch.Tensor:
+    """out[s] = t[s] through the photometric ops of params[s] = (b, c, sat, hue, gray, sigma) -- brightness, contrast, saturation, hue,
+    grayscale, Gaussian blur, in this order, identity values skipped (the definition: include/vqseg.h, vqseg_photometric_f; an
+    all-identity row returns the sample's bits).  t: (n, 3, H, W) float32 RGB in [0, 1], NCHW or channels_last; a new tensor of the
+    same layout.  On the GPU: the photometric kernel (a mean pass when a contrast is on, then one launch); CPU tensors: the same
+    definition with float32 torch ops.  ValueError: a tensor that is not (n, 3, H, W) float32, a row count other than n, |hue| > 0.5,
+    a sigma whose radius ceil(3 sigma) is above 8 or above min(H, W) - 1."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[1] != 3:
+        raise ValueError("photometric: a (n, 3, H, W) tensor of RGB planes required")
+    if t.dtype != torch.float32:
+        raise ValueError(f"photometric: a float32 tensor required, got {t.dtype}")
+    if t.is_cuda:
+        return _hip.photometric(_dense(t), params)
+    rows, radii, taps = _hip.photometric_rows(params, t.shape[0], t.shape[2], t.shape[3])
+    return _photometric_torch(t, rows, radii, taps)
+
+
+class StrongPhotometric:
+    """The strong view of weak-to-strong consistency training as a callable, for use outside the trainer: `__call__(batch) -> batch'`
+    draws one row per sample (`per` "sample") or one for the batch ("batch") with `draw_photometric` from this object's OWN
+    np.random.Generator (`seed`; None = fresh entropy) -- nothing is taken from the global generators -- and applies `photometric`.
+    `last_params`: the rows of the last call."""
+
+    def __init__(self, brightness: float = 0.5, contrast: float = 0.5, saturation: float = 0.5, hue: float = 0.25, jitter_p: float = 0.8,
+                 gray_p: float = 0.2, blur_p: float = 0.5, sigma=(0.1, 2.0), per: str = "sample", seed: Optional[int] = None):
+        if per not in ("batch", "sample"):
+            raise ValueError(f"per must be 'batch' or 'sample', got {per!r}")
+        self.draw = dict(jitter=(brightness, contrast, saturation, hue), jitter_p=jitter_p, gray_p=gray_p, blur_p=blur_p, sigma=tuple(sigma))
+        check_photometric_ranges(**self.draw)
+        self.per = per
+        self.rng = np.random.default_rng(seed)
+        self.last_params: List[PhotometricRow] = []
+
+    def __call__(self, batch: torch.Tensor) -> torch.Tensor:
+        n = batch.shape[0]
+        self.last_params = [draw_photometric(self.rng, **self.draw)] * n if self.per == "batch" else \
+            [draw_photometric(self.rng, **self.draw) for _ in range(n)]
+        return photometric(batch, self.last_params)
 
 
 class _BoxAug:

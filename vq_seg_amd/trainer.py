@@ -122,9 +122,28 @@ class CPSConfig:
                                               # are not masked.  None = today's step: nothing of it is entered
     salient_segments: int = 250               # saliency_rbd(n_segments): the reference's get_saliency_rbd default; SLIC with superpixel_compactness / _iters.
                                               # Equal to superpixel_mean: one SLIC run per batch serves both options
+    hard_aug: Optional[str] = None            # "photometric": the colour half of the strong view (data.augmentations.photometric; no reference counterpart,
+                                              # its hard augmentation stops at CutMix) -- the CLEAN unlabelled batch is colour-jittered, grayscaled and blurred
+                                              # once per step on the caller's stream (a mean pass + one launch of the photometric kernel), and the two
+                                              # unlabelled TRAINING forwards see it; CutMix, when on, mixes the distorted images.  Score maps are not touched
+                                              # (no pixel moves), nor are the pseudo-label forwards or the labelled batch.  None = today's step, nothing entered
+    hard_aug_per: str = "sample"              # "sample": one parameter row per image; "batch": one for the step
+    hard_aug_jitter: Sequence[float] = (0.5, 0.5, 0.5, 0.25)   # (B, C, S, Hh): brightness / contrast / saturation factors of 1 +- X, hue shift of +- Hh turns
+    hard_aug_jitter_p: float = 0.8            # the probabilities of the jitter, the grayscale and the blur (the usual FixMatch / UniMatch strong view)
+    hard_aug_gray_p: float = 0.2
+    hard_aug_blur_p: float = 0.5
+    hard_aug_sigma: Sequence[float] = (0.1, 2.0)              # blur sigma drawn of [lo, hi]; radius ceil(3 sigma) <= 8
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
+        if self.hard_aug not in (None, "photometric"):
+            raise ValueError(f"hard_aug must be None or 'photometric', got {self.hard_aug!r}")
+        if self.hard_aug_per not in ("batch", "sample"):
+            raise ValueError(f"hard_aug_per must be 'batch' or 'sample', got {self.hard_aug_per!r}")
+        augmentations.check_photometric_ranges(self.hard_aug_jitter, self.hard_aug_jitter_p, self.hard_aug_gray_p, self.hard_aug_blur_p,
+                                               self.hard_aug_sigma)
+        self.hard_aug_jitter = tuple(float(v) for v in self.hard_aug_jitter)
+        self.hard_aug_sigma = tuple(float(v) for v in self.hard_aug_sigma)
         if self.ema_decay is not None and not 0.0 <= float(self.ema_decay) < 1.0:
             raise ValueError(f"ema_decay must be None or lie in [0, 1), got {self.ema_decay!r}")
         if self.teacher_pseudo_labels and self.ema_decay is None:
@@ -349,7 +368,7 @@ class CPSTrainer:
         if cfg.keep_aux:
             self.aux = {}
         score_1, score_2 = self._pseudo_scores(ul_input)
-        ul_train, score_1, score_2 = self._cutmix(ul_input, score_1, score_2)
+        ul_train, score_1, score_2 = self._cutmix(self._photometric(ul_input), score_1, score_2)
         gt_ul_1, gt_ul_2, kw = self._targets(score_1, score_2, epoch_frac)
         segments = self._superpixels(l_input, ul_train)
         salient = self._saliency(l_input, ul_train, segments)
@@ -408,6 +427,24 @@ class CPSTrainer:
             self.aux.update(score_1=score_1, score_2=score_2)
             g.to_caller(score_1, score_2)
         return score_1, score_2
+
+    @torch.no_grad()
+    def _photometric(self, ul_input):
+        """cfg.hard_aug -> the clean unlabelled batch through the step's photometric rows (colour jitter, grayscale, blur): the images
+        the unlabelled training forwards (and CutMix before them) receive; else the batch as it came, and nothing is entered."""
+        cfg, g = self.cfg, self._glue
+        if cfg.hard_aug is None:
+            return ul_input
+        # rows on the host, a pure function of (seed, rank, iteration[, sample]) under a key of their own (the boxes and the easy
+        # transforms of the step do not move).  Distorted ONCE on the caller's stream (both networks get the same tensor object: one stem
+        # patch matrix); the score maps stay as they are -- no pixel moves
+        rows = augmentations.step_photometric(ul_input.shape[0], cfg.seed, vdist.rank(), self.iter, cfg.hard_aug_per, cfg.hard_aug_jitter,
+                                              cfg.hard_aug_jitter_p, cfg.hard_aug_gray_p, cfg.hard_aug_blur_p, cfg.hard_aug_sigma)
+        ul_hard = augmentations.photometric(ul_input, rows)
+        g.share(ul_hard)
+        if cfg.keep_aux:
+            self.aux.update(ul_photometric=ul_hard, photometric_params=list(rows))
+        return ul_hard
 
     @torch.no_grad()
     def _cutmix(self, ul_input, score_1, score_2):

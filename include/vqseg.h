@@ -17,6 +17,16 @@
  *     supplies a workspace of at least the size the matching *_workspace_bytes() returns;
  *   - return value: 0 = success, otherwise a negative VQSEG_E* code or a positive
  *     hipError_t; vqseg_last_error() returns a message for the calling thread;
+ *   - alignment: activation tensors, weight images and workspaces are 16-byte aligned wherever a kernel moves them in 16-byte
+ *     vectors, and the entry point checks it (VQSEG_EINVAL, nothing enqueued).  Besides the pointers named at the entry points
+ *     below that is: y / res / out of vqseg_bn_apply_f / vqseg_bn_apply_bits_f, g_out / out / y / g_y / g_res of vqseg_bn_backward_f / _bits_f, x / g /
+ *     out / gx_add / gx of the max-pool entry points, src / dst of vqseg_bilinear_f and gp / gx of vqseg_reflect_fold_f when the
+ *     channel count is a multiple of 8 (bf16) or 4 (fp32) -- with any other channel count a thread moves one channel and the
+ *     element's own alignment is enough; the images the four weight-pack entry points write; the 7x7x3 patch rows of vqseg_im2col_f with kp % 8 == 0; gy / x / x2 of the weight-gradient
+ *     entry points; the workspaces of the BatchNorm backward, head backward and weight-gradient entry points.
+ *     Per-channel fp32 vectors (scale, shift, gamma, statistics, dgamma ...), the head's weights, gradients and logits, fp32 images
+ *     read by vqseg_im2col_f, the buffers of vqseg_cast_f, scalars, counters and the uint8 index / bit tensors need only their
+ *     element's alignment;
  *   - activations are "rows": N = B*H*W pixel rows of C contiguous channels (NHWC /
  *     torch channels_last), which is the (B, HW, C) frame vq_img.py:232 rearranges into.
  */
@@ -149,7 +159,8 @@ int vqseg_vq_forward_f32(const float* x, const float* codebook, const void* prep
  * its logical value the fp32 sum hi + lo (what vqseg_s3_merge_f writes): idx is that of the f32 call on the merged rows, and quant[i]
  * is [n_rows][2 * channels] bf16 = the split of the winning fp32 code rows, byte for byte vqseg_s3_split_f of the f32 call's quant.
  * Split-3 rows are an eval-mode format: bf16 = 2 needs training = 0 and channels % 8 == 0 (VQSEG_EINVAL otherwise, nothing is
- * launched).  Results are bit-identical to n_levels single calls. */
+ * launched).  Every level is checked before anything is enqueued: a refused call (VQSEG_EINVAL, VQSEG_ENOSPC) has written nothing,
+ * not even the prepared codebooks of the levels in front of the offending one.  Results are bit-identical to n_levels single calls. */
 int vqseg_vq_forward_group(int n_levels, int bf16, const void* const* x, const float* const* codebook,
                            const void* const* prepared, const int64_t* n_rows, const int* channels, const int* n_codes,
                            int training, const float* commitment_weight, void* const* quant, int64_t* const* idx,
@@ -186,7 +197,8 @@ int vqseg_vq_assign_s3(const void* x, const float* codebook, const void* prepare
  * interleaved, code-padded copy + |e_k|^2).  The reference's codebook never changes after
  * its k-means init (no gradient, no EMA -- vq_img.py:236-239), so callers prepare once
  * and pass the blob to every forward; `prepared == NULL` makes forward/assign prepare
- * into the workspace on every call instead. */
+ * into the workspace on every call instead.  The blob is opaque: its parts start at 256-byte boundaries, and the bytes of the
+ * gaps between them (and of parts a shape does not use) are unspecified -- vqseg_vq_prepare_f32 need not write them. */
 size_t vqseg_vq_prepared_bytes(int channels, int n_codes);
 int vqseg_vq_prepare_f32(const float* codebook, int channels, int n_codes, void* prepared,
                          size_t prepared_bytes, void* stream);
@@ -224,6 +236,8 @@ int vqseg_vq_backward_bf16(const void* grad_quant, const float* grad_loss, const
  * at 1e-5 in tests/test_vq_gpu.py).
  *
  *   samples [N, C] f32, means [K, C] f32 in/out, bins [K] i64 out (last iteration).
+ *   samples, means and the workspace are 16-byte aligned (read in 16-byte vectors; checked: VQSEG_EINVAL); sums, counts, bins and
+ *   the means of vqseg_kmeans_finalize_f32 need only their element's alignment.
  *
  * Data-parallel use: vqseg_kmeans_accumulate_f32 produces this rank's sums/counts so
  * the host can all-reduce them (RCCL) before vqseg_kmeans_finalize_f32.

@@ -24,6 +24,8 @@ int hipfail(hipError_t e, const char* where) {
 bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int conv_rows_per_slot(int cout) { return cout >= 64 ? 64 : 32; }
+// the row kernels (dispatch_rows, bn_apply / bn_backward) move 16-byte vectors -- 8 bf16 / 4 fp32 channels -- when the channel count allows
+bool rows_vec(int bf16, int c) { return bf16 ? c % 8 == 0 : c % 4 == 0; }
 }  // namespace
 
 extern "C" {
@@ -36,6 +38,7 @@ size_t vqseg_conv_packed_elems(int cout, int cin, int kh, int kw, int transpose_
 int vqseg_conv_pack_weights_f32(const float* w, int cout, int cin, int kh, int kw, int transpose_flip, void* hi, void* lo,
                                 void* stream) {
     if (!w || !hi || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0) return bad("conv_pack_weights: bad argument");
+    if (!a16(hi) || !a16(lo)) return bad("conv_pack_weights: the images must be 16-byte aligned");
     hipError_t e = vqseg::launch_pack_weights(w, cout, cin, kh, kw, transpose_flip, static_cast<unsigned short*>(hi),
                                               static_cast<unsigned short*>(lo), static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "conv_pack_weights");
@@ -150,6 +153,8 @@ int vqseg_conv2d_wgrad2_f(const void* gy, const void* x, const void* x2, int n, 
     if (!gy || !x || !workspace || !gw) return bad("conv2d_wgrad: null pointer");
     if (n <= 0 || n_b < 0) return bad("conv2d_wgrad: bad image count");
     if (n_b > 0 && (!gy_b || !x_b)) return bad("conv2d_wgrad: second source missing");
+    if (!a16(gy) || !a16(x) || !a16(x2) || !a16(gy_b) || !a16(x_b) || !a16(x2_b) || !a16(workspace))
+        return bad("conv2d_wgrad: gy, x, x2 and the workspace must be 16-byte aligned");
     const int epc = precise ? 4 : 8;
     if (cin % epc || cout % epc) return bad("conv2d_wgrad: Cin and Cout must be multiples of 4 (f32) / 8 (bf16)");
     if (c1 <= 0 || c1 > cin || (c1 < cin && (!x2 || (n_b > 0 && !x2_b) || c1 % epc || (cin - c1) % epc))) return bad("conv2d_wgrad: bad channel split");
@@ -202,6 +207,7 @@ int vqseg_bn_finalize_f(float* partial, int64_t m_rows, int c, const float* gamm
 int vqseg_bn_apply_f(int bf16, const void* y, const void* res, const float* scale, const float* shift, int64_t m_rows, int c,
                      int relu, void* out, void* stream) {
     if (!y || !scale || !shift || !out || c <= 0 || m_rows <= 0) return bad("bn_apply: bad argument");
+    if (rows_vec(bf16, c) && (!a16(y) || !a16(res) || !a16(out))) return bad("bn_apply: y, res and out must be 16-byte aligned (channels % 8 bf16 / % 4 fp32)");
     hipError_t e = vqseg::launch_bn_apply(bf16, y, res, scale, shift, m_rows, c, relu, out, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "bn_apply_kernel");
 }
@@ -210,6 +216,7 @@ int vqseg_bn_apply_bits_f(const void* y, const void* res, const float* scale, co
                           unsigned char* bits, void* stream) {
     if (!y || !scale || !shift || !out || !bits || c <= 0 || m_rows <= 0) return bad("bn_apply_bits: bad argument");
     if (c % 8) return bad("bn_apply_bits: the channel count must be a multiple of 8");
+    if (!a16(y) || !a16(res) || !a16(out)) return bad("bn_apply_bits: y, res and out must be 16-byte aligned");
     hipError_t e = vqseg::launch_bn_apply(1, y, res, scale, shift, m_rows, c, 1, out, static_cast<hipStream_t>(stream), bits);
     return e == hipSuccess ? 0 : hipfail(e, "bn_apply_kernel");
 }
@@ -227,6 +234,9 @@ int vqseg_bn_backward_f(int bf16, const void* g_out, const void* out, const void
     if (relu && !out && (!fwd_scale || !fwd_shift)) return bad("bn_backward: with ReLU pass either `out` or the forward scale/shift");
     if (relu && !out && g_res) return bad("bn_backward: a residual branch needs `out` (the mask depends on the residual)");
     if (c <= 0 || m_rows <= 0) return bad("bn_backward: bad size");
+    if (!a16(workspace)) return bad("bn_backward: the workspace must be 16-byte aligned");
+    if (rows_vec(bf16, c) && (!a16(g_out) || !a16(out) || !a16(y) || !a16(g_y) || !a16(g_res)))
+        return bad("bn_backward: g_out, out, y, g_y and g_res must be 16-byte aligned (channels % 8 bf16 / % 4 fp32)");
     float* partial = workspace;
     float* coef = workspace + (size_t)vqseg::bn_bwd_blocks(m_rows) * 2 * c;
     hipError_t e = vqseg::launch_bn_backward(bf16, g_out, out, y, mean, invstd, gamma, fwd_scale, fwd_shift, m_rows, c, relu, training, accumulate, partial, coef,
@@ -241,6 +251,7 @@ int vqseg_bn_backward_bits_f(const void* g_out, const unsigned char* bits, const
         return bad("bn_backward_bits: null pointer");
     if (c <= 0 || c % 8) return bad("bn_backward_bits: the channel count must be a multiple of 8");
     if (m_rows <= 0) return bad("bn_backward_bits: bad size");
+    if (!a16(workspace) || !a16(g_out) || !a16(y) || !a16(g_y) || !a16(g_res)) return bad("bn_backward_bits: g_out, y, g_y, g_res and the workspace must be 16-byte aligned");
     float* partial = workspace;
     float* coef = workspace + (size_t)vqseg::bn_bwd_blocks(m_rows) * 2 * c;
     hipError_t e = vqseg::launch_bn_backward(1, g_out, nullptr, y, mean, invstd, gamma, nullptr, nullptr, m_rows, c, 1, training, accumulate, partial,
@@ -252,6 +263,7 @@ int vqseg_maxpool3x3s2_f(int bf16, int backward, const void* x, const void* g, i
                          unsigned char* idx, void* stream) {
     if (!out || (!x && !(backward && idx)) || (backward && !g)) return bad("maxpool: null pointer");
     if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return bad("maxpool: bad size");
+    if (rows_vec(bf16, c) && (!a16(x) || !a16(g) || !a16(out))) return bad("maxpool: x, g and out must be 16-byte aligned (channels % 8 bf16 / % 4 fp32)");
     hipError_t e = vqseg::launch_maxpool(bf16, backward, x, g, n, h, w, c, out, idx, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "maxpool");
 }
@@ -259,6 +271,7 @@ int vqseg_maxpool3x3s2_f(int bf16, int backward, const void* x, const void* g, i
 int vqseg_bilinear_f(int bf16, int backward, const void* src, int n, int h, int w, int c, int ho, int wo, int align_corners,
                      void* dst, void* stream) {
     if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || c <= 0 || ho <= 0 || wo <= 0) return bad("bilinear: bad argument");
+    if (rows_vec(bf16, c) && (!a16(src) || !a16(dst))) return bad("bilinear: src and dst must be 16-byte aligned (channels % 8 bf16 / % 4 fp32)");
     hipError_t e = vqseg::launch_bilinear(bf16, backward, src, n, h, w, c, ho, wo, align_corners, dst, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "bilinear");
 }
@@ -277,8 +290,9 @@ size_t vqseg_head1x1_backward_workspace_floats(int64_t m_rows, int cin, int cout
 
 int vqseg_head1x1_backward_f(int bf16, const void* x, const float* w, const float* g, int64_t m_rows, int cin, int cout, void* gx,
                              float* gw, float* workspace, void* stream) {
-    if (!x || !w || !g || !gx || !gw || !workspace || cout > 4 || cout <= 0 || cin <= 0 || cin * cout > 256 || cin % 8 || cin > 64 || !a16(x) || !a16(gx))
-        return bad("head1x1 backward: bad argument (Cout <= 4, Cin % 8 == 0, Cin <= 64, 16-byte aligned rows)");
+    if (!x || !w || !g || !gx || !gw || !workspace || cout > 4 || cout <= 0 || cin <= 0 || cin * cout > 256 || cin % 8 || cin > 64 || !a16(x) || !a16(gx) ||
+        !a16(workspace))
+        return bad("head1x1 backward: bad argument (Cout <= 4, Cin % 8 == 0, Cin <= 64, 16-byte aligned rows and workspace)");
     hipError_t e = vqseg::launch_head_bwd(bf16, x, w, g, m_rows, cin, cout, gx, gw, workspace, nullptr, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "head_bwd");
 }
@@ -286,8 +300,8 @@ int vqseg_head1x1_backward_f(int bf16, const void* x, const float* w, const floa
 int vqseg_head1x1_backward_add_f(int bf16, const void* x, const float* w, const float* g, int64_t m_rows, int cin, int cout, void* gx,
                                  float* gw, float* workspace, const void* gx_add, void* stream) {
     if (!x || !w || !g || !gx || !gw || !workspace || cout > 4 || cout <= 0 || cin <= 0 || cin * cout > 256 || cin % 8 || cin > 64 || !a16(x) || !a16(gx) ||
-        !a16(gx_add))
-        return bad("head1x1 backward: bad argument (Cout <= 4, Cin % 8 == 0, Cin <= 64, 16-byte aligned rows)");
+        !a16(gx_add) || !a16(workspace))
+        return bad("head1x1 backward: bad argument (Cout <= 4, Cin % 8 == 0, Cin <= 64, 16-byte aligned rows and workspace)");
     hipError_t e = vqseg::launch_head_bwd(bf16, x, w, g, m_rows, cin, cout, gx, gw, workspace, gx_add, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "head_bwd");
 }
@@ -295,6 +309,7 @@ int vqseg_head1x1_backward_add_f(int bf16, const void* x, const float* w, const 
 int vqseg_maxpool3x3s2_backward_add_f(int bf16, const void* g, const unsigned char* idx, const void* gx_add, int n, int h, int w, int c,
                                       void* gx, void* stream) {
     if (!g || !idx || !gx || n <= 0 || h <= 0 || w <= 0 || c <= 0) return bad("maxpool backward: null pointer or bad size");
+    if (rows_vec(bf16, c) && (!a16(g) || !a16(gx_add) || !a16(gx))) return bad("maxpool backward: g, gx_add and gx must be 16-byte aligned (channels % 8 bf16 / % 4 fp32)");
     hipError_t e = vqseg::launch_maxpool(bf16, gx_add ? 2 : 1, gx_add, g, n, h, w, c, gx, const_cast<unsigned char*>(idx), static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "maxpool");
 }
@@ -302,6 +317,7 @@ int vqseg_maxpool3x3s2_backward_add_f(int bf16, const void* g, const unsigned ch
 int vqseg_im2col_f(int out_bf16, const float* x, int n, int h, int w, int cin, int kh, int kw, int stride, int pad, int reflect,
                    int ho, int wo, int kp, void* out, void* stream) {
     if (!x || !out || kp < kh * kw * cin) return bad("im2col: bad argument");
+    if (kh == 7 && kw == 7 && cin == 3 && kp % 8 == 0 && !a16(out)) return bad("im2col: the 7x7x3 patch rows (kp % 8 == 0) must be 16-byte aligned");
     if (reflect && (pad >= h || pad >= w)) return bad("im2col: reflect padding needs pad < size");   // one reflection only, as F.pad
     hipError_t e = vqseg::launch_im2col_stem(out_bf16, x, n, h, w, cin, kh, kw, stride, pad, reflect, ho, wo, kp, out,
                                              static_cast<hipStream_t>(stream));
@@ -311,6 +327,7 @@ int vqseg_im2col_f(int out_bf16, const float* x, int n, int h, int w, int cin, i
 int vqseg_conv_pack_all_f32(const float* w, int cout, int cin, int k, int c1, void* fwd, void* tr, void* s3, void* stream) {
     if (!w || cout <= 0 || cin <= 0 || (k != 1 && k != 3) || c1 <= 0 || c1 > cin || (!fwd && !tr && !s3)) return bad("conv_pack_all: bad argument (k = 1 or 3)");
     if (s3 && (cin % 32 || c1 % 32)) return bad("conv_pack_all: the split-3 image needs Cin and the concat split to be multiples of 32");
+    if (!a16(fwd) || !a16(tr) || !a16(s3)) return bad("conv_pack_all: the images must be 16-byte aligned");
     hipError_t e = vqseg::launch_pack_all(w, cout, cin, k, c1, static_cast<unsigned short*>(fwd), static_cast<unsigned short*>(tr),
                                           static_cast<unsigned short*>(s3), static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "conv_pack_all_kernel");
@@ -323,6 +340,7 @@ size_t vqseg_conv_packed_s2_elems(int cout, int cin, int k) {
 
 int vqseg_conv_pack_weights_s2_f32(const float* w, int cout, int cin, int k, void* hi, void* lo, void* stream) {
     if (!w || !hi || cout <= 0 || cin <= 0 || (k != 1 && k != 3)) return bad("conv_pack_weights_s2: bad argument (k = 1 or 3)");
+    if (!a16(hi) || !a16(lo)) return bad("conv_pack_weights_s2: the images must be 16-byte aligned");
     hipError_t e = vqseg::launch_pack_weights_s2(w, cout, cin, k, static_cast<unsigned short*>(hi), static_cast<unsigned short*>(lo),
                                                  static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "conv_pack_weights_s2");
@@ -386,6 +404,7 @@ int vqseg_reflect_ring_f(const void* gy, const void* t_hi, void* ring, void* gx,
 int vqseg_conv_pack_weights_s3_f32(const float* w, int cout, int cin, int c1, int kh, int kw, void* out, void* stream) {
     if (!w || !out || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0 || c1 <= 0 || c1 > cin || cin % 32 || c1 % 32)
         return bad("conv_pack_weights_s3: bad argument (Cin and the concat split must be multiples of 32)");
+    if (!a16(out)) return bad("conv_pack_weights_s3: the image must be 16-byte aligned");
     hipError_t e = vqseg::launch_pack_weights_s3(w, cout, cin, c1, kh, kw, static_cast<unsigned short*>(out), static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "conv_pack_weights_s3");
 }
@@ -416,6 +435,7 @@ int vqseg_s3_bilinear_f(const void* x, int n, int h, int w, int c, int ho, int w
 
 int vqseg_reflect_fold_f(int bf16, const void* gp, int n, int h, int w, int c, void* gx, void* stream) {
     if (!gp || !gx || h < 2 || w < 2) return bad("reflect_fold: bad argument");
+    if (rows_vec(bf16, c) && (!a16(gp) || !a16(gx))) return bad("reflect_fold: gp and gx must be 16-byte aligned (channels % 8 bf16 / % 4 fp32)");
     hipError_t e = vqseg::launch_reflect_fold(bf16, gp, n, h, w, c, gx, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hipfail(e, "reflect_fold_kernel");
 }

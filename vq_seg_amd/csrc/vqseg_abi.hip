@@ -183,6 +183,8 @@ int vqseg_vq_forward_group(int n_levels, int bf16, const void* const* x, const f
         if (ws_bytes[i] < plans[i].bytes) return fail(VQSEG_ENOSPC, "workspace %zu < %zu bytes", ws_bytes[i], plans[i].bytes);
         wsp[i] = static_cast<char*>(ws[i]);
         prep[i] = prepared ? prepared[i] : nullptr;
+    }
+    for (int i = 0; i < n_levels; ++i) {                    // every level is checked before anything is enqueued: a refused call writes nothing
         if (!prep[i]) {
             hipError_t e = vqseg::launch_prepare(codebook[i], k[i], c[i], wsp[i] + plans[i].off_prepared, st);
             if (e != hipSuccess) return hip_fail(e, "vq codebook prepare");
@@ -231,7 +233,7 @@ int vqseg_kmeans_accumulate_f32(const float* samples, const float* means, int64_
                                 int64_t* counts, void* ws, size_t ws_bytes, void* stream) {
     if (int rc = check_shape(n, c, k)) return rc;
     if (!samples || !means || !sums || !counts || !ws) return fail(VQSEG_EINVAL, "null pointer argument");
-    if (!aligned16(samples) || !aligned16(ws)) return fail(VQSEG_EINVAL, "samples and workspace must be 16-byte aligned");
+    if (!aligned16(samples) || !aligned16(means) || !aligned16(ws)) return fail(VQSEG_EINVAL, "samples, means and workspace must be 16-byte aligned");
     const vqseg::KmPlan p = vqseg::km_plan(n, c, k);
     if (ws_bytes < p.bytes) return fail(VQSEG_ENOSPC, "workspace %zu < %zu bytes", ws_bytes, p.bytes);
     hipError_t e = vqseg::launch_km_accumulate(samples, means, n, c, k, p, static_cast<char*>(ws), sums, counts,

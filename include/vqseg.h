@@ -1080,6 +1080,64 @@ int vqseg_photometric_f(const float* src, float* out, int n, int h, int w, int64
                         const float* params_host, const int32_t* radii_host, const float* taps_host, float* partials, float* means,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------- *
+ * Connected regions of an integer map: roots, ids, the instance table, areas and the area filter (vq_seg_amd.nnf.region_roots /
+ * region_ids / region_table / region_areas / filter_regions, vq_seg_amd.utils.regions, predict.Predictor(min_area=...) and
+ * .instances, CPSConfig.pseudo_min_area).  The reference labels on the host, per file, with skimage / cv2; THIS is the definition,
+ * restated by a plain union-find in tests/region_cases.py.  Integers throughout: every output is exact, bit-identical between calls,
+ * and an image's outputs do not depend on the batch it travels in.
+ *
+ * Inputs: values u8 or i32 [b][h * w]; connectivity 4 or 8; 0 to 4 ignored values (ignore0.. are read up to n_ignore).
+ * Limits: 1 <= b <= 65535, 1 <= h, w <= 4096; for the table 1 <= capacity and b * capacity <= 2^26 rows (2 GiB of table).
+ *
+ * Region: a maximal set of non-ignored pixels of ONE image with equal value, connected through 4- or 8-neighbours.
+ *   root  i32 [b][h * w]   the smallest row-major index y * w + x among the pixels of the pixel's region; -1 for an ignored pixel
+ *   id    i32 [b][h * w]   the region's 0-based rank among the image's regions by rising root; -1 where root is -1
+ *   count i32 [b]          the number of regions of the image (id + 1 with ignore = {0} on a binary map is scipy.ndimage.label's
+ *                          numbering, cross structure for 4, full 3 x 3 for 8)
+ *   table i32 [b][capacity][8] = (value, area, ymin, xmin, ymax, xmax, root, 0), row `id`; moments i64 [b][capacity][2] = (sum y, sum x).
+ *                          Rows from min(count, capacity) on are zero; a region with id >= capacity is counted, keeps its id in the id
+ *                          map and writes no row
+ *   area  i32 [b][h * w]   the region's area at its root index, 0 elsewhere
+ *   filter                 out[p] = values[p] where p belongs to no region or its region's area >= min_area; otherwise the fill: the
+ *                          constant `fill`, or with neighbour = 1 the INPUT value of the pixel before the region's root: (y, x - 1) if
+ *                          the root has x > 0, else (y - 1, x) if y > 0, else the pixel keeps its value.  That pixel lies outside the
+ *                          region and its value differs from the region's (equal and adjacent, it would be the root).  Single shot:
+ *                          no cascade of merges.
+ * Maps handed in (root, id) are never trusted as indices: a root outside [0, h * w) -- or, for the ids, one that is not its own
+ * root -- is a pixel of no region; an id outside [0, capacity) writes no row.
+ *
+ * vqseg_region_roots_u8 / _i32: three launches.  Local: a workgroup per 16 x 64 tile, union-find in LDS (links to the left and upper
+ *     neighbours, the two upper diagonals for 8; a link is an atomicMin on the larger root, so parents only fall), then a flatten in
+ *     LDS and a store of the local root's global index to `parent` (a workspace of b * h * w i32, not `root`).  Merge: the tiles'
+ *     border pixels join across the borders by find + atomicMin on `parent`, tile corners included; the find loads are agent-scope
+ *     relaxed atomic loads.  Flatten: every pixel follows its chain in `parent` and writes `root`.  Whatever order the merges run
+ *     in, the root is the region's smallest index.
+ * vqseg_region_ids_i32: four launches: roots counted per 1024 pixels, a scan per image over `partial` (a workspace of
+ *     b * vqseg_region_ids_partials(h, w) i32), ranks at the roots, id[p] = id[root[p]] elsewhere.
+ * vqseg_region_table_i32: table and moments are zeroed; the roots write value, ymin and root, then integer atomics add area, box and
+ *     moments, one set per run of equal ids among the 64 consecutive pixels of a wave.  value_bytes: 1 (values is u8) or 4 (i32).
+ * vqseg_region_areas_i32: area is zeroed; the runs of equal roots of a workgroup's 256 pixels are gathered in LDS, then one atomicAdd per root.
+ * vqseg_region_filter_u8 / _i32: a gather, out of place.  neighbour 0: the constant `fill` (0..255 for u8).
+ * No workgroup waits for another; every find / union loop has a trip bound of at most h * w and falls through at it.
+ *
+ * Errors (VQSEG_EINVAL before anything touches a device): null pointers, sizes outside the limits, a connectivity other than 4 or 8,
+ * n_ignore outside 0..4, parent == root, root == id, out == values, a capacity outside its limit, a fill outside the element type.
+ * ---------------------------------------------------------------------------------- */
+int vqseg_region_roots_u8(const uint8_t* values, int b, int h, int w, int connectivity, int n_ignore, int ignore0, int ignore1, int ignore2,
+                          int ignore3, int32_t* parent, int32_t* root, void* stream);
+int vqseg_region_roots_i32(const int32_t* values, int b, int h, int w, int connectivity, int n_ignore, int ignore0, int ignore1, int ignore2,
+                           int ignore3, int32_t* parent, int32_t* root, void* stream);
+int64_t vqseg_region_ids_partials(int h, int w);
+int vqseg_region_ids_i32(const int32_t* root, int b, int h, int w, int32_t* partial, int32_t* id, int32_t* count, void* stream);
+int vqseg_region_table_i32(const void* values, int value_bytes, const int32_t* root, const int32_t* id, int b, int h, int w, int capacity,
+                           int32_t* table, int64_t* moments, void* stream);
+int vqseg_region_areas_i32(const int32_t* root, int b, int h, int w, int32_t* area, void* stream);
+int vqseg_region_filter_u8(const uint8_t* values, const int32_t* root, const int32_t* area, int b, int h, int w, int min_area, int neighbour,
+                           int fill, uint8_t* out, void* stream);
+int vqseg_region_filter_i32(const int32_t* values, const int32_t* root, const int32_t* area, int b, int h, int w, int min_area, int neighbour,
+                            int fill, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

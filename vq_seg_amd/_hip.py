@@ -178,6 +178,14 @@ SYMBOLS = {
     "vqseg_rbd_paint_f": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 2),
     "vqseg_photometric_mean_blocks": (c_int, [c_int64]),
     "vqseg_photometric_f": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_int64] * 3 + [c_void_p] * 6),
+    "vqseg_region_roots_u8": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 3),
+    "vqseg_region_roots_i32": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 3),
+    "vqseg_region_ids_partials": (c_int64, [c_int, c_int]),
+    "vqseg_region_ids_i32": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 4),
+    "vqseg_region_table_i32": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3),
+    "vqseg_region_areas_i32": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2),
+    "vqseg_region_filter_u8": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
+    "vqseg_region_filter_i32": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
 }
 
 _lib: Optional[ctypes.CDLL] = None

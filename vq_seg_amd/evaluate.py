@@ -24,6 +24,9 @@ then have the same size (e.g. BaseDataset(resize=None)); the sheets of `visualiz
 `crf` (with fused; a utils.crf.DenseCRF or True for its defaults) scores the dense-CRF refinement of the prediction at the mask size,
 as deprecated/test _crf.py does between the forward and the metrics: predict.Predictor(crf=...).refined, then the counts from one
 `nnf.resize_argmax` call on the refined energies.  Not built with `window` or `visualize`.
+
+`min_area` (with fused; `min_area_fill` a class id or "neighbour", `connectivity`, `region_ignore`) scores the area-filtered class maps of
+predict.Predictor(min_area=...) in whatever mode is asked for: the counts come from the confusion kernel on the one-hot form of the filtered map.
 """
 from typing import Dict, Iterable, Tuple
 
@@ -65,8 +68,16 @@ def _detail_sheets(img, logits, flips, target, num_classes):
 @torch.no_grad()
 def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], num_classes: int,
               device=None, amp_dtype=None, fused: bool = False, tta=None, visualize=None, window=None, stride=None,
-              blend: str = "linear", window_batch=None, net_size=None, crf=None) -> Dict[str, object]:
+              blend: str = "linear", window_batch=None, net_size=None, crf=None, min_area=None, min_area_fill=0, connectivity: int = 4,
+              region_ignore=()) -> Dict[str, object]:
     """batches yields (images (N, 3, H, W) float in [0, 1], labels (N, Hm, Wm) int class ids)."""
+    if min_area is not None and not fused:
+        raise ValueError("test_loop: min_area needs fused=True (the filter runs on the fused path's class maps)")
+    if min_area is not None and visualize is not None:
+        raise ValueError("test_loop: visualize is not built for the scoring of area-filtered maps (min_area=...)")
+    if min_area is not None and (isinstance(min_area_fill, bool) or not (min_area_fill == "neighbour" or (
+            isinstance(min_area_fill, int) and 0 <= min_area_fill < num_classes))):
+        raise ValueError(f"test_loop: a scored map holds classes only: min_area_fill must be a class id or 'neighbour', got {min_area_fill!r}")
     if window is not None and not fused:
         raise ValueError("test_loop: window needs fused=True (the windows are blended inside the fused merge + arg-max)")
     if window is not None and visualize is not None:
@@ -80,7 +91,8 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
     if crf is not None and visualize is not None:
         raise ValueError("test_loop: visualize is not built for CRF scoring (crf=...)")
     predictor = Predictor(model, num_classes, amp_dtype=amp_dtype, tta=tta or ("none",), window=window, stride=stride, blend=blend,
-                          window_batch=window_batch, net_size=net_size, crf=crf) if fused else None
+                          window_batch=window_batch, net_size=net_size, crf=crf, min_area=min_area, min_area_fill=min_area_fill,
+                          connectivity=connectivity, region_ignore=region_ignore) if fused else None
     views = predictor.views if fused else None
     was_training = model.training
     model.eval()
@@ -92,7 +104,16 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
         for img, target in batches:
             if device is not None:
                 img, target = img.to(device), target.to(device)
-            if fused and window is not None:
+            if fused and min_area is not None:
+                # the filtered class map of predict.Predictor in whatever mode, counted by the confusion kernel from its one-hot form
+                size = tuple(target.shape[-2:])
+                label = predictor(img, size=None if window is not None else size).label
+                if tuple(label.shape[-2:]) != size:
+                    raise ValueError(f"test_loop: tiled scoring needs images and masks of one size, got {tuple(label.shape[-2:])} and {size}")
+                onehot = (label[:, None] == torch.arange(num_classes, device=label.device, dtype=label.dtype)[None, :, None, None]).float()
+                conf = confusion_matrix_device(onehot, target.to(label.device), num_classes)
+                hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (size[0] * size[1])
+            elif fused and window is not None:
                 if tuple(img.shape[-2:]) != tuple(target.shape[-2:]):
                     raise ValueError(f"test_loop: tiled scoring needs images and masks of one size, got {tuple(img.shape[-2:])} and "
                                      f"{tuple(target.shape[-2:])} (e.g. BaseDataset(resize=None))")

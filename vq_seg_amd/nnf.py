@@ -17,6 +17,7 @@ import ctypes
 from typing import Optional
 import weakref
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -2754,3 +2755,211 @@ def saliency_rbd(images, n_segments=250, compactness=10.0, iters=10, sigma_clr=1
     if return_parts:
         out[1].update(labels=labels, centers=centers, grid=(gy, gx), lab=lab)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Connected regions of an integer map (vqseg_region_*; include/vqseg.h states the definition, tests/region_cases.py restates it)
+# ------------------------------------------------------------------------------------------------
+REGION_MAX_SIDE = 4096
+REGION_VALUE_DTYPES = (torch.uint8, torch.int32)              # what the kernels read; int64 is converted here and the result converted back
+REGION_CALLS = 0              # calls of filter_regions that reached the library (as _hip.BOX_MIX_CALLS: for tests, never read by the product)
+
+
+def region_settings(connectivity=4, ignore=(), who="regions"):
+    """the checked (connectivity, ignore tuple) of a region call: 4 or 8; 0 to 4 integers that fit int32"""
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
+    if isinstance(ignore, (int, np.integer)) and not isinstance(ignore, bool):
+        ignore = (ignore,)
+    try:
+        ignore = tuple(ignore)
+    except TypeError:
+        raise ValueError(f"{who}: ignore must be a sequence of 0 to 4 integers, got {ignore!r}") from None
+    if len(ignore) > 4 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -2 ** 31 <= int(v) < 2 ** 31 for v in ignore):
+        raise ValueError(f"{who}: ignore must be a sequence of 0 to 4 integers that fit int32, got {ignore!r}")
+    return int(connectivity), tuple(int(v) for v in ignore)
+
+
+def _region_shape(t, name, who, dtypes):
+    E = _hip.HipLibraryError
+    if not (torch.is_tensor(t) and t.dim() == 3):
+        raise E(f"{who}: {name} must be a (B, H, W) tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if t.dtype not in dtypes:
+        raise E(f"{who}: {name} must be {' or '.join(str(d).removeprefix('torch.') for d in dtypes)}, got {t.dtype}")
+    b, h, w = t.shape
+    if not (1 <= b <= 65535 and 1 <= h <= REGION_MAX_SIDE and 1 <= w <= REGION_MAX_SIDE):
+        raise E(f"{who}: 1..65535 images with sides of 1..{REGION_MAX_SIDE}, got {tuple(t.shape)}")
+    return b, h, w
+
+
+def _region_same(who, first, **others):
+    E = _hip.HipLibraryError
+    for name, t in others.items():
+        if tuple(t.shape) != tuple(first.shape):
+            raise E(f"{who}: {name} must have the values' shape {tuple(first.shape)}, got {tuple(t.shape)}")
+        if t.device != first.device:
+            raise E(f"{who}: all tensors must be on one device, got {first.device} and {t.device} ({name})")
+
+
+def regions_supported(values) -> bool:
+    """what the kernels take: an integer GPU tensor (B, H, W) of uint8, int32 or int64, 1..65535 images, sides up to REGION_MAX_SIDE"""
+    return (torch.is_tensor(values) and values.is_cuda and values.dim() == 3 and values.dtype in REGION_VALUE_DTYPES + (torch.int64,)
+            and 1 <= values.shape[0] <= 65535 and 1 <= values.shape[1] <= REGION_MAX_SIDE and 1 <= values.shape[2] <= REGION_MAX_SIDE)
+
+
+def _region_values(values, who):
+    """(the map as the kernels read it, its entry-point suffix).  An int64 map is narrowed to int32 without a look at its values (that
+    would be a host round trip): class ids, superpixel labels and 255 fit; a value outside int32 wraps, in the result too."""
+    _region_shape(values, "values", who, REGION_VALUE_DTYPES + (torch.int64,))
+    v = values.detach()
+    v = (v.to(torch.int32) if v.dtype == torch.int64 else v).contiguous()
+    return v, "u8" if v.dtype == torch.uint8 else "i32"
+
+
+def _i32(t, name, numel):
+    return _T(t, name, dtype=torch.int32, numel=numel)
+
+
+def _region_roots(v, kind, conn, ign):
+    b, h, w = v.shape
+    dev, n = v.device, b * h * w
+    name = f"vqseg_region_roots_{kind}"
+    vp = _T(v, "values", dtype=v.dtype, numel=n)
+    ig = list(ign) + [0] * (4 - len(ign))
+    if dev.type != "cuda":
+        _launch(name, dev, vp, b, h, w, conn, len(ign), *ig, None, None)
+    parent = torch.empty((b, h, w), dtype=torch.int32, device=dev)
+    roots = torch.empty((b, h, w), dtype=torch.int32, device=dev)
+    _launch(name, dev, vp, b, h, w, conn, len(ign), *ig, _i32(parent, "parent", n), _i32(roots, "roots", n))
+    return roots
+
+
+def region_roots(values, connectivity=4, ignore=()):
+    """roots int32 (B, H, W) of the connected regions of `values` (B, H, W) uint8 / int32 (int64 is converted) on the GPU: the smallest
+    row-major index y * W + x of the pixel's region -- equal value, 4- or 8-connected, per image -- and -1 where the value is one of
+    `ignore` (0 to 4 integers).  Three launches (vqseg_region_roots_u8 / _i32); exact, bit-identical from call to call.  There is no
+    CPU form here (utils.regions has one)."""
+    conn, ign = region_settings(connectivity, ignore, "region_roots")
+    v, kind = _region_values(values, "region_roots")
+    return _region_roots(v, kind, conn, ign)
+
+
+def _region_ids(roots):
+    b, h, w = roots.shape
+    dev, n = roots.device, b * h * w
+    rp = _i32(roots, "roots", n)
+    if dev.type != "cuda":
+        _launch("vqseg_region_ids_i32", dev, rp, b, h, w, None, None, None)
+    nblk = int(lib().vqseg_region_ids_partials(h, w))
+    partial = torch.empty((b, nblk), dtype=torch.int32, device=dev)
+    ids = torch.empty((b, h, w), dtype=torch.int32, device=dev)
+    counts = torch.empty((b,), dtype=torch.int32, device=dev)
+    _launch("vqseg_region_ids_i32", dev, rp, b, h, w, _i32(partial, "partial", b * nblk), _i32(ids, "ids", n), _i32(counts, "counts", b))
+    return ids, counts
+
+
+def region_ids(roots):
+    """(ids int32 (B, H, W), counts int32 (B,)) of a root map as region_roots makes it: a region's id is its 0-based rank among the
+    image's regions by rising root (scipy.ndimage.label's order, minus one), -1 where root is -1; counts the regions per image.  An
+    entry of `roots` outside [0, H W), or one that does not point at a root, is a pixel of no region.  Four launches."""
+    _region_shape(roots, "roots", "region_ids", (torch.int32,))
+    return _region_ids(roots.detach().contiguous())
+
+
+def _region_areas(roots):
+    b, h, w = roots.shape
+    dev, n = roots.device, b * h * w
+    rp = _i32(roots, "roots", n)
+    if dev.type != "cuda":
+        _launch("vqseg_region_areas_i32", dev, rp, b, h, w, None)
+    areas = torch.empty((b, h, w), dtype=torch.int32, device=dev)
+    _launch("vqseg_region_areas_i32", dev, rp, b, h, w, _i32(areas, "areas", n))
+    return areas
+
+
+def region_areas(roots):
+    """areas int32 (B, H, W): every region's area at its root index, 0 elsewhere (one memset and one launch: the runs of equal
+    roots of a workgroup's 256 pixels are gathered in LDS, then one atomic per root)"""
+    _region_shape(roots, "roots", "region_areas", (torch.int32,))
+    return _region_areas(roots.detach().contiguous())
+
+
+def region_table(values, roots, ids, counts, capacity):
+    """(table int32 (B, capacity, 8) = (value, area, ymin, xmin, ymax, xmax, root, 0), moments int64 (B, capacity, 2) = (sum y, sum x)):
+    row `id` of every region of region_roots / region_ids' maps; rows from min(count, capacity) on are zero, and a region whose id is
+    >= capacity writes no row.  ids outside [0, capacity) and roots outside [0, H W) are never used as indices.  `counts` (B,) int32
+    is what region_ids returned (its shape is checked; the kernels do not read it)."""
+    E = _hip.HipLibraryError
+    v, _kind = _region_values(values, "region_table")
+    b, h, w = _region_shape(roots, "roots", "region_table", (torch.int32,))
+    _region_shape(ids, "ids", "region_table", (torch.int32,))
+    _region_same("region_table", v, roots=roots, ids=ids)
+    if not (torch.is_tensor(counts) and counts.dtype == torch.int32 and tuple(counts.shape) == (b,)):
+        raise E(f"region_table: counts must be an int32 tensor ({b},), got {getattr(counts, 'dtype', None)} {tuple(getattr(counts, 'shape', ()))}")
+    if isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= int(capacity) or b * int(capacity) > 1 << 26:
+        raise ValueError(f"region_table: capacity must be a positive integer with B * capacity <= 2^26, got {capacity!r}")
+    capacity = int(capacity)
+    roots, ids = roots.detach().contiguous(), ids.detach().contiguous()
+    dev, n = v.device, b * h * w
+    vp, rp, ip = _T(v, "values", dtype=v.dtype, numel=n), _i32(roots, "roots", n), _i32(ids, "ids", n)
+    if dev.type != "cuda":
+        _launch("vqseg_region_table_i32", dev, vp, v.element_size(), rp, ip, b, h, w, capacity, None, None)
+    table = torch.empty((b, capacity, 8), dtype=torch.int32, device=dev)
+    moments = torch.empty((b, capacity, 2), dtype=torch.int64, device=dev)
+    _launch("vqseg_region_table_i32", dev, vp, v.element_size(), rp, ip, b, h, w, capacity, _i32(table, "table", b * capacity * 8),
+            _T(moments, "moments", dtype=torch.int64, numel=b * capacity * 2))
+    return table, moments
+
+
+def region_fill(fill, dtype, who="filter_regions"):
+    """the checked fill of a filter call as (neighbour flag, constant): "neighbour", or an integer the element type holds"""
+    if isinstance(fill, str):
+        if fill != "neighbour":
+            raise ValueError(f"{who}: fill must be 'neighbour' or an integer, got {fill!r}")
+        return 1, 0
+    info = torch.iinfo(torch.int32 if dtype == torch.int64 else dtype)
+    if isinstance(fill, bool) or not isinstance(fill, (int, np.integer)) or not info.min <= int(fill) <= info.max:
+        raise ValueError(f"{who}: fill must be 'neighbour' or an integer in {info.min}..{info.max} for {dtype}, got {fill!r}")
+    return 0, int(fill)
+
+
+def region_min_area(min_area, who="filter_regions"):
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or not 0 <= int(min_area) < 2 ** 31:
+        raise ValueError(f"{who}: min_area must be an integer >= 0, got {min_area!r}")
+    return int(min_area)
+
+
+def filter_regions_from(values, roots, areas, min_area, fill=0):
+    """the filter launch alone, from maps already made (region_roots, region_areas): see filter_regions"""
+    global REGION_CALLS
+    min_area = region_min_area(min_area)
+    v, kind = _region_values(values, "filter_regions")
+    neighbour, const = region_fill(fill, values.dtype)
+    b, h, w = v.shape
+    _region_shape(roots, "roots", "filter_regions", (torch.int32,))
+    _region_shape(areas, "areas", "filter_regions", (torch.int32,))
+    _region_same("filter_regions", v, roots=roots, areas=areas)
+    roots, areas = roots.detach().contiguous(), areas.detach().contiguous()
+    dev, n = v.device, b * h * w
+    name = f"vqseg_region_filter_{kind}"
+    vp, rp, ap = _T(v, "values", dtype=v.dtype, numel=n), _i32(roots, "roots", n), _i32(areas, "areas", n)
+    if dev.type != "cuda":
+        _launch(name, dev, vp, rp, ap, b, h, w, min_area, neighbour, const, None)
+    out = torch.empty_like(v)
+    _launch(name, dev, vp, rp, ap, b, h, w, min_area, neighbour, const, _T(out, "out", dtype=v.dtype, numel=n))
+    REGION_CALLS += 1
+    return out.to(values.dtype)
+
+
+def filter_regions(values, min_area, connectivity=4, ignore=(), fill=0):
+    """`values` (B, H, W) uint8 / int32 / int64 on the GPU with every region (region_roots' definition) of fewer than `min_area` pixels
+    replaced: by the constant `fill`, or with fill="neighbour" by the input value of the pixel before the region's root -- (y, x - 1),
+    else (y - 1, x), else the region stays.  Ignored pixels keep their value.  Read from the input: single shot, no cascade.  Roots
+    (three launches), areas (a memset and one) and the gather; exact and bit-identical from call to call."""
+    conn, ign = region_settings(connectivity, ignore, "filter_regions")
+    region_min_area(min_area)
+    v, kind = _region_values(values, "filter_regions")
+    region_fill(fill, values.dtype)
+    roots = _region_roots(v, kind, conn, ign)
+    out = filter_regions_from(v, roots, _region_areas(roots), min_area, fill)
+    return out.to(values.dtype)

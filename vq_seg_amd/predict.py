@@ -29,6 +29,14 @@ resize Q" -- which `size=` equal to the network's gives.
 
     Predictor(model, 3, crf=True)(images).label
     Predictor(model, 3, crf=DenseCRF(iter_max=5, truncate=None))(images, size=(966, 1296), want_confidence=True)
+
+Regions, `min_area=...` (every mode): after the arg-max, connected regions of one class (utils.regions; vqseg_region_* on the GPU) with
+fewer than `min_area` pixels are replaced -- by `min_area_fill`, a class id or "neighbour" -- so specks of predicted weed and pinholes
+in a plant go.  `Predictor.instances` returns the prediction together with the table of its regions: the plants, with class, area,
+bounding box and centroid.  Under tiled prediction the filter runs on the merged map.
+
+    Predictor(model, 3, min_area=64, min_area_fill="neighbour")(images).label
+    pred, plants = Predictor(model, 3, min_area=64).instances(images, classes=(1, 2))       # plants.count, .value, .area, .bbox, .centroid
 """
 from collections import namedtuple
 from typing import Iterable, Iterator, List, Optional, Sequence, Tuple, Union
@@ -93,11 +101,15 @@ class Predictor:
     `superpixels`: a component count K or dict(num_components=, compactness=, iters=) -- object-based smoothing, the cheap alternative
     to the CRF (the reference's users write pred[assignment]): the view-averaged class probabilities are averaged over SLIC
     superpixels of the images (utils.superpixel) at the network's size, between the softmax and the arg-max.  Inference only; not
-    with `window` or `crf`."""
+    with `window` or `crf`.
+    `min_area` (None: off, nothing is launched): in every mode the class map is filtered after the arg-max -- a connected region
+    (`connectivity` 4 or 8) of one class with fewer than `min_area` pixels takes `min_area_fill`, a class id (default 0, the
+    background) or "neighbour" (utils.regions.remove_small_regions); pixels of a class in `region_ignore` belong to no region and stay.
+    `confidence` stays the network's top probability at every pixel, also where the filter changed the class."""
 
     def __init__(self, models: Union[nn.Module, Sequence[nn.Module]], num_classes: int, amp_dtype=None, tta: Sequence[str] = ("none",),
                  device=None, window=None, stride=None, blend: str = "linear", window_batch: Optional[int] = None, net_size=None, crf=None,
-                 superpixels=None):
+                 superpixels=None, min_area: Optional[int] = None, min_area_fill=0, connectivity: int = 4, region_ignore=()):
         self.models: List[nn.Module] = [models] if isinstance(models, nn.Module) else list(models)
         self.tta: Tuple[str, ...] = (tta,) if isinstance(tta, str) else tuple(tta)
         unknown = [t for t in self.tta if t not in TTA_FLIPS]
@@ -128,6 +140,17 @@ class Predictor:
             raise ValueError("superpixels together with window: superpixels under tiled prediction are not built")
         if self.superpixels is not None and self.crf is not None:
             raise ValueError("superpixels together with crf: one refinement of the probabilities at a time")
+        self.connectivity, self.region_ignore = nnf.region_settings(connectivity, region_ignore, "Predictor")
+        self.min_area = None if min_area is None else nnf.region_min_area(min_area, "Predictor")
+        nnf.region_fill(min_area_fill, torch.uint8, "Predictor: min_area_fill")
+        self.min_area_fill = min_area_fill
+
+    def _filtered(self, label: torch.Tensor) -> torch.Tensor:
+        """the class map after the area filter (min_area None: the map itself, nothing is launched)"""
+        if self.min_area is None:
+            return label
+        from .utils.regions import remove_small_regions
+        return remove_small_regions(label, self.min_area, self.connectivity, self.region_ignore, fill=self.min_area_fill)
 
     def _forward(self, model: nn.Module, x: torch.Tensor) -> torch.Tensor:
         """fp32 logits of one forward, under autocast on the GPU if asked for"""
@@ -257,7 +280,29 @@ class Predictor:
         finally:
             for m, was_training in zip(self.models, modes):
                 m.train(was_training)
-        return Prediction(label, top)
+        return Prediction(self._filtered(label), top)
+
+    @torch.no_grad()
+    def instances(self, images: torch.Tensor, size: Optional[Sequence[int]] = None, classes: Optional[Sequence[int]] = None,
+                  capacity: int = 1024, want_confidence: bool = False):
+        """images -> (Prediction, utils.regions.Regions): the prediction of __call__ (filtered, with `min_area`) and the table of its
+        connected regions per image -- count, and per region its class (`value`), area, bounding box, centroid and first pixel;
+        `capacity` rows per image.  `classes`: the class ids that count (e.g. (1, 2): crop and weed, not the background); pixels of
+        any other class, and of a value in `region_ignore`, belong to no region.  None: every value outside `region_ignore`.  (At most
+        four values can be ignored; with num_classes <= 4 only a `region_ignore` of values that are no class ids can exceed that.)"""
+        from .utils.regions import region_table
+        ignore = set(self.region_ignore)
+        if classes is not None:
+            wanted = set()
+            for c in classes:
+                if isinstance(c, bool) or int(c) != c or not 0 <= int(c) < self.num_classes:
+                    raise ValueError(f"instances: classes are ids in 0..{self.num_classes - 1}, got {tuple(classes)!r}")
+                wanted.add(int(c))
+            ignore |= set(range(self.num_classes)) - wanted
+        if len(ignore) > 4:
+            raise ValueError(f"instances: at most 4 values can be ignored, got {sorted(ignore)}")
+        pred = self(images, size=size, want_confidence=want_confidence)
+        return pred, region_table(pred.label, self.connectivity, tuple(sorted(ignore)), capacity)
 
     @torch.no_grad()
     def render(self, images: torch.Tensor, targets: Optional[torch.Tensor] = None, size: Optional[Sequence[int]] = None, panels=None,
@@ -267,7 +312,8 @@ class Predictor:
         launch (utils.visualize.render_sheet; vqseg_render_sheet_u8 on the GPU) from the labels, `targets` (N, Ht, Wt) at any size
         and the images themselves.  `panels` default: image | target | pred | 20 px white | mix_pred (without `targets`: no target
         panel); size None: (H, W).  Tiled mode: the merged labels of __call__ are what the sheet shows (`size`: None or the
-        images' own).  crf and superpixels mode: likewise the refined labels of __call__."""
+        images' own).  crf and superpixels mode: likewise the refined labels of __call__.  With `min_area` the sheet shows the
+        filtered labels in every mode (the plain mode then takes the label path too)."""
         from .utils.visualize import GAP, render_sheet
         size = self._own_size(images, size) if self.window is not None else \
             tuple(images.shape[-2:]) if size is None else (int(size[0]), int(size[1]))
@@ -285,12 +331,14 @@ class Predictor:
                 label = nnf.resize_argmax(logits, size)[0]
             else:
                 logits, flips = self.views(images)
+                if self.min_area is not None:
+                    label = nnf.resize_argmax(logits, size, flips=flips)[0]
         finally:
             for m, was_training in zip(self.models, modes):
                 m.train(was_training)
         dev = logits[0].device
-        if self.window is not None or self.crf is not None or self.superpixels is not None:
-            return render_sheet(panels, images.to(dev), label, None if targets is None else targets.to(dev), size=size, palette=palette,
+        if self.window is not None or self.crf is not None or self.superpixels is not None or self.min_area is not None:
+            return render_sheet(panels, images.to(dev), self._filtered(label), None if targets is None else targets.to(dev), size=size, palette=palette,
                                 alpha=alpha, half=half, num_classes=self.num_classes)
         return render_sheet(panels, images.to(dev), logits, None if targets is None else targets.to(dev), size=size, palette=palette, alpha=alpha,
                             half=half, flips=flips)
@@ -304,8 +352,10 @@ class Predictor:
 
 def predict_batches(models, batches: Iterable, num_classes: int, amp_dtype=None, tta: Sequence[str] = ("none",), device=None,
                     size: Optional[Sequence[int]] = None, want_confidence: bool = False, window=None, stride=None, blend: str = "linear",
-                    window_batch: Optional[int] = None, net_size=None, crf=None) -> Iterator[Prediction]:
-    """Predictor(models, num_classes, amp_dtype, tta, device, window, stride, blend, window_batch, net_size, crf)
+                    window_batch: Optional[int] = None, net_size=None, crf=None, min_area: Optional[int] = None, min_area_fill=0,
+                    connectivity: int = 4, region_ignore=()) -> Iterator[Prediction]:
+    """Predictor(models, num_classes, amp_dtype, tta, device, window, stride, blend, window_batch, net_size, crf, min_area=...)
     .predict_batches(batches, size, want_confidence)"""
     return Predictor(models, num_classes, amp_dtype=amp_dtype, tta=tta, device=device, window=window, stride=stride, blend=blend,
-                     window_batch=window_batch, net_size=net_size, crf=crf).predict_batches(batches, size, want_confidence)
+                     window_batch=window_batch, net_size=net_size, crf=crf, min_area=min_area, min_area_fill=min_area_fill,
+                     connectivity=connectivity, region_ignore=region_ignore).predict_batches(batches, size, want_confidence)

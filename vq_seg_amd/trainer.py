@@ -33,7 +33,7 @@ from . import nnf
 from .averaging import AveragedNetwork
 from .evaluate import test_loop
 from .utils.visualize import default_palette
-from .utils import saliency, superpixel
+from .utils import regions, saliency, superpixel
 from .models import init_weight
 from .models.networks import make_model
 from .optim import HipAdam
@@ -133,9 +133,17 @@ class CPSConfig:
     hard_aug_gray_p: float = 0.2
     hard_aug_blur_p: float = 0.5
     hard_aug_sigma: Sequence[float] = (0.1, 2.0)              # blur sigma drawn of [lo, hi]; radius ceil(3 sigma) <= 8
+    pseudo_min_area: Optional[int] = None     # speckle removal in the pseudo labels (utils.regions; no reference counterpart): in the mask each network hands
+                                              # to the other, a connected region of one class (255 belongs to no region) with fewer than this many pixels
+                                              # becomes 255, on that network's stream -- both recipes.  Per rank; no collective.  None = today's step: no
+                                              # launch is added and no tensor made
+    pseudo_connectivity: int = 4              # 4 or 8: which neighbours connect a region
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
+        if self.pseudo_min_area is not None:
+            self.pseudo_min_area = nnf.region_min_area(self.pseudo_min_area, "pseudo_min_area")
+        self.pseudo_connectivity = nnf.region_settings(self.pseudo_connectivity, (), "pseudo_connectivity")[0]
         if self.hard_aug not in (None, "photometric"):
             raise ValueError(f"hard_aug must be None or 'photometric', got {self.hard_aug!r}")
         if self.hard_aug_per not in ("batch", "sample"):
@@ -561,7 +569,8 @@ class CPSTrainer:
         return (crt if cfg.recipe == "v1" else self._ce_dice), False
 
     def _own_mask(self, ps, pu, kw, segments=None, salient=None):
-        """a network's fp32 predictions (labelled, unlabelled, both) and the pseudo-label mask it hands to the other network.
+        """a network's fp32 predictions (labelled, unlabelled, both), the pseudo-label mask it hands to the other network, and that mask
+        before the area filter (cfg.pseudo_min_area; the same tensor when the option is off).
         `segments` (cfg.superpixel_mean): both predictions are first averaged over their batch's superpixels, on this network's stream.
         `salient` (cfg.salient_mask): then the scores of the classes >= 1 are zeroed where the batch's saliency map is <= the threshold"""
         ps, pu = ps.float(), pu.float()
@@ -572,8 +581,13 @@ class CPSTrainer:
                       saliency.salient_masking(pu, salient[1], self.cfg.salient_mask))
         pred = torch.cat([ps, pu], dim=0)
         if self.cfg.recipe == "v1":
-            return ps, pu, pred, regularized_pseudo_label(pred, kw["percent"])
-        return ps, pu, pred, score_mask(pred, _argmax_classes(pred), kw["th"])
+            mask = regularized_pseudo_label(pred, kw["percent"])
+        else:
+            mask = score_mask(pred, _argmax_classes(pred), kw["th"])
+        raw = mask
+        if self.cfg.pseudo_min_area is not None:                        # specks of confident noise do not supervise the other network
+            mask = regions.remove_small_regions(raw, self.cfg.pseudo_min_area, self.cfg.pseudo_connectivity, ignore=(255,), fill=255)
+        return ps, pu, pred, mask, raw
 
     def _terms(self, l_target, sup, unsup, score_1, score_2, kw, segments=None, salient=None):
         """Each network's own mask and its two criterion terms (supervised; CPS against the other's mask) on its stream ->
@@ -587,9 +601,9 @@ class CPSTrainer:
             g.fork()
             g.share(cls_weight)
         with g.on(0):
-            ps1, pu1, pred_1, mask_1 = self._own_mask(sup[0][0], unsup[0][0], kw, segments, salient)
+            ps1, pu1, pred_1, mask_1, raw_1 = self._own_mask(sup[0][0], unsup[0][0], kw, segments, salient)
         with g.on(1):
-            ps2, pu2, pred_2, mask_2 = self._own_mask(sup[1][0], unsup[1][0], kw, segments, salient)
+            ps2, pu2, pred_2, mask_2, raw_2 = self._own_mask(sup[1][0], unsup[1][0], kw, segments, salient)
         g.exchange(mask_1, mask_2)
         crit, fused = self._criterion(cls_weight, pred_1)
         soft = cfg.unsup_criterion is not None                          # the unlabelled half of the CPS terms is _soft_cps's
@@ -605,6 +619,9 @@ class CPSTrainer:
             cps_1, cps_2 = self._soft_cps(cps_1, cps_2, ps1, ps2, pu1, pu2, kw)
         if cfg.keep_aux:
             self.aux.update(mask_1=mask_1, mask_2=mask_2, pred_sup_1=ps1.detach(), pred_ul_2=pu2.detach())
+            if cfg.pseudo_min_area is not None:                         # the masks before the area filter
+                self.aux.update(mask_1_unfiltered=raw_1, mask_2_unfiltered=raw_2)
+                g.to_caller(raw_1, raw_2)
             if segments is not None:                                    # the unpooled logits of network 1, and what the terms are restated from
                 raw_s, raw_u = sup[0][0].detach().float(), unsup[0][0].detach().float()
                 self.aux.update(pred_sup_1_unpooled=raw_s, pred_ul_1_unpooled=raw_u, pred_1=pred_1.detach(), pred_2=pred_2.detach())
@@ -752,16 +769,20 @@ class CPSTrainer:
         return self.teachers if which == "teacher" else self.models
 
     def evaluate(self, batches, which: str = "student", index: int = 0, fused: bool = False, visualize=None, window=None, stride=None,
-                 blend: str = "linear", window_batch=None, net_size=None, crf=None):
+                 blend: str = "linear", window_batch=None, net_size=None, crf=None, min_area=None, min_area_fill=0, connectivity: int = 4,
+                 region_ignore=()):
         """evaluate.test_loop on network `index` of the pair: which="student" scores the trained weights, which="teacher" their
         exponential moving average (cfg.ema_decay), under cfg.amp_dtype.  `batches` yields (images, labels).  `fused`: resize, arg-max
         and confusion counts in one kernel (evaluate.test_loop's opt-in; the same numbers).  `visualize` (with fused): a callable
         (batch_index, viz_v1, viz_v2) that receives the test script's two uint8 sheets per batch (evaluate.test_loop).  `window`
         (with fused; `stride`, `blend`, `window_batch`, `net_size`): tiled scoring, as predict.Predictor(window=...) predicts.  `crf`
-        (with fused; a utils.crf.DenseCRF or True): the dense-CRF refinement is scored, as predict.Predictor(crf=...) predicts."""
+        (with fused; a utils.crf.DenseCRF or True): the dense-CRF refinement is scored, as predict.Predictor(crf=...) predicts.
+        `min_area` (with fused; `min_area_fill`, `connectivity`, `region_ignore`): the area-filtered class maps are scored, as
+        predict.Predictor(min_area=...) predicts."""
         model = self._networks(which)[index]
         return test_loop(model, batches, self.cfg.num_classes, device=self.device, amp_dtype=self.cfg.amp_dtype, fused=fused, visualize=visualize,
-                         window=window, stride=stride, blend=blend, window_batch=window_batch, net_size=net_size, crf=crf)
+                         window=window, stride=stride, blend=blend, window_batch=window_batch, net_size=net_size, crf=crf, min_area=min_area,
+                         min_area_fill=min_area_fill, connectivity=connectivity, region_ignore=region_ignore)
 
     @torch.no_grad()
     def example_image(self, l_input, l_target, ul_input, which: str = "student", index: int = 0, half: bool = True):
@@ -786,18 +807,20 @@ class CPSTrainer:
 
     def predict(self, images, size=None, which: str = "student", index: int = 0, ensemble: bool = False, tta=("none",),
                 want_confidence: bool = False, window=None, stride=None, blend: str = "linear", window_batch=None, net_size=None,
-                crf=None, superpixels=None) -> Prediction:
+                crf=None, superpixels=None, min_area=None, min_area_fill=0, connectivity: int = 4, region_ignore=()) -> Prediction:
         """Class maps of `images` (N, 3, H, W) at `size` (None: their own): predict.Predictor on network `index` of the pair `which`
         names, or with `ensemble` on both of them (mean of the two networks' logits), times the flipped views of `tta`, under
         cfg.amp_dtype.  `window` (with `stride`, `blend`, `window_batch`, `net_size`): tiled prediction at the images' own size
         (predict.Predictor).  `crf` (a utils.crf.DenseCRF or True; not with `window`): dense-CRF refinement of the prediction.
         `superpixels` (a component count or dict(num_components=, compactness=, iters=); not with `window` or `crf`): the class
-        probabilities are averaged over SLIC superpixels of the images before the arg-max.
+        probabilities are averaged over SLIC superpixels of the images before the arg-max.  `min_area` (with `min_area_fill`,
+        `connectivity`, `region_ignore`; every mode): regions of one class smaller than that are replaced after the arg-max.
         -> Prediction(label (N, Ho, Wo) uint8, confidence (N, Ho, Wo) f32 | None)."""
         nets = self._networks(which)
         return Predictor(list(nets) if ensemble else nets[index], self.cfg.num_classes, amp_dtype=self.cfg.amp_dtype, tta=tta,
                          device=self.device, window=window, stride=stride, blend=blend, window_batch=window_batch,
-                         net_size=net_size, crf=crf, superpixels=superpixels)(images, size=size, want_confidence=want_confidence)
+                         net_size=net_size, crf=crf, superpixels=superpixels, min_area=min_area, min_area_fill=min_area_fill,
+                         connectivity=connectivity, region_ignore=region_ignore)(images, size=size, want_confidence=want_confidence)
 
     def _weighted(self, pred, target, weight):
         """the configured criterion with this step's class weights: the module's own parameters (ignore index 255, the focal

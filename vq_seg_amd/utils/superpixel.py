@@ -4,7 +4,7 @@ the label maps are made on the device (nnf.slic: vqseg_slic_lab_f / _assign_f / 
 (nnf.segment_mean: vqseg_segment_sums_f / _broadcast_f) with a backward pass that is the same two.
 
 The algorithm is the one stated in include/vqseg.h -- SLIC in its gather (gSLIC) form on float CIELAB, a regular gy x gx grid, a
-3 x 3 candidate window around the home cell, no connectivity enforcement -- NOT fast_slic's: that library quantises the image to
+3 x 3 candidate window around the home cell, no connectivity enforcement (utils.regions.enforce_connectivity is a pass of its own) -- NOT fast_slic's: that library quantises the image to
 uint8, and neither it nor skimage is available to compare against, so no parity with either is claimed.  The pooling is the mean of
 the class scores over each superpixel, which train_slic.py:62-69 evidently means (as written it reduces over the wrong axes and
 multiplies the prediction by means / prediction).

@@ -1138,6 +1138,64 @@ int vqseg_region_filter_u8(const uint8_t* values, const int32_t* root, const int
 int vqseg_region_filter_i32(const int32_t* values, const int32_t* root, const int32_t* area, int b, int h, int w, int min_area, int neighbour,
                             int fill, int32_t* out, void* stream);
 
+/* ---------------------------------------------------------------------------------- *
+ * Boundary metrics: the class boundaries of a label map, the exact squared Euclidean distance transform (EDT) of seed planes, and
+ * the count table behind boundary F1, boundary IoU and the Hausdorff distance (vq_seg_amd.nnf.class_boundaries / edt_sq /
+ * boundary_counts, vq_seg_amd.utils.boundary, evaluate.test_loop(boundary=...)).  The reference scores region overlap only; THIS is
+ * the definition, restated in plain numpy in tests/boundary_cases.py.  Integers throughout: every output is exact, bit-identical
+ * between calls, and an image's outputs do not depend on the batch it travels in.
+ *
+ * Inputs: labels u8 or i32 [b][h * w]; C = num_classes in 1..32; 0 to 4 ignored values (ignore0.. are read up to n_ignore).
+ * Limits: 1 <= h, w <= 2048 (the distance along a row is kept in 16 bits; the region kernels' limit of 4096 does not apply here),
+ *         1 <= planes = b * C <= 2^19 per launch.  The largest real squared distance, 2 * 2047^2, fits an int32.
+ *
+ * Boundary  seeds u8 [b][C][h * w] of 0 / 1: pixel p is a boundary pixel of class c when labels[p] == c and at least one of its
+ *           4-neighbours q INSIDE the image has a value that is neither c nor one of the ignored values.  The image border makes no
+ *           boundary, an ignored neighbour makes none, a neighbour with any other value (>= C included) does.  A label is compared
+ *           with the class, never used as an index.
+ * Distance  d2 i32 [planes][h * w]: d2[p] = min over q with seeds[q] != 0 of (py - qy)^2 + (px - qx)^2; VQSEG_EDT_NONE = 2^31 - 1
+ *           everywhere on a plane without a seed.  Planes are independent.  Where the plane has a seed, d2 is
+ *           rint(scipy.ndimage.distance_transform_edt(seeds == 0)^2) (scipy measures to the nearest ZERO).
+ * Counts    table i32 [b][C][8] from pred and target (class maps of one size), bp / bg = the boundaries of pred / target and
+ *           dp / dg = their squared distances, tol_sq = floor(tolerance^2) and width_sq = floor(width^2).  A pixel is VALID when
+ *           target[p] is not ignored; only valid pixels are counted:
+ *             0 n_pred      valid pixels with bp                  1 hit_pred    of those, dg <= tol_sq
+ *             2 n_gt        valid pixels with bg                  3 hit_gt      of those, dp <= tol_sq
+ *             4 band_inter  valid pixels in both Pd and Gd        5 band_union  valid pixels in Pd or Gd
+ *             6 hd_pred_sq  max of dg over the pixels of column 0; -1 if column 0 is 0 or the target has no boundary of c
+ *             7 hd_gt_sq    max of dp over the pixels of column 2; -1 likewise
+ *           with the inner bands Pd = (pred == c) & (dp <= width_sq), Gd = (target == c) & (dg <= width_sq): the mask pixels within
+ *           `width` of the mask's own contour (Cheng et al.'s boundary IoU, except that the image border is no contour).
+ * Scores (host, float64): P = hit_pred / n_pred, R = hit_gt / n_gt, F = 2 P R / (P + R); F is NaN (undefined) when n_pred == n_gt
+ *           == 0, and 0 when exactly one of them is 0 or P + R == 0.  BIoU = band_inter / band_union, NaN when band_union == 0.
+ *           HD = sqrt(max(column 6, column 7)), NaN when either is -1.  Means skip NaN; a class that is NaN for every image is left
+ *           out of the class mean; the mean of nothing is NaN.
+ *
+ * vqseg_boundary_seeds_u8 / _i32: one launch, a thread per pixel, every plane of the pixel written.
+ * vqseg_boundary_edt_rows_u8: one launch, a workgroup per plane row: g u16 [planes][h * w] = the distance along the row to the row's
+ *     nearest seed (0xffff in a row without one), from ballot words in LDS and clz / ctz; row_has u8 [planes][h] = the row has a seed.
+ * vqseg_boundary_edt_cols_i32: one launch, a workgroup per 64 x 64 tile: d2[y][x] = min over j of g[j][x]^2 + (y - j)^2, searched
+ *     outwards from y through the rows that have a seed only (compacted from row_has in LDS) until (y - j)^2 >= best; a plane
+ *     without a seed is filled with VQSEG_EDT_NONE.  A g of 0xffff is skipped, whatever row_has says.
+ * vqseg_boundary_counts_i32: the table is preset (zeros, -1 in columns 6 and 7) by a small launch, then one pass over pred, target,
+ *     bp, bg, dp and dg: a wave folds its lanes by shuffles and makes one integer atomicAdd / atomicMax per class and column.
+ *     pred_bytes / target_bytes: 1 (u8) or 4 (i32).
+ * Integer atomics only; no workgroup waits for another; every loop is bounded by h, w, C or a constant.
+ *
+ * Errors (VQSEG_EINVAL before anything touches a device): null pointers, sizes outside the limits, num_classes outside 1..32,
+ * n_ignore outside 0..4, element sizes other than 1 and 4, tol_sq or width_sq outside 0..2^31 - 2.
+ * ---------------------------------------------------------------------------------- */
+#define VQSEG_EDT_NONE 2147483647
+int vqseg_boundary_seeds_u8(const uint8_t* labels, int b, int h, int w, int num_classes, int n_ignore, int ignore0, int ignore1, int ignore2,
+                            int ignore3, uint8_t* seeds, void* stream);
+int vqseg_boundary_seeds_i32(const int32_t* labels, int b, int h, int w, int num_classes, int n_ignore, int ignore0, int ignore1, int ignore2,
+                             int ignore3, uint8_t* seeds, void* stream);
+int vqseg_boundary_edt_rows_u8(const uint8_t* seeds, int planes, int h, int w, uint16_t* g, uint8_t* row_has, void* stream);
+int vqseg_boundary_edt_cols_i32(const uint16_t* g, const uint8_t* row_has, int planes, int h, int w, int32_t* d2, void* stream);
+int vqseg_boundary_counts_i32(const void* pred, int pred_bytes, const void* target, int target_bytes, const uint8_t* bp, const uint8_t* bg,
+                              const int32_t* dp, const int32_t* dg, int b, int h, int w, int num_classes, int tol_sq, int width_sq,
+                              int n_ignore, int ignore0, int ignore1, int ignore2, int ignore3, int32_t* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,11 @@ SYMBOLS = {
     "vqseg_region_areas_i32": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2),
     "vqseg_region_filter_u8": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
     "vqseg_region_filter_i32": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
+    "vqseg_boundary_seeds_u8": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 2),
+    "vqseg_boundary_seeds_i32": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 2),
+    "vqseg_boundary_edt_rows_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 3),
+    "vqseg_boundary_edt_cols_i32": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2),
+    "vqseg_boundary_counts_i32": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 11 + [c_void_p] * 2),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -27,6 +27,12 @@ as deprecated/test _crf.py does between the forward and the metrics: predict.Pre
 
 `min_area` (with fused; `min_area_fill` a class id or "neighbour", `connectivity`, `region_ignore`) scores the area-filtered class maps of
 predict.Predictor(min_area=...) in whatever mode is asked for: the counts come from the confusion kernel on the one-hot form of the filtered map.
+
+`boundary` (with fused; True for the defaults or a dict of `tolerance`, `width`, `ignore` as utils.boundary.BoundaryMeasurement takes them)
+adds contour-level scores of the label map the fused call of the branch returns anyway -- resize_argmax's, merge_argmax's or the Predictor's;
+no second forward is made -- in every mode fused has: test_boundary_f1 / test_boundary_f1s, test_boundary_iou / test_boundary_ious (means
+over all images, NaN skipped; the lists per class, rounded to 5 places) and test_hausdorff.  With None nothing changes: no extra launch, the
+same dict.
 """
 from typing import Dict, Iterable, Tuple
 
@@ -35,7 +41,7 @@ import torch
 import torch.nn.functional as F
 
 from . import nnf
-from .measurement import Measurement, confusion_matrix_device
+from .measurement import BoundaryMeasurement, Measurement, confusion_matrix_device
 from .predict import Predictor
 
 
@@ -69,8 +75,13 @@ def _detail_sheets(img, logits, flips, target, num_classes):
 def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], num_classes: int,
               device=None, amp_dtype=None, fused: bool = False, tta=None, visualize=None, window=None, stride=None,
               blend: str = "linear", window_batch=None, net_size=None, crf=None, min_area=None, min_area_fill=0, connectivity: int = 4,
-              region_ignore=()) -> Dict[str, object]:
+              region_ignore=(), boundary=None) -> Dict[str, object]:
     """batches yields (images (N, 3, H, W) float in [0, 1], labels (N, Hm, Wm) int class ids)."""
+    if boundary is not None and not fused:
+        raise ValueError("test_loop: boundary needs fused=True (the contours are those of the fused path's class maps)")
+    if boundary is not None and boundary is not True and not (isinstance(boundary, dict) and set(boundary) <= {"tolerance", "width", "ignore"}):
+        raise ValueError(f"test_loop: boundary is None, True or a dict of tolerance, width and ignore, got {boundary!r}")
+    contours = None if boundary is None else BoundaryMeasurement(num_classes, **({} if boundary is True else boundary))
     if min_area is not None and not fused:
         raise ValueError("test_loop: min_area needs fused=True (the filter runs on the fused path's class maps)")
     if min_area is not None and visualize is not None:
@@ -118,20 +129,22 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
                     raise ValueError(f"test_loop: tiled scoring needs images and masks of one size, got {tuple(img.shape[-2:])} and "
                                      f"{tuple(target.shape[-2:])} (e.g. BaseDataset(resize=None))")
                 logits, flips, grid = predictor.tiled_views(img)
-                conf = nnf.merge_argmax(logits, grid, flips=flips, blend=blend, target=target)[2]
+                label, _top, conf = nnf.merge_argmax(logits, grid, flips=flips, blend=blend, target=target)
                 hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (target.shape[-2] * target.shape[-1])
             elif fused and predictor.crf is not None:
                 size = tuple(target.shape[-2:])
-                conf = nnf.resize_argmax(predictor.refined(img, size), size, target=target)[2]
+                label, _top, conf = nnf.resize_argmax(predictor.refined(img, size), size, target=target)
                 hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (size[0] * size[1])
             elif fused:
                 logits, flips = views(img)
-                conf = nnf.resize_argmax(logits, tuple(target.shape[-2:]), flips=flips, target=target)[2]
+                label, _top, conf = nnf.resize_argmax(logits, tuple(target.shape[-2:]), flips=flips, target=target)
                 hits = torch.diagonal(conf, dim1=1, dim2=2).sum(dim=1).double() / (target.shape[-2] * target.shape[-1])
                 if visualize is not None:
                     visualize(n_batches, *_detail_sheets(img, logits, flips, target, num_classes))
             else:
                 conf, hits = _resized_counts(model, img, target, num_classes, amp_dtype)
+            if contours is not None:
+                contours.update(label, target.to(label.device))
             conf_np = conf.cpu().numpy()
             miou, ious = meas.miou(conf_np)
             precision, _ = meas.precision(conf_np)
@@ -149,4 +162,9 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
         raise ValueError("test_loop: no batches")
     out = {k: v / n_batches for k, v in sums.items()}
     out["test_ious"] = np.round(iou_per_class / n_batches, 5).tolist()
+    if contours is not None:
+        r = contours.result()
+        out["test_boundary_f1"], out["test_boundary_f1s"] = r["boundary_f1"], np.round(r["boundary_f1s"], 5).tolist()
+        out["test_boundary_iou"], out["test_boundary_ious"] = r["boundary_iou"], np.round(r["boundary_ious"], 5).tolist()
+        out["test_hausdorff"] = r["hausdorff"]
     return out

@@ -89,3 +89,7 @@ def miou_device(conf: torch.Tensor):
     diag = torch.diagonal(conf, dim1=-2, dim2=-1)
     ious = (diag / (conf.sum(-2) + conf.sum(-1) - diag + 1e-8)).mean(dim=0)
     return ious.mean(), ious
+
+
+# contour-level scores (boundary F1, boundary IoU, Hausdorff distance) beside the region overlap above: utils/boundary.py
+from .utils.boundary import BoundaryMeasurement  # noqa: E402,F401

@@ -2963,3 +2963,144 @@ def filter_regions(values, min_area, connectivity=4, ignore=(), fill=0):
     roots = _region_roots(v, kind, conn, ign)
     out = filter_regions_from(v, roots, _region_areas(roots), min_area, fill)
     return out.to(values.dtype)
+
+
+# ------------------------------------------------------------------------------------------------
+# Boundary metrics (vqseg_boundary_*; include/vqseg.h states the definition, tests/boundary_cases.py restates it)
+# ------------------------------------------------------------------------------------------------
+EDT_NONE = 2 ** 31 - 1        # the squared distance on a plane without a seed
+EDT_MAX_SIDE = 2048           # sides of a distance transform (the row pass keeps distances in 16 bits); REGION_MAX_SIDE is 4096
+EDT_MAX_PLANES = 1 << 19      # planes per launch
+BOUNDARY_MAX_CLASSES = 32
+BOUNDARY_WORKSPACE_BYTES = 512 << 20          # boundary_counts: the int32 distance planes of one chunk of images stay under this
+BOUNDARY_CALLS = 0            # calls of boundary_counts that reached the library (as REGION_CALLS: for tests, never read by the product)
+
+
+def boundary_classes(num_classes, who="boundary"):
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= int(num_classes) <= BOUNDARY_MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes must be an integer in 1..{BOUNDARY_MAX_CLASSES}, got {num_classes!r}")
+    return int(num_classes)
+
+
+def boundary_threshold(value, name, who="boundary_counts"):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) <= EDT_NONE - 1:
+        raise ValueError(f"{who}: {name} must be an integer in 0..2^31 - 2 (a squared distance), got {value!r}")
+    return int(value)
+
+
+def _boundary_labels(labels, name, who):
+    """(the map as the kernels read it: uint8 or int32, int64 narrowed as _region_values does; b, h, w)"""
+    E = _hip.HipLibraryError
+    _region_shape(labels, name, who, REGION_VALUE_DTYPES + (torch.int64,))
+    b, h, w = labels.shape
+    if h > EDT_MAX_SIDE or w > EDT_MAX_SIDE:
+        raise E(f"{who}: sides of 1..{EDT_MAX_SIDE}, got {tuple(labels.shape)}")
+    v = labels.detach()
+    v = (v.to(torch.int32) if v.dtype == torch.int64 else v).contiguous()
+    return v, b, h, w
+
+
+def boundaries_supported(labels) -> bool:
+    """what the boundary kernels take: regions_supported with sides up to EDT_MAX_SIDE"""
+    return regions_supported(labels) and labels.shape[1] <= EDT_MAX_SIDE and labels.shape[2] <= EDT_MAX_SIDE
+
+
+def _boundary_seeds(v, c, ign):
+    b, h, w = v.shape
+    dev, n = v.device, b * h * w
+    name = "vqseg_boundary_seeds_" + ("u8" if v.dtype == torch.uint8 else "i32")
+    vp = _T(v, "labels", dtype=v.dtype, numel=n)
+    ig = list(ign) + [0] * (4 - len(ign))
+    if dev.type != "cuda":
+        _launch(name, dev, vp, b, h, w, c, len(ign), *ig, None)
+    seeds = torch.empty((b, c, h, w), dtype=torch.uint8, device=dev)
+    _launch(name, dev, vp, b, h, w, c, len(ign), *ig, _T(seeds, "seeds", dtype=torch.uint8, numel=n * c))
+    return seeds
+
+
+def class_boundaries(labels, num_classes, ignore=()):
+    """seeds uint8 (B, C, H, W) of 0 / 1 from `labels` (B, H, W) uint8 / int32 (int64 is converted) on the GPU: pixel p is a boundary
+    pixel of class c when labels[p] == c and one of its 4-neighbours inside the image is neither c nor one of `ignore` (0 to 4
+    integers).  The image border makes no boundary.  One launch (vqseg_boundary_seeds_u8 / _i32); sides up to 2048, B * C <= 2^19.
+    There is no CPU form here (utils.boundary has one)."""
+    c = boundary_classes(num_classes, "class_boundaries")
+    _conn, ign = region_settings(4, ignore, "class_boundaries")
+    v, b, _h, _w = _boundary_labels(labels, "labels", "class_boundaries")
+    if b * c > EDT_MAX_PLANES:
+        raise _hip.HipLibraryError(f"class_boundaries: at most 2^19 planes (B * num_classes), got {b} x {c}")
+    return _boundary_seeds(v, c, ign)
+
+
+def _edt_planes(seeds):
+    """(planes, h, w) uint8 contiguous -> int32 squared distances: the row launch and the column launch"""
+    planes, h, w = seeds.shape
+    dev, n = seeds.device, planes * h * w
+    sp = _T(seeds, "seeds", dtype=torch.uint8, numel=n)
+    if dev.type != "cuda":
+        _launch("vqseg_boundary_edt_rows_u8", dev, sp, planes, h, w, None, None)
+    g = torch.empty((planes, h, w), dtype=torch.int16, device=dev)          # u16 on the device: torch has no arithmetic for it, none is needed
+    row_has = torch.empty((planes, h), dtype=torch.uint8, device=dev)
+    d2 = torch.empty((planes, h, w), dtype=torch.int32, device=dev)
+    gp, rp = _T(g, "g", dtype=torch.int16, numel=n), _T(row_has, "row_has", dtype=torch.uint8, numel=planes * h)
+    _launch("vqseg_boundary_edt_rows_u8", dev, sp, planes, h, w, gp, rp)
+    _launch("vqseg_boundary_edt_cols_i32", dev, gp, rp, planes, h, w, _i32(d2, "d2", n))
+    return d2
+
+
+def edt_sq(seeds):
+    """int32 squared Euclidean distances to the nearest non-zero pixel of `seeds` (..., H, W) uint8 or bool on the GPU, every leading
+    dimension a batch of independent planes; EDT_NONE on a plane without a seed.  Exact: rint(scipy's distance_transform_edt(seeds ==
+    0) ** 2) where the plane has a seed.  Two launches per 2^19 planes (vqseg_boundary_edt_rows_u8, vqseg_boundary_edt_cols_i32);
+    sides up to 2048."""
+    E = _hip.HipLibraryError
+    if not (torch.is_tensor(seeds) and seeds.dim() >= 2):
+        raise E(f"edt_sq: seeds must be a (..., H, W) tensor, got {tuple(getattr(seeds, 'shape', ()))}")
+    if seeds.dtype not in (torch.uint8, torch.bool):
+        raise E(f"edt_sq: seeds must be uint8 or bool, got {seeds.dtype}")
+    h, w = seeds.shape[-2:]
+    if not (1 <= h <= EDT_MAX_SIDE and 1 <= w <= EDT_MAX_SIDE) or seeds.numel() == 0:
+        raise E(f"edt_sq: at least one plane with sides of 1..{EDT_MAX_SIDE}, got {tuple(seeds.shape)}")
+    s = seeds.detach()
+    s = (s.to(torch.uint8) if s.dtype == torch.bool else s).contiguous().view(-1, h, w)
+    parts = [_edt_planes(s[k:k + EDT_MAX_PLANES]) for k in range(0, s.shape[0], EDT_MAX_PLANES)]
+    return (parts[0] if len(parts) == 1 else torch.cat(parts)).view(seeds.shape)
+
+
+def boundary_chunk(num_classes, h, w):
+    """images per chunk of boundary_counts: 2 C int32 distance planes per image stay under BOUNDARY_WORKSPACE_BYTES, C B under 2^19"""
+    per_image = 2 * num_classes * h * w * 4
+    return max(1, min((BOUNDARY_WORKSPACE_BYTES - 1) // per_image, EDT_MAX_PLANES // num_classes))
+
+
+def boundary_counts(pred, target, num_classes, tol_sq, width_sq, ignore=()):
+    """table int32 (B, C, 8) = (n_pred, hit_pred, n_gt, hit_gt, band_inter, band_union, hd_pred_sq, hd_gt_sq) per image and class from
+    the class maps `pred` and `target` (B, H, W) uint8 / int32 / int64 on the GPU -- include/vqseg.h states every column.  tol_sq =
+    floor(tolerance^2), width_sq = floor(width^2); a pixel counts when its target is not one of `ignore`.  Per chunk of images (whose
+    distance planes stay under 512 MiB): two boundary launches, two row and two column launches, the table preset and the counts."""
+    global BOUNDARY_CALLS
+    c = boundary_classes(num_classes, "boundary_counts")
+    tol_sq, width_sq = boundary_threshold(tol_sq, "tol_sq"), boundary_threshold(width_sq, "width_sq")
+    _conn, ign = region_settings(4, ignore, "boundary_counts")
+    p, b, h, w = _boundary_labels(pred, "pred", "boundary_counts")
+    t, _b, _h, _w = _boundary_labels(target, "target", "boundary_counts")
+    _region_same("boundary_counts", p, target=t)
+    dev = p.device
+    ig = list(ign) + [0] * (4 - len(ign))
+    if dev.type != "cuda":                                     # everything else is right: the device error, before anything is made
+        n = b * h * w
+        _launch("vqseg_boundary_counts_i32", dev, _T(p, "pred", dtype=p.dtype, numel=n), p.element_size(), _T(t, "target", dtype=t.dtype, numel=n),
+                t.element_size(), None, None, None, None, b, h, w, c, tol_sq, width_sq, len(ign), *ig, None)
+    table = torch.empty((b, c, 8), dtype=torch.int32, device=dev)
+    step = boundary_chunk(c, h, w)
+    for k in range(0, b, step):
+        pk, tk = p[k:k + step], t[k:k + step]
+        nb = pk.shape[0]
+        n = nb * h * w
+        bp, bg = _boundary_seeds(pk, c, ign), _boundary_seeds(tk, c, ign)
+        dp, dg = _edt_planes(bp.view(nb * c, h, w)), _edt_planes(bg.view(nb * c, h, w))
+        _launch("vqseg_boundary_counts_i32", dev, _T(pk, "pred", dtype=pk.dtype, numel=n), pk.element_size(),
+                _T(tk, "target", dtype=tk.dtype, numel=n), tk.element_size(), _T(bp, "bp", dtype=torch.uint8, numel=n * c),
+                _T(bg, "bg", dtype=torch.uint8, numel=n * c), _i32(dp, "dp", n * c), _i32(dg, "dg", n * c), nb, h, w, c, tol_sq, width_sq,
+                len(ign), *ig, _i32(table[k:k + step], "table", nb * c * 8))
+    BOUNDARY_CALLS += 1
+    return table

@@ -22,40 +22,11 @@ import numpy as np
 import torch
 
 from .. import nnf
+from .maps import as_map as _as_map, back as _back, shift as _shift
 
 # count (B,) int32; value, area, root (B, capacity) int32; bbox (B, capacity, 4) int32 = (ymin, xmin, ymax, xmax), inclusive;
 # centroid (B, capacity, 2) float64 = (sum y, sum x) / area.  Row `id`; rows from min(count, capacity) on are zero.
 Regions = namedtuple("Regions", "count value area bbox centroid root")
-
-_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
-
-
-def _as_map(values, who):
-    """(the (B, H, W) integer tensor, how to hand a result back: numpy or not, and whether a batch axis was added)"""
-    is_np = isinstance(values, np.ndarray)
-    t = torch.from_numpy(np.ascontiguousarray(values)) if is_np else values
-    if not torch.is_tensor(t) or t.dtype not in _INT_DTYPES or t.dim() not in (2, 3):
-        raise ValueError(f"{who}: an integer map (B, H, W) or (H, W) is required (uint8, int8, int16, int32 or int64), got "
-                         f"{getattr(t, 'dtype', type(values).__name__)} {tuple(getattr(t, 'shape', ()))}")
-    if t.numel() == 0:
-        raise ValueError(f"{who}: an empty map, shape {tuple(t.shape)}")
-    single = t.dim() == 2
-    return (t[None] if single else t).detach(), is_np, single
-
-
-def _back(t, is_np, single):
-    t = t[0] if single else t
-    return t.cpu().numpy() if is_np else t
-
-
-def _shift(x, dy, dx, pad):
-    """y[.., i, j] = x[.., i + dy, j + dx], `pad` where that is outside"""
-    h, w = x.shape[-2:]
-    out = torch.full_like(x, pad)
-    ys, yd = (slice(dy, h), slice(0, h - dy)) if dy >= 0 else (slice(0, h + dy), slice(-dy, h))
-    xs, xd = (slice(dx, w), slice(0, w - dx)) if dx >= 0 else (slice(0, w + dx), slice(-dx, w))
-    out[..., yd, xd] = x[..., ys, xs]
-    return out
 
 
 def roots_torch(values: torch.Tensor, connectivity: int = 4, ignore=()) -> torch.Tensor:

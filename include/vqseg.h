@@ -1196,6 +1196,46 @@ int vqseg_boundary_counts_i32(const void* pred, int pred_bytes, const void* targ
                               const int32_t* dp, const int32_t* dg, int b, int h, int w, int num_classes, int tol_sq, int width_sq,
                               int n_ignore, int ignore0, int ignore1, int ignore2, int ignore3, int32_t* table, void* stream);
 
+/* ---------------------------------------------------------------------------------- *
+ * Feature perturbation: channel dropout of the decoder's inputs, fused with the concatenation that doubles the batch
+ * (vq_seg_amd.nnf.channel_keep / channel_dropout_cat; the model's decode with a perturbation spec; CPSConfig.feature_perturb).
+ * The reference's UniMatch stream is decoder(torch.cat((f, nn.Dropout2d(0.5)(f)))) (deprecated/train_UNIMatch.py:172,183-185;
+ * models/networks/deeplabv3/net.py:109-116).  THIS is the definition; vq_seg_amd.nnf restates it with torch ops, bit for bit.
+ *
+ * vqseg_channel_keep_f: the keep / scale table of one forward, all levels in one launch.
+ *     word0(e)  = word 0 of Philox4x32-10 with counter (e, stream_id, step & 0xffffffff, step >> 32) and key (seed & 0xffffffff, seed >> 32)
+ *     scale[e]  = word0(e) >= threshold ? inv_keep : 0.0f                    for e in [0, total)
+ *   The host supplies threshold = clamp(round(p * 2^32), 0, 2^32 - 1) and inv_keep = float32(1 / (1 - p)), 0 <= p < 1.  The caller
+ *   lays the table out level-major: level l is a dense [B][C_l] block at offset B * sum_{j < l} C_j.  Philox rounds: (c0, c1, c2, c3)
+ *   <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), M0 = 0xD2511F53, M1 = 0xCD9E8D57, then (k0, k1) +=
+ *   (0x9E3779B9, 0xBB67AE85); ten rounds.  Integer arithmetic only: two calls agree bit for bit, on any device.
+ *   total in 1 .. 2^32 - 1; stream_id and threshold in 0 .. 2^32 - 1; inv_keep finite, >= 1.
+ *
+ * vqseg_channel_dropout_cat_f: x [n][c][h][w] (bf16 = 0: f32, 1: bf16; channels_last = 0: NCHW-contiguous, 1: channels_last storage),
+ *   scale f32 [n][c], out [2 n][c][h][w] in x's type and layout, out of place:
+ *     out[i]        = x[i]                                                     by bits (NaN payloads, infinities, -0.0 unchanged)
+ *     out[n + i, k] = scale[i, k] == 0 ? +0.0 : round(float(x[i, k]) * scale[i, k])
+ *   a SELECTION of +0.0 where the channel is dropped (an Inf or NaN activation there does not leak); the product is the f32 product
+ *   (round to nearest), for bf16 rounded once more to bf16 (nearest even; a NaN becomes 0x7fc0) -- what (x.float() * scale).to(dtype)
+ *   computes.  scale = 2 (p = 0.5) is exact.
+ * vqseg_channel_dropout_fold_f: its backward pass.  g [2 n][c][h][w], gx [n][c][h][w], the same type and layout:
+ *     gx[i, k] = scale[i, k] == 0 ? g[i, k] (by bits) : round(float(g[i, k]) + round_f32(float(g[n + i, k]) * scale[i, k]))
+ *   The product is rounded to f32 BEFORE the add (no FMA contraction), so separate multiply and add operators give the same bits;
+ *   where the channel was dropped the second term is absent: an Inf or NaN in g[n + i, k] does not reach gx.
+ * Both are HBM-bound (forward 1 read + 2 writes per element, backward 2 reads + 1 write): a 1 KiB tile of one sample per wave and
+ * iteration, 16-byte loads / stores where the sample's position in every tensor is 16-byte aligned, element-wise and coalesced
+ * elsewhere (a partial last tile; a sample or a half at an unaligned position); the scale is picked per element and re-read from
+ * L2.  No alignment is required of any pointer beyond the element's own.  Grid capped by option "nn_grid_cap".
+ * Errors (VQSEG_EINVAL before anything touches a device): null pointers, in-place calls, flags other than 0 / 1, sizes <= 0,
+ * c h w > 2^40, n c > 2^31.
+ * ---------------------------------------------------------------------------------- */
+int vqseg_channel_keep_f(float* scale, int64_t total, uint64_t seed, int64_t stream_id, uint64_t step, int64_t threshold, float inv_keep,
+                         void* stream);
+int vqseg_channel_dropout_cat_f(int bf16, const void* x, const float* scale, void* out, int n, int c, int h, int w, int channels_last,
+                                void* stream);
+int vqseg_channel_dropout_fold_f(int bf16, const void* g, const float* scale, void* gx, int n, int c, int h, int w, int channels_last,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

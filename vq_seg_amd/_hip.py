@@ -191,6 +191,9 @@ SYMBOLS = {
     "vqseg_boundary_edt_rows_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 3),
     "vqseg_boundary_edt_cols_i32": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2),
     "vqseg_boundary_counts_i32": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 11 + [c_void_p] * 2),
+    "vqseg_channel_keep_f": (c_int, [c_void_p, c_int64, ctypes.c_uint64, c_int64, ctypes.c_uint64, c_int64, c_float, c_void_p]),
+    "vqseg_channel_dropout_cat_f": (c_int, [c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p]),
+    "vqseg_channel_dropout_fold_f": (c_int, [c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

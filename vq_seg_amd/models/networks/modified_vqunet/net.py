@@ -95,11 +95,48 @@ class _VQRePTUnet1x1Base(nn.Module):
                 usage.append(dead.detach())
         return feats, loss / len(feats), usage
 
-    def decode(self, feats):
-        decoder_out = self.decoder(*feats)
-        if self.training:                                    # two consumers in training mode: the head and the prototype loss
-            nnf.fanin_tag(decoder_out)
-        return decoder_out, self.segmentation_head(decoder_out)
+    def decode(self, feats, perturb=None):
+        """-> decoder_out, logits; with a perturbation spec `perturb` (see _perturb_spec) -> decoder_out, logits, logits_fp: the
+        feature-perturbation stream of UniMatch (deprecated/train_UNIMatch.py:172,183-185; models/networks/deeplabv3/net.py:109-116:
+        decoder(torch.cat((f, nn.Dropout2d(0.5)(f))))).  Every decoder input -- all five levels, after quantisation, in the dtype it has
+        here -- is doubled to 2B images by nnf.channel_dropout_cat with its own slice of ONE keep table (nnf.channel_keep: one launch),
+        so the encoder and the VQ phase ran on B images and only the decoder and the head run on 2B (their BatchNorm statistics are
+        taken over the 2B batch, as in the reference).  The clean halves are what is returned first; the table is left under
+        perturb["scale"]."""
+        if perturb is None:
+            decoder_out = self.decoder(*feats)
+            if self.training:                                # two consumers in training mode: the head and the prototype loss
+                nnf.fanin_tag(decoder_out)
+            return decoder_out, self.segmentation_head(decoder_out)
+        self._training_only(perturb)
+        b = feats[0].shape[0]
+        table, scales = nnf.channel_keep([(b, f.shape[1]) for f in feats], perturb["p"], perturb["seed"], perturb["stream"], perturb["step"],
+                                         feats[0].device)
+        perturb["scale"] = table
+        # the encoder features gain no consumer (the one op stands where the decoder stood); its gradient goes back through autograd,
+        # and so do the two gradients of decoder_out (the head sees 2B images, the prototype loss the clean half): the unfused adds
+        decoder_out = self.decoder(*[nnf.channel_dropout_cat(f, s) for f, s in zip(feats, scales)])
+        logits = self.segmentation_head(decoder_out)
+        return decoder_out[:b], logits[:b], logits[b:]
+
+    def _training_only(self, need_fp):
+        if need_fp and not self.training:
+            raise RuntimeError("feature perturbation (need_fp / a perturbation spec) is a training-mode option: this model is in eval "
+                               "mode -- call train() first, or leave need_fp off")
+
+    def _perturb_spec(self, need_fp, side):
+        """The perturbation spec of this forward, or None: a dict with the drop probability "p" and the draw's key "seed", "stream",
+        "step" (nnf.channel_keep: the table is a pure function of them).  `need_fp`: False, a spec, or True for p = 0.5 under seed 0,
+        stream 0 and this module's count of such forwards as the step; `side`: a caller-owned dict may carry one under "perturb"
+        (trainer.CPSTrainer: per network and iteration).  The dict is the caller's: the table is left in it under "scale"."""
+        self._training_only(need_fp)
+        if need_fp is True:
+            step = self.__dict__.get("_fp_forwards", 0)
+            self.__dict__["_fp_forwards"] = step + 1
+            return dict(p=0.5, seed=0, stream=0, step=step)
+        if need_fp:
+            return need_fp
+        return side.get("perturb") if side is not None else None
 
     def _side_terms(self, decoder_out, gt, side):
         """`side`: a dict the CALLER of finish() supplies and owns (trainer.CPSTrainer; nothing is kept on the module).  In training mode
@@ -146,11 +183,15 @@ class _VQRePTUnet1x1Base(nn.Module):
 class VQRePTUnet1x1(_VQRePTUnet1x1Base):
     _proto_cls = ReliablePrototypeLoss
 
-    def forward(self, x, gt=None, code_usage_loss=False, percent=None):
-        return self.finish(*self.quantize(self.encode(x)), gt=gt, code_usage_loss=code_usage_loss, percent=percent)
+    def forward(self, x, gt=None, code_usage_loss=False, percent=None, need_fp=False):
+        """`need_fp` (training mode only): True or a perturbation spec appends `output_fp`, the prediction of the feature-perturbation
+        stream (decode), to the usual tuple; False leaves tuple and computation as they are"""
+        self._training_only(need_fp)
+        return self.finish(*self.quantize(self.encode(x)), gt=gt, code_usage_loss=code_usage_loss, percent=percent, need_fp=need_fp)
 
-    def finish(self, feats, loss, usage, gt=None, code_usage_loss=False, percent=None, side=None):
-        decoder_out, output = self.decode(feats)
+    def finish(self, feats, loss, usage, gt=None, code_usage_loss=False, percent=None, side=None, need_fp=False):
+        spec = self._perturb_spec(need_fp, side)
+        decoder_out, output, *fp = self.decode(feats, spec)
         self._side_terms(decoder_out, gt, side)
         prototype_loss = None
         if self.training:
@@ -162,22 +203,27 @@ class VQRePTUnet1x1(_VQRePTUnet1x1Base):
                     entropy = -torch.sum(prob * torch.log(prob + 1e-10), dim=1)
             prototype_loss = self.prototype_loss(decoder_out, gt, percent=percent, entropy=entropy)
         output = self.upsampling(output)
+        fp = tuple(self.upsampling(o) for o in fp)              # (output_fp,) with a perturbation spec, else empty
         if code_usage_loss:
-            return output, loss, self._usage_to_host(usage, output), torch.stack(usage).sum()[None] / len(self.codebook)
-        return output, loss, self._usage_to_host(usage, output), prototype_loss
+            return (output, loss, self._usage_to_host(usage, output), torch.stack(usage).sum()[None] / len(self.codebook)) + fp
+        return (output, loss, self._usage_to_host(usage, output), prototype_loss) + fp
 
 
 class VQRePTUnet1x1v2(_VQRePTUnet1x1Base):
     _proto_cls = ReliablePrototypeLossv2
 
-    def forward(self, x, gt=None, code_usage_loss=False, th=None):
-        return self.finish(*self.quantize(self.encode(x)), gt=gt, code_usage_loss=code_usage_loss, th=th)
+    def forward(self, x, gt=None, code_usage_loss=False, th=None, need_fp=False):
+        """`need_fp`: as VQRePTUnet1x1.forward"""
+        self._training_only(need_fp)
+        return self.finish(*self.quantize(self.encode(x)), gt=gt, code_usage_loss=code_usage_loss, th=th, need_fp=need_fp)
 
-    def finish(self, feats, loss, usage, gt=None, code_usage_loss=False, th=None, side=None):
-        decoder_out, output = self.decode(feats)
+    def finish(self, feats, loss, usage, gt=None, code_usage_loss=False, th=None, side=None, need_fp=False):
+        spec = self._perturb_spec(need_fp, side)
+        decoder_out, output, *fp = self.decode(feats, spec)
         self._side_terms(decoder_out, gt, side)
         prototype_loss = self.prototype_loss(decoder_out, gt, th) if self.training else None
         output = self.upsampling(output)
+        fp = tuple(self.upsampling(o) for o in fp)              # (output_fp,) with a perturbation spec, else empty
         if code_usage_loss:
-            return output, loss, self._usage_to_host(usage, output), torch.stack(usage).sum()[None] / len(self.codebook)
-        return output, loss, self._usage_to_host(usage, output), prototype_loss
+            return (output, loss, self._usage_to_host(usage, output), torch.stack(usage).sum()[None] / len(self.codebook)) + fp
+        return (output, loss, self._usage_to_host(usage, output), prototype_loss) + fp

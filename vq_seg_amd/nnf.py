@@ -3104,3 +3104,169 @@ def boundary_counts(pred, target, num_classes, tol_sq, width_sq, ignore=()):
                 len(ign), *ig, _i32(table[k:k + step], "table", nb * c * 8))
     BOUNDARY_CALLS += 1
     return table
+
+
+# ------------------------------------------------------------------------------------------------
+# Feature perturbation: channel dropout of the decoder's inputs, fused with the concatenation that doubles the batch
+# (vqseg_channel_keep_f, vqseg_channel_dropout_cat_f, vqseg_channel_dropout_fold_f; include/vqseg.h states the definition).
+# The reference's UniMatch stream is decoder(torch.cat((f, nn.Dropout2d(0.5)(f)))) (deprecated/train_UNIMatch.py:172,183-185).
+# CPU tensors, and anything the kernels do not take, use the torch-op form of the SAME definition -- the Philox draw in int64
+# tensor ops, the product and the sum as separate float32 operators -- so a result is the same bits wherever it is computed;
+# VQSEG_OPTS=py_feature_perturb=0 forces that form on the device (A/B runs).
+# ------------------------------------------------------------------------------------------------
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57             # the round multipliers of Philox4x32
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85             # the key's Weyl increments
+_U32 = 0xffffffff
+CHANNEL_DROPOUT_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _mulhilo32(m: int, v: torch.Tensor):
+    """(hi, lo) words of the 64-bit product m * v for a 32-bit constant m and an int64 tensor v of 32-bit values: 16-bit halves keep
+    every intermediate below 2^49"""
+    low = m * (v & 0xffff)
+    mid = m * (v >> 16) + (low >> 16)
+    return mid >> 16, ((mid & 0xffff) << 16) | (low & 0xffff)
+
+
+def philox4x32(counter, key, rounds: int = 10, device=None):
+    """Philox4x32 (ten rounds by default) with torch integer ops: `counter` four and `key` two 32-bit words, each an int or an int64
+    tensor (broadcast against each other) -> the block's four words as int64 tensors.  What channel_keep_kernel computes."""
+    c = [torch.as_tensor(v, dtype=torch.int64, device=device) & _U32 for v in counter]
+    k0, k1 = (torch.as_tensor(v, dtype=torch.int64, device=device) & _U32 for v in key)
+    c0, c1, c2, c3 = torch.broadcast_tensors(*c)
+    for _ in range(rounds):
+        hi0, lo0 = _mulhilo32(PHILOX_M0, c0)
+        hi1, lo1 = _mulhilo32(PHILOX_M1, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + PHILOX_W0) & _U32, (k1 + PHILOX_W1) & _U32
+    return c0, c1, c2, c3
+
+
+def channel_keep_params(p):
+    """-> (threshold, inv_keep) of a drop probability 0 <= p < 1: clamp(round(p 2^32), 0, 2^32 - 1), and 1 / (1 - p) rounded to float32
+    (returned as the Python float of that value)"""
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.floating, np.integer)) or not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"channel_keep: the drop probability must lie in [0, 1), got {p!r}")
+    p = float(p)
+    return min(max(int(np.floor(p * 4294967296.0 + 0.5)), 0), _U32), float(np.float32(1.0 / (1.0 - p)))
+
+
+def _u_int(v, bits, name):
+    if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < (1 << bits):
+        raise ValueError(f"channel_keep: {name} must be an integer in [0, 2^{bits}), got {v!r}")
+    return int(v)
+
+
+def channel_keep(sizes, p, seed, stream, step, device):
+    """The keep / scale table of one perturbed forward -> (flat float32 table, [one (B, C_l) view per level]).  `sizes`: the levels'
+    (B, C_l), one B.  Element e of the flat table (level-major: level l at offset B * sum_{j<l} C_j) is 1 / (1 - p) where word 0 of
+    Philox4x32-10(counter (e, stream, step_lo, step_hi), key (seed_lo, seed_hi)) >= round(p 2^32), else 0: a pure function of its
+    arguments -- no generator state, no host-to-device copy, one launch (vqseg_channel_keep_f) for all levels."""
+    sizes = [(int(b), int(c)) for b, c in sizes]
+    if not sizes or any(b < 1 or c < 1 for b, c in sizes) or len({b for b, _c in sizes}) != 1:
+        raise ValueError(f"channel_keep: sizes must be (B, C_l) pairs of one positive B and positive C_l, got {sizes!r}")
+    threshold, inv_keep = channel_keep_params(p)
+    seed, stream, step = _u_int(seed, 64, "seed"), _u_int(stream, 32, "stream"), _u_int(step, 64, "step")
+    total = sum(b * c for b, c in sizes)
+    if total > _U32:
+        raise ValueError(f"channel_keep: {total} table elements, above 2^32 - 1 (the element index is one counter word)")
+    dev = torch.device(device)
+    if dev.type == "cuda" and py_opt("py_feature_perturb", 1) == 1:
+        flat = torch.empty(total, dtype=torch.float32, device=dev)
+        _launch("vqseg_channel_keep_f", dev, _f32(flat, "scale", total), total, seed, stream, step, threshold, inv_keep)
+    else:
+        e = torch.arange(total, dtype=torch.int64, device=dev)
+        word0 = philox4x32((e, stream, step & _U32, step >> 32), (seed & _U32, seed >> 32), device=dev)[0]
+        flat = torch.where(word0 >= threshold, inv_keep, 0.0).to(torch.float32)
+    views, at = [], 0
+    for b, c in sizes:
+        views.append(flat[at:at + b * c].view(b, c))
+        at += b * c
+    return flat, views
+
+
+def _cl_format(x):
+    """the memory format channel_dropout_cat's output takes: x's when x is dense in one of the two, else contiguous"""
+    if x.is_contiguous() or not x.is_contiguous(memory_format=torch.channels_last):
+        return torch.contiguous_format
+    return torch.channels_last
+
+
+def channel_dropout_supported(x) -> bool:
+    """what the kernels take: a non-empty float32 / bfloat16 (B, C, H, W) tensor on the GPU, NCHW-contiguous or channels_last"""
+    return (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in CHANNEL_DROPOUT_DTYPES and x.numel() > 0
+            and (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last))
+            and x.shape[1] * x.shape[2] * x.shape[3] <= 1 << 40 and x.shape[0] * x.shape[1] <= 1 << 31)
+
+
+def _compute_dtype(t):
+    return torch.float64 if t.dtype == torch.float64 else torch.float32
+
+
+def _dropout_cat_torch(x, scale):
+    n = x.shape[0]
+    s = scale[:, :, None, None]
+    ct = _compute_dtype(x)
+    out = torch.empty((2 * n,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device, memory_format=_cl_format(x))
+    out[:n].copy_(x)
+    out[n:].copy_(torch.where(s == 0, torch.zeros((), dtype=x.dtype, device=x.device), (x.to(ct) * s.to(ct)).to(x.dtype)))
+    return out
+
+
+def _dropout_fold_torch(g, scale):
+    n = g.shape[0] // 2
+    s = scale[:, :, None, None]
+    ct = _compute_dtype(g)
+    return torch.where(s == 0, g[:n], (g[:n].to(ct) + g[n:].to(ct) * s.to(ct)).to(g.dtype))
+
+
+def _dropout_launch(name, src, scale, dst, n, c, h, w):
+    bf = _is_bf16(src)
+    _launch(name, src.device, bf, _T(src, "x" if dst.shape[0] > src.shape[0] else "g", bf=bf, numel=src.numel()),
+            _f32(scale, "scale", n * c), _T(dst, "out", bf=bf, numel=dst.numel()), n, c, h, w, int(not src.is_contiguous()))
+
+
+class _ChannelDropoutCat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale, hip):
+        n, c, h, w = x.shape
+        ctx.save_for_backward(scale)
+        ctx.hip, ctx.fmt = hip, _cl_format(x)
+        if not hip:
+            return _dropout_cat_torch(x, scale)
+        out = torch.empty((2 * n, c, h, w), dtype=x.dtype, device=x.device, memory_format=ctx.fmt)
+        _dropout_launch("vqseg_channel_dropout_cat_f", x, scale, out, n, c, h, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (scale,) = ctx.saved_tensors
+        if not ctx.hip:
+            return _dropout_fold_torch(g, scale), None, None
+        n, c, h, w = g.shape[0] // 2, g.shape[1], g.shape[2], g.shape[3]
+        g = g.contiguous(memory_format=ctx.fmt)              # (the forward's layout; the decoder's gradients arrive in it)
+        gx = torch.empty((n, c, h, w), dtype=g.dtype, device=g.device, memory_format=ctx.fmt)
+        _dropout_launch("vqseg_channel_dropout_fold_f", g, scale, gx, n, c, h, w)
+        return gx, None, None
+
+
+def channel_dropout_cat(x, scale):
+    """torch.cat((x, dropout(x))) in one pass: x (B, C, H, W), scale float32 (B, C) (a level's view of channel_keep's table) ->
+    (2B, C, H, W) of x's dtype and layout with out[:B] = x by bits and out[B + n, c] = +0.0 where scale[n, c] == 0 (a selection: an
+    Inf or NaN activation of a dropped channel does not leak), else x[n, c] * scale[n, c] (the float32 product, rounded once more
+    for bfloat16).  Backward: gx = g[:B] + g[B:] * scale with the product rounded to float32 before the add, and g[:B] alone where
+    the channel was dropped; no gradient flows to `scale`.  float32 / bfloat16 tensors on the GPU run the HIP kernels; everything
+    else (and everything under VQSEG_OPTS=py_feature_perturb=0) the torch-op form of the same definition."""
+    E = _hip.HipLibraryError
+    if not (torch.is_tensor(x) and x.dim() == 4 and x.is_floating_point()):
+        raise E("channel_dropout_cat: x must be a floating-point (B, C, H, W) tensor")
+    if not (torch.is_tensor(scale) and scale.dtype == torch.float32 and tuple(scale.shape) == tuple(x.shape[:2])):
+        raise E(f"channel_dropout_cat: scale must be a float32 (B, C) = {tuple(x.shape[:2])} tensor, got "
+                f"{tuple(scale.shape) if torch.is_tensor(scale) else type(scale).__name__}"
+                f"{' of ' + str(scale.dtype) if torch.is_tensor(scale) else ''}")
+    if scale.device != x.device:
+        raise E(f"channel_dropout_cat: x and scale must be on one device, got {x.device} and {scale.device}")
+    if x.numel() == 0:
+        raise E("channel_dropout_cat: empty tensor")
+    scale = scale.detach().contiguous()
+    return _ChannelDropoutCat.apply(x, scale, channel_dropout_supported(x) and py_opt("py_feature_perturb", 1) == 1)

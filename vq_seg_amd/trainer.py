@@ -138,9 +138,31 @@ class CPSConfig:
                                               # becomes 255, on that network's stream -- both recipes.  Per rank; no collective.  None = today's step: no
                                               # launch is added and no tensor made
     pseudo_connectivity: int = 4              # 4 or 8: which neighbours connect a region
+    feature_perturb: Optional[float] = None   # the drop probability (the reference's: 0.5).  UniMatch's feature-perturbation stream (deprecated/
+                                              # train_UNIMatch.py:172,183-185; models/networks/deeplabv3/net.py:109-116), per network of the CPS pair: in the
+                                              # UNLABELLED training forward every decoder input passes the decoder and the head a second time under channel
+                                              # dropout (one 2B-image decoder pass, nnf.channel_dropout_cat), and that prediction is supervised by the OTHER
+                                              # network's mask: cps_k += feature_perturb_weight * crit(pred_fp_k, mask_other[unlabelled]).  The keep table of
+                                              # network k (0, 1) in iteration i is nnf.channel_keep(seed=cfg.seed, stream=2 * rank + k, step=i): a pure
+                                              # function of (seed, rank, network, iteration, level, sample, channel), drawn on the device in one launch -- no
+                                              # host generator, no host-to-device copy, nothing to checkpoint.  The labelled pair and the pseudo-label pair
+                                              # are untouched.  None = today's step: nothing of it is entered, launches and tensors are the same
+    feature_perturb_weight: float = 0.5       # the reference's weight of the perturbed stream's term
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
+        if self.feature_perturb is not None:
+            try:
+                nnf.channel_keep_params(self.feature_perturb)
+            except ValueError:
+                raise ValueError(f"feature_perturb must be None or a drop probability in [0, 1), got {self.feature_perturb!r}") from None
+            self.feature_perturb = float(self.feature_perturb)
+            if self.unsup_criterion == "conf_ce":
+                raise ValueError("feature_perturb does not combine with unsup_criterion='conf_ce': that option composes the unlabelled half of "
+                                 "the CPS term differently (soft targets across the networks), and the combination is not tested")
+        if isinstance(self.feature_perturb_weight, bool) or not float(self.feature_perturb_weight) >= 0.0 \
+                or float(self.feature_perturb_weight) == float("inf"):
+            raise ValueError(f"feature_perturb_weight must be a finite number >= 0, got {self.feature_perturb_weight!r}")
         if self.pseudo_min_area is not None:
             self.pseudo_min_area = nnf.region_min_area(self.pseudo_min_area, "pseudo_min_area")
         self.pseudo_connectivity = nnf.region_settings(self.pseudo_connectivity, (), "pseudo_connectivity")[0]
@@ -381,11 +403,13 @@ class CPSTrainer:
         segments = self._superpixels(l_input, ul_train)
         salient = self._saliency(l_input, ul_train, segments)
         sup, unsup, sup_con = self._train_forwards(l_input, l_target, ul_train, gt_ul_1, gt_ul_2, kw)
-        fused, ps1, sup_terms, cps_terms = self._terms(l_target, sup, unsup, score_1, score_2, kw, segments, salient)
+        fused, ps1, sup_terms, cps_terms, fp = self._terms(l_target, sup, unsup, score_1, score_2, kw, segments, salient)
         lr = self.sched.get_lr(self.iter)
         for o in self.opts:
             o.param_groups[0]["lr"] = lr
         loss, terms = self._total_loss(fused, sup_terms, cps_terms, [o[1] for o in sup + unsup], [o[3] for o in sup + unsup])
+        if fp is not None:                                              # reported unweighted; cps_loss holds it with feature_perturb_weight
+            terms["fp_loss"] = fp[0] + fp[1]
         if sup_con is not None:                                         # train_supcon_unet.py:143-153: weight * (l_1 + l_2) joins the total
             terms["sup_con_loss"] = (sup_con[0] + sup_con[1]) * cfg.sup_con_loss_weight
             loss = loss + terms["sup_con_loss"]
@@ -549,7 +573,18 @@ class CPSTrainer:
                 self.aux.update(decoder_out_1=sides[0]["decoder_out"], decoder_out_2=sides[1]["decoder_out"], sup_con_1=sup_con[0].detach(),
                                 sup_con_2=sup_con[1].detach())
         g.exchange(gt_ul_2, gt_ul_1, marks=ready)
-        unsup = self._fwd_pair((ul_train, gt_ul_1), (ul_train, gt_ul_2), **kw)
+        if self.cfg.feature_perturb is None:
+            unsup = self._fwd_pair((ul_train, gt_ul_1), (ul_train, gt_ul_2), **kw)
+        else:
+            # cfg.feature_perturb: each network's unlabelled forward decodes 2B images (models: decode with a perturbation spec) and
+            # returns the perturbed stream's prediction as a fifth output.  The key of network k's keep table: (cfg.seed, 2 * rank + k,
+            # iteration) -- drawn on its stream by nnf.channel_keep and left in the dict under "scale"
+            sides = tuple(dict(perturb=dict(p=self.cfg.feature_perturb, seed=self.cfg.seed, stream=2 * vdist.rank() + k, step=self.iter))
+                          for k in range(len(self.models)))
+            unsup = self._fwd_pair((ul_train, gt_ul_1), (ul_train, gt_ul_2), sides=sides, **kw)
+            self.lanes.to_caller(*(d["perturb"]["scale"] for d in sides))
+            if self.cfg.keep_aux:
+                self.aux.update(perturb_scale_1=sides[0]["perturb"]["scale"], perturb_scale_2=sides[1]["perturb"]["scale"])
         if g is OFF:
             self._join()
         return sup, unsup, sup_con
@@ -562,11 +597,23 @@ class CPSTrainer:
             return (lambda p, t: self._weighted(p, t, cls_weight)), False
         if cfg.unsup_criterion is not None:                            # the CPS terms gain a scalar the one-launch combination does not take
             return crt, False
+        if cfg.feature_perturb is not None:                            # likewise: the perturbed stream's term
+            return (crt if cfg.recipe == "v1" else self._ce_dice), False
         if (crt.weight is None and crt.ignore_index is not None and pred.is_cuda and nnf.dice_sums_supported(pred, crt.num_classes)
                 and nnf.py_opt("py_loss_combine", 1) == 1):
             sums = nnf.dice_sums if cfg.recipe == "v1" else nnf.dice_ce_sums
             return (lambda p, t: sums(p, t, crt.ignore_index)), True
         return (crt if cfg.recipe == "v1" else self._ce_dice), False
+
+    def _perturbed_pred(self, pu_fp, segments=None, salient=None):
+        """a network's fp32 prediction of its feature-perturbation stream (cfg.feature_perturb) through the steps its clean unlabelled
+        prediction takes in _own_mask -- the superpixel mean, the salient masking -- on this network's stream; it contributes to no mask"""
+        pu_fp = pu_fp.float()
+        if segments is not None:
+            pu_fp = superpixel.superpixel_mean(pu_fp, segments[1], segments[2])
+        if salient is not None:
+            pu_fp = saliency.salient_masking(pu_fp, salient[1], self.cfg.salient_mask)
+        return pu_fp
 
     def _own_mask(self, ps, pu, kw, segments=None, salient=None):
         """a network's fp32 predictions (labelled, unlabelled, both), the pseudo-label mask it hands to the other network, and that mask
@@ -591,7 +638,9 @@ class CPSTrainer:
 
     def _terms(self, l_target, sup, unsup, score_1, score_2, kw, segments=None, salient=None):
         """Each network's own mask and its two criterion terms (supervised; CPS against the other's mask) on its stream ->
-        fused, pred_sup_1, (sup_1, sup_2), (cps_1, cps_2).  Ends the glue: the caller's stream joins the lanes."""
+        fused, pred_sup_1, (sup_1, sup_2), (cps_1, cps_2), fp.  Ends the glue: the caller's stream joins the lanes.
+        fp: cfg.feature_perturb -- (fp_1, fp_2), network k's criterion of its perturbed stream's prediction against the OTHER network's
+        mask of the unlabelled batch, on its stream, already inside cps_k with cfg.feature_perturb_weight; else None, nothing entered."""
         cfg, g = self.cfg, self._glue
         cls_weight = self._fixed_weight
         if cfg.class_weight == "balanced":
@@ -612,7 +661,22 @@ class CPSTrainer:
             cps_1, sup_1 = (crit(ps1, mask_2[:b_l]) if soft else crit(pred_1, mask_2)), crit(ps1, l_target)
         with g.on(1):
             cps_2, sup_2 = (crit(ps2, mask_1[:b_l]) if soft else crit(pred_2, mask_1)), crit(ps2, l_target)
+        fp = None
+        if cfg.feature_perturb is not None:
+            with g.on(0):
+                pu_fp_1 = self._perturbed_pred(unsup[0][4], segments, salient)
+                fp_1 = crit(pu_fp_1, mask_2[b_l:])
+                cps_1 = cps_1 + cfg.feature_perturb_weight * fp_1
+            with g.on(1):
+                pu_fp_2 = self._perturbed_pred(unsup[1][4], segments, salient)
+                fp_2 = crit(pu_fp_2, mask_1[b_l:])
+                cps_2 = cps_2 + cfg.feature_perturb_weight * fp_2
+            fp = (fp_1, fp_2)
         g.join()
+        if fp is not None:
+            g.to_caller(fp_1, fp_2, pu_fp_1, pu_fp_2, pu1, ps2)
+            if cfg.keep_aux:                                            # what fp_loss and cps_loss are restated from
+                self.aux.update(pred_fp_1=pu_fp_1.detach(), pred_fp_2=pu_fp_2.detach(), pred_ul_1=pu1.detach(), pred_sup_2=ps2.detach())
         g.to_caller(cps_1, sup_1, cps_2, sup_2, ps1, pu2, mask_1, mask_2, score_1, score_2)
         if soft:
             g.to_caller(pu1, ps2)
@@ -633,7 +697,7 @@ class CPSTrainer:
             if cls_weight is not None or not isinstance(self.criterion, DiceLoss):     # what the criterion arms' terms are restated from
                 self.aux.update(pred_1=pred_1.detach(), pred_2=pred_2.detach(), class_weight=cls_weight)
                 g.to_caller(pred_1, pred_2)
-        return fused, ps1, (sup_1, sup_2), (cps_1, cps_2)
+        return fused, ps1, (sup_1, sup_2), (cps_1, cps_2), fp
 
     def _soft_cps(self, cps_1, cps_2, ps1, ps2, pu1, pu2, kw):
         """cfg.unsup_criterion == "conf_ce" -> the two CPS terms with their unlabelled halves added, on the caller's stream after the

@@ -1197,6 +1197,68 @@ int vqseg_boundary_counts_i32(const void* pred, int pred_bytes, const void* targ
                               int n_ignore, int ignore0, int ignore1, int ignore2, int ignore3, int32_t* table, void* stream);
 
 /* ---------------------------------------------------------------------------------- *
+ * Panoptic quality: the overlap of two region labellings, the one-to-one matching at IoU > 0.5 and the per-class instance counts
+ * (vq_seg_amd.nnf.instance_overlap / instance_tally, vq_seg_amd.utils.instances, evaluate.test_loop(panoptic=...)).  The reference
+ * scores pixels only; THIS is the definition, restated by brute force over all pairs in tests/instance_cases.py.  Every table is
+ * integer and exact; iou_sum is a float64 sum in a fixed order, bit-identical between calls; an image's outputs do not depend on the
+ * batch it travels in.
+ *
+ * Inputs: pred and target class maps [b][h * w]; C = num_classes in 1..255; things, a subset of 0..C-1 (default 1..C-1); 0 to 4 void
+ *         values, none of them a thing class (default {255}); connectivity 4 or 8; capacity in 1..65535 rows per image and side.
+ * Limits: those of the region kernels (1 <= b <= 65535, 1 <= h, w <= 4096).
+ *
+ * Regions   prediction regions are the connected regions of pred (the region definition above) with every value that is not a thing
+ *           class ignored; ground-truth regions the same on target.  pred_id / gt_id i32 [b][h * w], pred_count / gt_count i32 [b]
+ *           and pred_table / gt_table i32 [b][capacity][8] are what vqseg_region_ids_i32 / vqseg_region_table_i32 make of them
+ *           (column 0 the value, column 1 the area).  The host makes the "ignored" maps; these entry points start from ids and tables.
+ * Void      void[b][p] = the number of pixels of prediction region p (p < capacity) that belong to no ground-truth region and whose
+ *           target value is a void value (a void value is no thing class, so a void pixel never has a ground-truth id).
+ * IoU       inter(g, p) = the number of pixels with gt_id == g and pred_id == p; union = area[p] - void[p] + area[g] - inter.
+ * Match     p and g match when value[p] == value[g] and 2 * inter > union: integers, strict (2 * inter == union is no match), so a
+ *           region has at most one partner.  match i32 [b][capacity] = the partner of ground-truth row g or -1; inter and uni i32
+ *           [b][capacity] = inter and union of that match, 0 without one; matched i32 [b][capacity] = 1 for a prediction row that
+ *           has a partner, else 0.
+ * Overflow  overflow i32 [b] = 1 when pred_count or gt_count exceeds capacity: the image matches nothing (match -1, inter, uni and
+ *           matched 0), all its counts and sums are 0, and the caller raises capacity.  void is counted all the same.
+ * Counts    tally i32 [b][C][5] per class c = (tp, fp, fn, n_pred, n_gt): tp the matched ground-truth regions of value c, fn the
+ *           unmatched ones, fp the unmatched prediction regions of value c with 2 * void[p] <= area[p] (one lying mostly on void is
+ *           dropped, as in the panoptic reference evaluation), n_pred / n_gt the regions of value c.  iou_sum f64 [b][C] = the sum of
+ *           (double)inter / (double)union over the matches of c, added one by one in rising ground-truth id, starting from 0.0.
+ * Scores (host, float64, counts summed over the images of a data set first): RQ = tp / (tp + fp / 2 + fn / 2), SQ = iou_sum / tp,
+ *           PQ = SQ * RQ, NaN where the denominator is 0; pq, sq, rq the means over the thing classes, NaN skipped.
+ * Maps handed in are never trusted as indices: an id outside [0, capacity) is a pixel of no region, a candidate is range-checked, a
+ * count is clamped to [0, capacity], a value outside [0, C) is counted nowhere.
+ *
+ * vqseg_instance_vote_bits: NB = the bit length of capacity (0 for a capacity outside its limits).
+ * vqseg_instance_vote_i32: votes i32 [b][capacity][NB] and void_count i32 [b][capacity] are zeroed, then one pass over pred_id, gt_id and
+ *     target (target_bytes 1: u8, 4: i32; read only where there is a prediction id and no ground-truth id): a pixel of g and p adds
+ *     1 to votes[b][g][k] for every set bit k of p + 1.  The runs of equal (g, p) among a wave's 64 consecutive pixels are folded,
+ *     gathered per workgroup in a direct-mapped LDS table over 2048 pixels, and the table's slots make the global integer atomics.
+ * vqseg_instance_overlap_i32: two launches.  cand i32 [b][capacity]: bit k of cand + 1 is 2 * votes[b][g][k] > area[g] -- the id of
+ *     the prediction region that holds more than half of g if there is one (a match needs that: union >= area[g]), garbage
+ *     otherwise, hence range-checked: an id in [0, capacity) or -1.  inter i32 [b][capacity] is zeroed, then a pass over both id
+ *     maps counts the pixels with gt_id == g and pred_id == cand[g], with the same folding.
+ * vqseg_instance_match_i32: matched is zeroed; a thread per ground-truth row tests its candidate and writes match, uni, matched
+ *     and inter (in-out: the overlap with the candidate comes in, the overlap of the match goes out).
+ * vqseg_instance_tally_i32: one launch, a workgroup per image: tally, iou_sum (one thread per class walks the rows) and overflow.
+ * Integer atomics only; no workgroup waits for another; every loop is bounded by the pixel count, capacity, NB or C.
+ *
+ * Errors (VQSEG_EINVAL before anything touches a device): null pointers, sizes or a capacity outside the limits, n_void outside
+ * 0..4, a target_bytes other than 1 and 4, cand == inter, num_classes outside 1..255.
+ * ---------------------------------------------------------------------------------- */
+int vqseg_instance_vote_bits(int capacity);
+int vqseg_instance_vote_i32(const int32_t* pred_id, const int32_t* gt_id, const void* target, int target_bytes, int b, int h, int w, int capacity,
+                            int n_void, int void0, int void1, int void2, int void3, int32_t* votes, int32_t* void_count, void* stream);
+int vqseg_instance_overlap_i32(const int32_t* pred_id, const int32_t* gt_id, const int32_t* votes, const int32_t* gt_table, int b, int h, int w,
+                               int capacity, int32_t* cand, int32_t* inter, void* stream);
+int vqseg_instance_match_i32(const int32_t* cand, const int32_t* void_count, const int32_t* pred_table, const int32_t* gt_table,
+                             const int32_t* pred_count, const int32_t* gt_count, int b, int capacity, int32_t* inter, int32_t* match,
+                             int32_t* uni, int32_t* matched, void* stream);
+int vqseg_instance_tally_i32(const int32_t* match, const int32_t* matched, const int32_t* inter, const int32_t* uni, const int32_t* void_count,
+                             const int32_t* pred_table, const int32_t* gt_table, const int32_t* pred_count, const int32_t* gt_count, int b,
+                             int capacity, int num_classes, int32_t* tally, double* iou_sum, int32_t* overflow, void* stream);
+
+/* ---------------------------------------------------------------------------------- *
  * Feature perturbation: channel dropout of the decoder's inputs, fused with the concatenation that doubles the batch
  * (vq_seg_amd.nnf.channel_keep / channel_dropout_cat; the model's decode with a perturbation spec; CPSConfig.feature_perturb).
  * The reference's UniMatch stream is decoder(torch.cat((f, nn.Dropout2d(0.5)(f)))) (deprecated/train_UNIMatch.py:172,183-185;

@@ -186,6 +186,11 @@ SYMBOLS = {
     "vqseg_region_areas_i32": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2),
     "vqseg_region_filter_u8": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
     "vqseg_region_filter_i32": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
+    "vqseg_instance_vote_bits": (c_int, [c_int]),
+    "vqseg_instance_vote_i32": (c_int, [c_void_p] * 3 + [c_int] * 10 + [c_void_p] * 3),
+    "vqseg_instance_overlap_i32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3),
+    "vqseg_instance_match_i32": (c_int, [c_void_p] * 6 + [c_int] * 2 + [c_void_p] * 5),
+    "vqseg_instance_tally_i32": (c_int, [c_void_p] * 9 + [c_int] * 3 + [c_void_p] * 4),
     "vqseg_boundary_seeds_u8": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 2),
     "vqseg_boundary_seeds_i32": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 2),
     "vqseg_boundary_edt_rows_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 3),

@@ -33,6 +33,13 @@ adds contour-level scores of the label map the fused call of the branch returns 
 no second forward is made -- in every mode fused has: test_boundary_f1 / test_boundary_f1s, test_boundary_iou / test_boundary_ious (means
 over all images, NaN skipped; the lists per class, rounded to 5 places) and test_hausdorff.  With None nothing changes: no extra launch, the
 same dict.
+
+`panoptic` (with fused; True for the defaults or a dict of `things`, `void`, `connectivity`, `capacity` as utils.instances.InstanceMeasurement
+takes them) adds object-level scores of the same label map -- the area-filtered one when `min_area` is given; no second forward is made:
+test_pq, test_sq, test_rq (panoptic quality = segmentation quality x recognition quality of the counts summed over all images; the means
+over the thing classes) with test_pqs / test_sqs / test_rqs per class (rounded to 5 places, NaN for a class that is no thing),
+test_count_error (the mean over images and thing classes of |regions predicted - regions in the ground truth|) and
+test_panoptic_overflowed (the number of images with more regions than `capacity`, which are left out: raise it).  With None nothing changes.
 """
 from typing import Dict, Iterable, Tuple
 
@@ -41,7 +48,7 @@ import torch
 import torch.nn.functional as F
 
 from . import nnf
-from .measurement import BoundaryMeasurement, Measurement, confusion_matrix_device
+from .measurement import BoundaryMeasurement, InstanceMeasurement, Measurement, confusion_matrix_device
 from .predict import Predictor
 
 
@@ -75,8 +82,13 @@ def _detail_sheets(img, logits, flips, target, num_classes):
 def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], num_classes: int,
               device=None, amp_dtype=None, fused: bool = False, tta=None, visualize=None, window=None, stride=None,
               blend: str = "linear", window_batch=None, net_size=None, crf=None, min_area=None, min_area_fill=0, connectivity: int = 4,
-              region_ignore=(), boundary=None) -> Dict[str, object]:
+              region_ignore=(), boundary=None, panoptic=None) -> Dict[str, object]:
     """batches yields (images (N, 3, H, W) float in [0, 1], labels (N, Hm, Wm) int class ids)."""
+    if panoptic is not None and not fused:
+        raise ValueError("test_loop: panoptic needs fused=True (the regions are those of the fused path's class maps)")
+    if panoptic is not None and panoptic is not True and not (isinstance(panoptic, dict) and set(panoptic) <= {"things", "void", "connectivity", "capacity"}):
+        raise ValueError(f"test_loop: panoptic is None, True or a dict of things, void, connectivity and capacity, got {panoptic!r}")
+    objects = None if panoptic is None else InstanceMeasurement(num_classes, **({} if panoptic is True else panoptic))
     if boundary is not None and not fused:
         raise ValueError("test_loop: boundary needs fused=True (the contours are those of the fused path's class maps)")
     if boundary is not None and boundary is not True and not (isinstance(boundary, dict) and set(boundary) <= {"tolerance", "width", "ignore"}):
@@ -145,6 +157,8 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
                 conf, hits = _resized_counts(model, img, target, num_classes, amp_dtype)
             if contours is not None:
                 contours.update(label, target.to(label.device))
+            if objects is not None:
+                objects.update(label, target.to(label.device))
             conf_np = conf.cpu().numpy()
             miou, ious = meas.miou(conf_np)
             precision, _ = meas.precision(conf_np)
@@ -167,4 +181,9 @@ def test_loop(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torc
         out["test_boundary_f1"], out["test_boundary_f1s"] = r["boundary_f1"], np.round(r["boundary_f1s"], 5).tolist()
         out["test_boundary_iou"], out["test_boundary_ious"] = r["boundary_iou"], np.round(r["boundary_ious"], 5).tolist()
         out["test_hausdorff"] = r["hausdorff"]
+    if objects is not None:
+        r = objects.result()
+        for key in ("pq", "sq", "rq"):
+            out["test_" + key], out["test_" + key + "s"] = r[key], np.round(r[key + "s"], 5).tolist()
+        out["test_count_error"], out["test_panoptic_overflowed"] = r["count_error"], r["overflowed"]
     return out

@@ -93,3 +93,5 @@ def miou_device(conf: torch.Tensor):
 
 # contour-level scores (boundary F1, boundary IoU, Hausdorff distance) beside the region overlap above: utils/boundary.py
 from .utils.boundary import BoundaryMeasurement  # noqa: E402,F401
+# object-level scores (panoptic quality, instance counts): utils/instances.py
+from .utils.instances import InstanceMeasurement  # noqa: E402,F401

@@ -2966,6 +2966,147 @@ def filter_regions(values, min_area, connectivity=4, ignore=(), fill=0):
 
 
 # ------------------------------------------------------------------------------------------------
+# Panoptic quality: region overlap, matching, counts (vqseg_instance_*; include/vqseg.h states the definition, tests/instance_cases.py
+# restates it)
+# ------------------------------------------------------------------------------------------------
+INSTANCE_MAX_CAPACITY = 65535
+INSTANCE_MAX_CLASSES = 255
+INSTANCE_CALLS = 0            # calls of instance_overlap that reached the library (as REGION_CALLS: for tests, never read by the product)
+
+InstanceTally = namedtuple("InstanceTally", "match inter union matched tally iou_sum overflow")
+
+
+def instance_settings(num_classes, things=None, void=(255,), connectivity=4, capacity=1024, who="instances"):
+    """the checked (num_classes, things, void, connectivity, capacity) of an instance call: 1..255 classes; things a sorted tuple of
+    distinct classes (default 1..C-1); void 0 to 4 integers that fit int32, none of them a thing; 4 or 8; capacity in 1..65535"""
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= int(num_classes) <= INSTANCE_MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes must be an integer in 1..{INSTANCE_MAX_CLASSES}, got {num_classes!r}")
+    c = int(num_classes)
+    if things is None:
+        things = range(1, c)
+    if isinstance(things, (int, np.integer)) and not isinstance(things, bool):
+        things = (things,)
+    try:
+        things = tuple(things)
+    except TypeError:
+        raise ValueError(f"{who}: things must be a sequence of classes in 0..{c - 1}, got {things!r}") from None
+    if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < c for t in things) or len(set(things)) != len(things):
+        raise ValueError(f"{who}: things must be distinct classes in 0..{c - 1}, got {things!r}")
+    things = tuple(sorted(int(t) for t in things))
+    connectivity, void = region_settings(connectivity, void, who)
+    if set(void) & set(things):
+        raise ValueError(f"{who}: a void value cannot be a thing class, got void {void!r} and things {things!r}")
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= int(capacity) <= INSTANCE_MAX_CAPACITY:
+        raise ValueError(f"{who}: capacity must be an integer in 1..{INSTANCE_MAX_CAPACITY}, got {capacity!r}")
+    return c, things, void, connectivity, int(capacity)
+
+
+def instance_supported(pred, target) -> bool:
+    """what the instance kernels take: two maps regions_supported takes, of one shape, on one device"""
+    return regions_supported(pred) and regions_supported(target) and tuple(pred.shape) == tuple(target.shape) and pred.device == target.device
+
+
+def _instance_rows(t, name, who, b, capacity, cols=None, dtype=torch.int32):
+    shape = (b, capacity) if cols is None else (b, capacity, cols)
+    if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape):
+        raise _hip.HipLibraryError(f"{who}: {name} must be a {str(dtype).removeprefix('torch.')} tensor {shape}, got "
+                                   f"{getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))}")
+    return t.detach().contiguous()
+
+
+def _instance_counts(t, name, who, b):
+    if not (torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == (b,)):
+        raise _hip.HipLibraryError(f"{who}: {name} must be an int32 tensor ({b},), got {getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))}")
+    return t.detach().contiguous()
+
+
+def _instance_capacity(capacity, table, who):
+    if capacity is None:
+        capacity = table.shape[1] if torch.is_tensor(table) and table.dim() == 3 else None
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= int(capacity) <= INSTANCE_MAX_CAPACITY:
+        raise ValueError(f"{who}: capacity must be an integer in 1..{INSTANCE_MAX_CAPACITY}, got {capacity!r}")
+    return int(capacity)
+
+
+def instance_overlap(pred_ids, gt_ids, target, pred_table, gt_table, void=(255,), capacity=None):
+    """(cand, inter, void_count), int32 (B, capacity) each, of two id maps int32 (B, H, W) as region_ids makes them, the target class map
+    (uint8 / int32; int64 is converted) and both region tables (B, capacity, 8): cand[b][g] the prediction id that holds more than
+    half of ground-truth region g (or -1; garbage that is a valid id where no region does -- instance_tally's test sorts that out),
+    inter[b][g] the pixels g shares with it, void_count[b][p] the pixels of prediction region p that have no ground-truth id and a
+    target value in `void`.  vqseg_instance_vote_i32 (two memsets, one pass) and vqseg_instance_overlap_i32 (a memset, a small launch,
+    one pass).  Ids outside [0, capacity) are pixels of no region.  Exact, bit-identical from call to call."""
+    global INSTANCE_CALLS
+    who = "instance_overlap"
+    _conn, vd = region_settings(4, void, who)
+    b, h, w = _region_shape(pred_ids, "pred_ids", who, (torch.int32,))
+    _region_shape(gt_ids, "gt_ids", who, (torch.int32,))
+    t, _kind = _region_values(target, who)
+    _region_same(who, pred_ids, gt_ids=gt_ids, target=t)
+    capacity = _instance_capacity(capacity, gt_table, who)
+    pred_table = _instance_rows(pred_table, "pred_table", who, b, capacity, 8)
+    gt_table = _instance_rows(gt_table, "gt_table", who, b, capacity, 8)
+    pred_ids, gt_ids = pred_ids.detach().contiguous(), gt_ids.detach().contiguous()
+    dev, n = pred_ids.device, b * h * w
+    nb = int(lib().vqseg_instance_vote_bits(capacity))
+    pp, gp, tp = _i32(pred_ids, "pred_ids", n), _i32(gt_ids, "gt_ids", n), _T(t, "target", dtype=t.dtype, numel=n)
+    _i32(pred_table, "pred_table", b * capacity * 8)
+    gtp = _i32(gt_table, "gt_table", b * capacity * 8)
+    vv = list(vd) + [0] * (4 - len(vd))
+    if dev.type != "cuda":
+        _launch("vqseg_instance_vote_i32", dev, pp, gp, tp, t.element_size(), b, h, w, capacity, len(vd), *vv, None, None)
+    votes = torch.empty((b, capacity, nb), dtype=torch.int32, device=dev)
+    void_count = torch.empty((b, capacity), dtype=torch.int32, device=dev)
+    cand, inter = torch.empty_like(void_count), torch.empty_like(void_count)
+    vp = _i32(votes, "votes", b * capacity * nb)
+    _launch("vqseg_instance_vote_i32", dev, pp, gp, tp, t.element_size(), b, h, w, capacity, len(vd), *vv, vp, _i32(void_count, "void_count", b * capacity))
+    _launch("vqseg_instance_overlap_i32", dev, pp, gp, vp, gtp, b, h, w, capacity, _i32(cand, "cand", b * capacity), _i32(inter, "inter", b * capacity))
+    INSTANCE_CALLS += 1
+    return cand, inter, void_count
+
+
+def instance_tally(cand, inter, void_count, pred_table, gt_table, pred_counts, gt_counts, num_classes):
+    """InstanceTally(match, inter, union, matched, tally, iou_sum, overflow) from instance_overlap's three tables, both region tables
+    (B, capacity, 8) and both region counts (B,): match[b][g] the partner of ground-truth row g (equal value, 2 * inter > union) or
+    -1, inter / union of the match (0 without one), matched[b][p] 1 for a prediction row with a partner; tally int32 (B, C, 5) = (tp,
+    fp, fn, n_pred, n_gt) per class, iou_sum float64 (B, C) in rising ground-truth id, overflow int32 (B,) = a count exceeds the
+    capacity (such an image matches nothing and counts nothing).  vqseg_instance_match_i32 and vqseg_instance_tally_i32: a memset
+    and two small launches."""
+    who = "instance_tally"
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= int(num_classes) <= INSTANCE_MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes must be an integer in 1..{INSTANCE_MAX_CLASSES}, got {num_classes!r}")
+    c = int(num_classes)
+    if not (torch.is_tensor(cand) and cand.dim() == 2 and 1 <= cand.shape[0] <= 65535 and 1 <= cand.shape[1] <= INSTANCE_MAX_CAPACITY):
+        raise _hip.HipLibraryError(f"{who}: cand must be an int32 tensor (B, capacity) with 1..65535 images and 1..{INSTANCE_MAX_CAPACITY} rows, got "
+                                   f"{tuple(getattr(cand, 'shape', ()))}")
+    b, capacity = cand.shape
+    cand = _instance_rows(cand, "cand", who, b, capacity)
+    inter = _instance_rows(inter, "inter", who, b, capacity).clone()         # the match launch rewrites it
+    void_count = _instance_rows(void_count, "void_count", who, b, capacity)
+    pred_table = _instance_rows(pred_table, "pred_table", who, b, capacity, 8)
+    gt_table = _instance_rows(gt_table, "gt_table", who, b, capacity, 8)
+    pred_counts, gt_counts = _instance_counts(pred_counts, "pred_counts", who, b), _instance_counts(gt_counts, "gt_counts", who, b)
+    dev, rows = cand.device, b * capacity
+    _region_same(who, cand, inter=inter, void_count=void_count)
+    for name, x in (("pred_table", pred_table), ("gt_table", gt_table), ("pred_counts", pred_counts), ("gt_counts", gt_counts)):
+        if x.device != dev:
+            raise _hip.HipLibraryError(f"{who}: all tensors must be on one device, got {dev} and {x.device} ({name})")
+    cp, ip, vp = _i32(cand, "cand", rows), _i32(inter, "inter", rows), _i32(void_count, "void_count", rows)
+    ptp, gtp = _i32(pred_table, "pred_table", rows * 8), _i32(gt_table, "gt_table", rows * 8)
+    pcp, gcp = _i32(pred_counts, "pred_counts", b), _i32(gt_counts, "gt_counts", b)
+    if dev.type != "cuda":
+        _launch("vqseg_instance_match_i32", dev, cp, vp, ptp, gtp, pcp, gcp, b, capacity, ip, None, None, None)
+    match, union, matched = torch.empty_like(cand), torch.empty_like(cand), torch.empty_like(cand)
+    tally = torch.empty((b, c, 5), dtype=torch.int32, device=dev)
+    iou_sum = torch.empty((b, c), dtype=torch.float64, device=dev)
+    overflow = torch.empty((b,), dtype=torch.int32, device=dev)
+    mp, up, dp = _i32(match, "match", rows), _i32(union, "union", rows), _i32(matched, "matched", rows)
+    _launch("vqseg_instance_match_i32", dev, cp, vp, ptp, gtp, pcp, gcp, b, capacity, ip, mp, up, dp)
+    _launch("vqseg_instance_tally_i32", dev, mp, dp, ip, up, vp, ptp, gtp, pcp, gcp, b, capacity, c, _i32(tally, "tally", b * c * 5),
+            _T(iou_sum, "iou_sum", dtype=torch.float64, numel=b * c), _i32(overflow, "overflow", b))
+    return InstanceTally(match, inter, union, matched, tally, iou_sum, overflow)
+
+
+# ------------------------------------------------------------------------------------------------
 # Boundary metrics (vqseg_boundary_*; include/vqseg.h states the definition, tests/boundary_cases.py restates it)
 # ------------------------------------------------------------------------------------------------
 EDT_NONE = 2 ** 31 - 1        # the squared distance on a plane without a seed

@@ -834,7 +834,7 @@ class CPSTrainer:
 
     def evaluate(self, batches, which: str = "student", index: int = 0, fused: bool = False, visualize=None, window=None, stride=None,
                  blend: str = "linear", window_batch=None, net_size=None, crf=None, min_area=None, min_area_fill=0, connectivity: int = 4,
-                 region_ignore=(), boundary=None):
+                 region_ignore=(), boundary=None, panoptic=None):
         """evaluate.test_loop on network `index` of the pair: which="student" scores the trained weights, which="teacher" their
         exponential moving average (cfg.ema_decay), under cfg.amp_dtype.  `batches` yields (images, labels).  `fused`: resize, arg-max
         and confusion counts in one kernel (evaluate.test_loop's opt-in; the same numbers).  `visualize` (with fused): a callable
@@ -843,11 +843,13 @@ class CPSTrainer:
         (with fused; a utils.crf.DenseCRF or True): the dense-CRF refinement is scored, as predict.Predictor(crf=...) predicts.
         `min_area` (with fused; `min_area_fill`, `connectivity`, `region_ignore`): the area-filtered class maps are scored, as
         predict.Predictor(min_area=...) predicts.  `boundary` (with fused; True or a dict of `tolerance`, `width`, `ignore`): boundary F1,
-        boundary IoU and the Hausdorff distance of the scored class maps are added (utils.boundary.BoundaryMeasurement)."""
+        boundary IoU and the Hausdorff distance of the scored class maps are added (utils.boundary.BoundaryMeasurement).  `panoptic` (with
+        fused; True or a dict of `things`, `void`, `connectivity`, `capacity`): panoptic, segmentation and recognition quality and the
+        instance-count error of the scored class maps are added (utils.instances.InstanceMeasurement)."""
         model = self._networks(which)[index]
         return test_loop(model, batches, self.cfg.num_classes, device=self.device, amp_dtype=self.cfg.amp_dtype, fused=fused, visualize=visualize,
                          window=window, stride=stride, blend=blend, window_batch=window_batch, net_size=net_size, crf=crf, min_area=min_area,
-                         min_area_fill=min_area_fill, connectivity=connectivity, region_ignore=region_ignore, boundary=boundary)
+                         min_area_fill=min_area_fill, connectivity=connectivity, region_ignore=region_ignore, boundary=boundary, panoptic=panoptic)
 
     @torch.no_grad()
     def example_image(self, l_input, l_target, ul_input, which: str = "student", index: int = 0, half: bool = True):
